@@ -25,6 +25,7 @@ roofline carries, besides the spec-peak fraction: the HBM traffic of the dominan
 rocprofv3 --pmc child passes; --traffic committed|none skips them) and this device's measured streaming read / write /
 copy ceilings (mpx_bw_probe).
 --quick skips configs2 / e2e / corpus_shard / the CPU baselines / the PMC passes.
+--dump-outputs DIR writes a fixed sample of what the last timed step computed (feature rows, waveform) as DIR/*.npy.
 
     python bench.py --workload corpus --utts 10000      BASELINE configs[3] + configs[4] as the whole job: the corpus is
                                                         LPT-sharded over the ranks (strong scaling), --gpus 1 --utts 1250
@@ -58,6 +59,41 @@ def make_batch(rank):
         pcm, pm, voi = syn.make_utterance(rank * UTTS_PER_GPU + i, dur_s=DUR_S, fs=FS)
         utts.append((pcm, FS, pm, voi))
     return utts
+
+
+DUMP_SEED = 20261015
+DUMP_ROWS = 1024          # frame rows of each feature matrix (of ~64 000)
+DUMP_SAMPLES = 1 << 21    # output samples (of ~15 M)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, feats, pcm):
+    """
+    --dump-outputs DIR: what a caller of the timed path receives from its last step -- the feature matrices mag / real /
+    imag [F x H] and the batch's waveform [total_out] -- as DIR/<name>.npy.  All of it is ~1.6 GB, so a fixed sample
+    (DUMP_SEED) is written: DUMP_ROWS whole frame rows of each matrix (mag.npy, real.npy, imag.npy; the rows in
+    frame_rows.npy) and DUMP_SAMPLES waveform samples (pcm.npy; their positions in pcm_index.npy), float32 as computed,
+    indices as float64.  The inputs are fixed (make_batch), so two builds can be compared file for file.
+    """
+    import torch
+
+    rng = np.random.RandomState(DUMP_SEED)
+    n_frames, n_out = int(feats[0].shape[0]), int(pcm.shape[0])
+    rows = np.sort(rng.choice(n_frames, min(n_frames, DUMP_ROWS), replace=False))
+    pos = np.sort(rng.choice(n_out, min(n_out, DUMP_SAMPLES), replace=False))
+    d_rows = torch.from_numpy(rows).to(pcm.device)
+    arrays = {name: f.index_select(0, d_rows).cpu().numpy() for name, f in zip(("mag", "real", "imag"), feats)}
+    arrays["pcm"] = pcm.index_select(0, torch.from_numpy(pos).to(pcm.device)).cpu().numpy()
+    arrays["frame_rows"] = rows.astype(np.float64)
+    arrays["pcm_index"] = pos.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "bytes": total, "seed": DUMP_SEED,
+            "arrays": {name: list(a.shape) for name, a in arrays.items()}}
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -602,21 +638,25 @@ def measure_e2e(utts):
         out["file_interface"] = corpus_throughput.run(n_utt=int(os.environ.get("BENCH_E2E_UTTS", 128)))
     except Exception as e:
         out["file_interface"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    try:    # the extraction batch path under EIGHT processes (all on this device: a 1-GPU box), files inside the clock
+    try:    # the extraction batch path under N processes (all on this device: a 1-GPU box), files inside the clock.  Every
+        # child opens the device beside this process, so N (BENCH_NPROC, default 4) bounds how many processes hold the GPU
+        # at once: N + 1.
         import file_interface_nproc
 
         n8 = int(os.environ.get("BENCH_NPROC_UTTS", 1024))
+        nproc = max(2, int(os.environ.get("BENCH_NPROC", 4)))
         r1 = file_interface_nproc.run(procs=1, n_utt=n8, share_device=True, reps=3, layouts=("one_directory",))
-        r8 = file_interface_nproc.run(procs=8, n_utt=n8, share_device=True, reps=3,
+        rn = file_interface_nproc.run(procs=nproc, n_utt=n8, share_device=True, reps=3,
                                       layouts=("one_directory", "rank_subdirs", "stage_then_rename"))
-        out["file_interface_8proc"] = dict(r8, one_process_same_corpus=r1["one_directory"],
-                                           note="8 ranks creating 5 files per utterance in ONE directory serialise on its lock "
+        out["file_interface_nproc"] = dict(rn, procs=nproc, one_process_same_corpus=r1["one_directory"],
+                                           note="%d ranks creating 5 files per utterance in ONE directory serialise on its lock "
                                                 "(one_directory = scripts/batch_feature_extraction_for_tts.py --direct); the "
                                                 "script's multi-rank default writes into OUT/.rank<r>/ and moves the files up "
                                                 "at the end (stage_then_rename: the reference's final layout); --rank-subdirs "
-                                                "keeps one subdirectory per rank; best of 3 runs (all listed) with os.sync() before each")
+                                                "keeps one subdirectory per rank; best of 3 runs (all listed) with os.sync() "
+                                                "before each" % nproc)
     except Exception as e:
-        out["file_interface_8proc"] = {"error": "%s: %s" % (type(e).__name__, e)}
+        out["file_interface_nproc"] = {"error": "%s: %s" % (type(e).__name__, e)}
     return out
 
 
@@ -967,7 +1007,12 @@ def main():
                          "measurement), 'committed' = profiles/traffic.json, 'none'")
     ap.add_argument("--pmc-child", action="store_true",
                     help="internal: the short workload the live PMC passes profile (lossless steps + 3 configs[2] steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (a fixed sample of the feature rows and "
+                         "of the waveform) as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.pmc_child:
         sys.exit(_self_launch(args.gpus))   # `python bench.py --gpus N` on its own: fan out like lu.run_multithreaded does
 
@@ -1133,6 +1178,9 @@ def main():
     # THE timed region: W warm-up steps, then exactly K steps between barriers, one step at a time on ONE stream -- the
     # figure a reader can reconcile with rocprofv3's kernel durations (ms_per_step = the dominant kernel + the fix-up)
     dt = timed(one_stream=True)
+    dumped = None
+    if args.dump_outputs and rank == 0 and not args.pmc_child:   # the last timed step's outputs, before anything reuses bufs[0]
+        dumped = dump_outputs(args.dump_outputs, feats, pcm_out)
     dt_ov = dt_idle = dt_two = None
     if not args.pmc_child and not args.no_idle_probe:
         time.sleep(0.5)
@@ -1489,6 +1537,8 @@ def main():
             "per_rank": per_rank,
             "host_contention": host_contention,
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         if full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(utts, _cpu_lossless, "lossless analysis+synthesis of 5 s utterances",
                                                "frames/s")

@@ -22,10 +22,13 @@ def test_header_and_binding_agree():
 def test_library_loads_and_exports_all_symbols():
     if not os.path.isfile(_lib.LIB_PATH):
         build.build()
+    # _lib.load() first: it imports torch, whose HIP runtime the library must bind to.  A bare CDLL as the process's first
+    # load binds it to a second runtime that torch never initialises, and every later test in this process that launches
+    # a kernel fails with "no ROCm-capable device is detected".
+    l2 = _lib.load()
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in _declared():
         assert hasattr(lib, name), name
-    l2 = _lib.load()
     assert l2.mpx_version() == 2
     assert l2.mpx_tables_bytes(4096) == 64 * (2 * 32 + 4) * 4   # one padded row per lane (wave_fft.hpp)
     assert l2.mpx_tables_bytes(2048) == 64 * (2 * 16 + 4) * 4
