@@ -239,6 +239,24 @@ int mpx_roundtrip_lossless_ola(void* stream, int fft_len, const void* tables, co
                                int32_t n_slots, const int32_t* pm_rel, float* out_mag, float* out_real, float* out_imag,
                                float* strips, float* pcm_out, int64_t ld);
 
+/*
+ * One iteration of the pitch-synchronous Griffin-Lim algorithm (magphase.py:3320-3372, the loop body after the first
+ * synthesis): frame f is cut out of sig_in and analysed as by mpx_roundtrip_lossless_ola (frame_pos / frame_left /
+ * frame_right: windowing :74-119 of the previous iteration's signal, with the bounds [0, pm..., len - 1]), the
+ * magnitude of every bin is replaced by target_mag's row f (float32, row pitch ld; bins 0..fft_len/2), keeping the phase
+ * (X == 0: the reference's angle(0) = 0), and the frame is rebuilt (ifft, no fftshift in the reference's centring) and
+ * overlap-added into sig_out by the runs of a synthesis plan over the same epochs (runs / slot_off / slot_runs / pm_rel /
+ * strips: slots mpx_synth_comp_slots(), weights mpx_roundtrip_slot_weights; mpx_ola_fixup afterwards).  The output index
+ * of epoch pm_f is pm_f, so the next iteration reads sig_out with the same frame tables.  sig_in and sig_out must be
+ * different buffers.  phase_out: null, or rows (pitch ld) that receive the phase that was synthesised, angle of the
+ * reference's spectrum (epoch at fft_len/2), bins 0..fft_len/2.  No feature rows are written.
+ */
+int mpx_griffin_lim_ola(void* stream, int fft_len, const void* tables, const float* sig_in, const int64_t* frame_pos,
+                        const int32_t* frame_left, const int32_t* frame_right, int64_t n_frames, const float* target_mag,
+                        const mpx_ola_run* runs, int32_t n_runs, const int32_t* slot_off, const int32_t* slot_runs,
+                        int32_t n_slots, const int32_t* pm_rel, float* phase_out, float* strips, float* sig_out,
+                        int64_t ld);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Compressed-feature synthesis (magphase.py:825-997 synthesis_from_compressed, b_fbank_mel=False, per_phase_type='magphase')
  * ------------------------------------------------------------------------------------------------------------------ */

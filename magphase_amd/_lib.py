@@ -38,6 +38,7 @@ SYMBOLS = (
     "mpx_ola_fixup",
     "mpx_roundtrip_lossless_ola",
     "mpx_roundtrip_slot_weights",
+    "mpx_griffin_lim_ola",
     "mpx_mel_unwarp",
     "mpx_mel_unwarp_rows",
     "mpx_spec_ld",
@@ -174,6 +175,9 @@ def _load_locked():
     lib.mpx_roundtrip_lossless_ola.restype = ctypes.c_int
     lib.mpx_roundtrip_lossless_ola.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, vp, i64, vp, i32, vp, vp, i32, vp, vp, vp,
                                                vp, vp, vp, i64]
+    lib.mpx_griffin_lim_ola.restype = ctypes.c_int
+    lib.mpx_griffin_lim_ola.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp,
+                                        i64]
     lib.mpx_ola_fixup.restype = ctypes.c_int
     lib.mpx_ola_fixup.argtypes = [vp, ctypes.c_int, vp, i32, vp, vp]
     lib.mpx_mel_unwarp.restype = ctypes.c_int

@@ -1639,6 +1639,243 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
 }
 
 // ---------------------------------------------------------------------------------------------
+// One pitch-synchronous Griffin-Lim iteration (magphase.py:3320-3372, the loop body after the first synthesis): the frames
+// of sig_in are analysed as k_roundtrip_pair analyses them (Hann halves around the epoch, epoch rotated to index 0, real
+// FFT in the paired layout), the magnitude of each bin is replaced by the target's, Y = |T| X / |X|, and the frame is
+// rebuilt and overlap-added into sig_out exactly as k_roundtrip_pair does (Hermitian merge, inverse transform, fftshift by
+// register renaming, LDS ring, runs / slots / tickets / head strips; k_ola_fixup afterwards).  Conventions: the reference
+// centres its frames at N/2 and does not fftshift after the iFFT; here the epoch sits at index 0, so X = (-1)^k X_ref and
+// the fftshift of the synthesis undoes the factor -- the magnitude is replaced in this kernel's own convention.  X == 0
+// (the reference's angle(0) = 0) becomes the phasor (-1)^k, never NaN.  phase_out (null except on the last iteration)
+// receives angle(X_ref) for bins 0..M with np.angle's range, rows `ld` floats apart like the target magnitudes.
+// No feature rows are written; target magnitudes are float32 rows of pitch ld.  sig_in and sig_out must not overlap.
+// A separate kernel rather than a template arm of k_roundtrip_pair so that kernel's code stays as it is.
+// ---------------------------------------------------------------------------------------------
+template <int P, bool PHASE>   // PHASE: phase_out is written (the last launch of a run of iterations)
+__global__ __launch_bounds__(kCompPairWaves * 64) void k_griffin_lim_pair(const float* __restrict__ sig,
+                                                                         const long long* __restrict__ fpos,
+                                                                         const int* __restrict__ fleft,
+                                                                         const int* __restrict__ fright,
+                                                                         const RunDesc* __restrict__ runs,
+                                                                         const int* __restrict__ slot_off,
+                                                                         const int* __restrict__ slot_runs, int nslots,
+                                                                         const int* __restrict__ pm_rel,
+                                                                         const float* __restrict__ tw_g,
+                                                                         const float* __restrict__ tmag,
+                                                                         float* __restrict__ phase_out,
+                                                                         float* __restrict__ strips,
+                                                                         float* __restrict__ pcm, long long ld) {
+    constexpr int M = 64 * P, N = 2 * M, R = ring_len<P>(), HP = P / 2;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* tw = smem;
+    const int lane_id = threadIdx.x & 63;
+    const int wave = rfl((int)(threadIdx.x >> 6));
+    const int pair = wave >> 1, half = wave & 1;
+    constexpr bool kCompact = comp_compact<P>();
+    float* xbuf = smem + comp_tw_floats<P>() + wave * comp_xbuf_floats<P>();
+    const unsigned xbuf_byte = 4u * (unsigned)(comp_tw_floats<P>() + wave * comp_xbuf_floats<P>());
+    constexpr int kRing0 = comp_tw_floats<P>() + kCompPairWaves * comp_xbuf_floats<P>();
+    float* ring = smem + kRing0 + pair * R;
+    const unsigned ring_byte = 4u * (unsigned)(kRing0 + pair * R);
+    int* turn = reinterpret_cast<int*>(smem + kRing0 + kCompPairs * R) + pair;
+    pair_kernel_prologue<P, kCompact, MPX_COMP_DIT != 0>(tw, tw_g, smem + kRing0, kCompPairs * R, turn - pair, kCompPairs,
+                                                         kCompPairWaves * 64);
+
+    float wa_s0, wa_c0, ws_s0, ws_c0;   // analysis-side lane twiddle W_N^kappa and synthesis-side conj(W_N^lane)
+    sincospif(-2.0f * (float)kappa<P>(lane_id) / (float)N, &wa_s0, &wa_c0);
+    sincospif(2.0f * (float)lane_id / (float)N, &ws_s0, &ws_c0);
+    const int slot = blockIdx.x * kCompPairs + pair;
+    if (slot >= nslots) return;
+
+    typedef PairCursor Cursor;
+    const int wi_end = slot_off[slot + 1];
+    auto advance = [&](Cursor& c) { pair_cursor_advance(c, wi_end, half, runs, slot_runs); };
+    Cursor cur;
+    cur.wi = slot_off[slot];
+    cur.ticket_base = 0;
+    pair_cursor_settle(cur, wi_end, half, runs, slot_runs);
+    if (!cur.valid) return;
+
+    constexpr int kTile = kCompact ? 32 * P : 64 * P;
+    FrameGeom g = frame_geom(sig, fpos[cur.fi], fleft[cur.fi], fright[cur.fi], N);
+    stage_samples_async(g, 0, kTile, xbuf_byte, lane_id);
+
+    while (cur.valid) {
+        int lane = lane_id;
+        float wa_s = 0.0f, wa_c = 1.0f, ws_s = 0.0f, ws_c = 1.0f;
+        constexpr float lc = 1.0f, ls = 0.0f;
+        if constexpr (kCompact) {
+            asm volatile("" : "+v"(lane));
+        } else {
+            wa_s = wa_s0, wa_c = wa_c0, ws_s = ws_s0, ws_c = ws_c0;
+            asm volatile("" : "+v"(lane), "+v"(wa_s), "+v"(wa_c), "+v"(ws_s), "+v"(ws_c));
+        }
+        Cursor nxt = cur;
+        advance(nxt);
+        const int fi = cur.fi;
+
+        float xr[P], xi[P];
+        {
+            // ---- analysis: X[k] of the own bins k = lane + 64 q and of their mirrors M - k, bin M/2 on lane 0
+            float no_r[HP], no_i[HP], nm_r[HP], nm_i[HP], nh_r, nh_i;
+            MPX_MARK("frame_setup");
+            staged_wait<0>();
+            noise_spectrum_paired<P, true, kCompact>(g, 0, tw, xbuf, xbuf_byte, lane, wa_c, wa_s, no_r, no_i, nm_r, nm_i, nh_r,
+                                                     nh_i, lc, ls);
+            if (P != 32) {   // FFT output lanes hold bins kappa(lane) + 64 q; the merge wants bins lane + 64 q
+                const int src = kappa<P>(lane);
+#pragma unroll
+                for (int q = 0; q < HP; ++q) {
+                    no_r[q] = __shfl(no_r[q], src);
+                    no_i[q] = __shfl(no_i[q], src);
+                    nm_r[q] = __shfl(nm_r[q], src);
+                    nm_i[q] = __shfl(nm_i[q], src);
+                }
+                nh_r = __shfl(nh_r, src);
+                nh_i = __shfl(nh_i, src);
+            }
+            mpx_pin(no_r), mpx_pin(no_i), mpx_pin(nm_r), mpx_pin(nm_i);
+            MPX_MARK("magnitude_merge");
+            // ---- per bin pair q: Y = T X / |X| (X == 0 -> T (-1)^k), then the pair's step of the Hermitian merge as in
+            // k_roundtrip_pair.  Bin k = lane + 64 q and its mirror M - k share the parity of lane (M is even).
+            const bool lane0 = (lane == 0);
+            const float sgn = (lane & 1) ? -1.0f : 1.0f;
+            const float* trow = tmag + (long long)fi * ld;
+            float* prow = PHASE ? phase_out + (long long)fi * ld : nullptr;
+            if constexpr (PHASE) {   // angle(X_ref), X_ref = (-1)^k X; X == 0 -> 0.  One bin pair at a time (the
+                // barrier keeps the compiler from interleaving the arctangents, which spills at P = 32)
+                auto ang = [](float x_r, float x_i, float s) {
+                    return (x_r == 0.0f && x_i == 0.0f) ? 0.0f : atan2f(s * x_i, s * x_r);
+                };
+#pragma unroll
+                for (int q = 0; q < HP; ++q) {
+                    const int k = lane + 64 * q;
+                    prow[k] = ang(no_r[q], no_i[q], sgn);
+                    prow[M - k] = ang(nm_r[q], nm_i[q], sgn);
+                    asm volatile("" ::: "memory");
+                }
+                if (lane0) prow[M / 2] = ang(nh_r, nh_i, 1.0f);
+            }
+            auto replace = [](float& x_r, float& x_i, float t, float s) {
+                const bool z = (x_r == 0.0f) && (x_i == 0.0f);
+                // largest component below 2^-60: scaled by 2^100 first, so that |u|^2 of any nonzero X (denormals
+                // included: |u| >= 2^-49) is a normal float above the 1e-37 floor and |Y| is T, not less
+                const float sc = (fmaxf(fabsf(x_r), fabsf(x_i)) < 0x1p-60f) ? 0x1p100f : 1.0f;
+                const float u_r = x_r * sc, u_i = x_i * sc;
+                const float r = __builtin_amdgcn_rsqf(fmaxf(u_r * u_r + u_i * u_i, 1.0e-37f));
+                x_r = z ? t * s : t * (u_r * r);
+                x_i = z ? 0.0f : t * (u_i * r);
+            };
+            if constexpr (kCompact) {   // kappa(lane) == lane: the synthesis-side twiddle is the conjugate of the split's
+                const float4 pk = tw_half_pad<P>(tw, lane);
+                ws_c = pk.x;
+                ws_s = -pk.y;
+            }
+            float zr[HP], zi[HP];   // Z[M - k]
+#pragma unroll
+            for (int q = 0; q < HP; ++q) {
+                const int k = lane + 64 * q;
+                float x_r = no_r[q], x_i = no_i[q], p_r = nm_r[q], p_i = nm_i[q];
+                replace(x_r, x_i, trow[k], sgn);
+                replace(p_r, p_i, trow[M - k], sgn);
+                if (q == 0) {   // DC and Nyquist: imaginary parts dropped (Q5)
+                    x_i = lane0 ? 0.0f : x_i;
+                    p_i = lane0 ? 0.0f : p_i;
+                }
+                const float er = x_r + p_r, ei = x_i - p_i, tr = x_r - p_r, ti = x_i + p_i;
+                const float cq = cos2p<P>(q), sq = sin2p<P>(q);
+                const float wr = ws_c * cq - ws_s * sq, wi = ws_c * sq + ws_s * cq;
+                const float orr = wr * tr - wi * ti, oi = wr * ti + wi * tr;
+                xr[q] = er - oi;
+                xi[q] = ei + orr;
+                zr[q] = er + oi;
+                zi[q] = orr - ei;
+            }
+            // bin M/2 (lane 0; M/2 = 32 P is even): Y, then Z = 2 conj(Y); then the hand-over of Z[M - k] to the lanes
+            // that own those registers
+            replace(nh_r, nh_i, trow[M / 2], 1.0f);
+            const float hr = 2.0f * nh_r, hi = -2.0f * nh_i;
+            const int src_lane = (64 - lane) & 63;
+#pragma unroll
+            for (int r = HP; r < P; ++r) {
+                const float pr = lane0 ? ((r == HP) ? hr : zr[P - r]) : zr[P - 1 - r];
+                const float pi = lane0 ? ((r == HP) ? hi : zi[P - r]) : zi[P - 1 - r];
+                xr[r] = __shfl(pr, src_lane);
+                xi[r] = __shfl(pi, src_lane);
+            }
+        }
+        mpx_pin(xr), mpx_pin(xi);
+        MPX_MARK("fft_inverse");
+        constexpr bool kDit = kCompact && MPX_COMP_DIT;
+        if constexpr (kDit) {
+            constexpr int LBJ = ilog2(P);
+            float yr[P], yi[P];
+#pragma unroll
+            for (int j = 0; j < P; ++j) {
+                yr[brev(j, LBJ)] = xr[j];
+                yi[brev(j, LBJ)] = xi[j];
+            }
+            const float4 pk = tw_half_pad<P>(tw, lane);
+            wave_fft_dit_compact_front<P, +1>(yr, yi, tw, xbuf, lane, pk.z, pk.w);
+#pragma unroll
+            for (int j = 0; j < P; ++j) {
+                xr[j] = yr[j];
+                xi[j] = yi[j];
+            }
+        } else if constexpr (kCompact) {
+            const float4 pk = tw_half_pad<P>(tw, lane);
+            wave_fft_front_compact<P, +1>(xr, xi, tw, xbuf, lane, pk.z, pk.w);
+        } else {
+            wave_fft_front<P, +1>(xr, xi, tw, xbuf, lane);
+        }
+        if (nxt.valid) {   // the exchange buffer is idle from here on: start the copy of the next frame's samples
+            g = frame_geom(sig, fpos[nxt.fi], fleft[nxt.fi], fright[nxt.fi], N);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            stage_samples_async(g, 0, kTile, xbuf_byte, lane);
+        }
+        if constexpr (kDit) wave_fft_dit_back<P, +1>(xr, xi);
+        else fft_inreg<P, +1>(xr, xi);
+
+        // ---- ordered section: wait for this frame's ticket (as k_roundtrip_pair)
+        mpx_pin(xr), mpx_pin(xi);
+        MPX_MARK("ticket");
+        const RunDesc rd = runs[cur.ci];
+        float* strip = strips + rd.strip_off;
+        float* pcm0 = pcm + rd.out_base;
+        const int ticket = cur.ticket_base + (fi - cur.fb);
+        const int x = pm_rel[fi] - cur.x0;   // strip position of the frame's first sample
+        const int target = x & ~63;
+        const int flushed = (fi == cur.fb) ? 0 : ((pm_rel[fi - 1] - cur.x0) & ~63);
+        asm volatile("" ::"s"(x), "s"(flushed), "s"(rd.head_end), "s"(rd.out_lo), "s"(rd.out_hi), "s"(rd.flush_end));
+        while (__hip_atomic_load(turn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != ticket)
+            __builtin_amdgcn_s_sleep(1);
+        asm volatile("" ::: "memory");
+        MPX_MARK("flush");
+        if (flushed < target) flush_ring<R>(ring, strip, pcm0, rd.head_end, rd.out_lo, rd.out_hi, flushed, target, lane);
+        wave_sync();
+        MPX_MARK("overlap_add");
+        constexpr float kScale = 0.5f / (float)M;   // the inverse transform's scale, on the overlap-add's multiply-add
+        auto plain_add = [](float o, float v, int) { return fmaf(v, kScale, o); };
+        auto all_rows = [](int) { return true; };
+        {
+            constexpr int CH = (P < MPX_COMP_CH) ? P : MPX_COMP_CH;
+            const RingAddr ra = ring_addr<P>(ring_byte, x, lane);
+            ring_add_plane<P, 0, CH, kDit, true>(smem, ra, xr, lane, plain_add, all_rows);
+            ring_add_plane<P, 1, CH, kDit, true>(smem, ra, xi, lane, plain_add, all_rows);
+        }
+        wave_sync();
+        if (fi == cur.fe - 1) {   // last frame of the run: stream out the rest, leave the ring cleared
+            flush_ring<R>(ring, strip, pcm0, rd.head_end, rd.out_lo, rd.out_hi, target, rd.flush_end, lane);
+            wave_sync();
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __hip_atomic_store(turn, ticket + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        MPX_MARK("loop_end");
+        cur = nxt;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Mel warp on the matrix cores: out[F x nout] = ln-prologue(x)[F x H] . W^T[H x nout], v_mfma_f32_16x16x4_f32.
 // One workgroup = 64 output frames x up to 64 outputs; the reduction runs over the H bins in chunks of 64.  Per chunk
 // the 256 threads stage the prologue values and the W slab into LDS as [row][k] (k contiguous, row stride 68 floats:
@@ -2519,6 +2756,39 @@ int mpx_roundtrip_lossless_ola(void* stream, int fft_len, const void* tables, co
     else if (P == 16) MPX_LAUNCH_RT(16);
     else MPX_LAUNCH_RT(8);
 #undef MPX_LAUNCH_RT
+    MPX_HIP_CHECK(hipGetLastError());
+    return MPX_OK;
+}
+
+int mpx_griffin_lim_ola(void* stream, int fft_len, const void* tables, const float* sig_in, const int64_t* frame_pos,
+                        const int32_t* frame_left, const int32_t* frame_right, int64_t n_frames, const float* target_mag,
+                        const mpx_ola_run* runs, int32_t n_runs, const int32_t* slot_off, const int32_t* slot_runs,
+                        int32_t n_slots, const int32_t* pm_rel, float* phase_out, float* strips, float* sig_out,
+                        int64_t ld) {
+    const int P = p_of(fft_len);
+    if (!P) return fail(MPX_ERR_ARG, "mpx_griffin_lim_ola: fft_len must be 1024, 2048 or 4096%s");
+    if (n_frames < 0 || n_runs < 0 || n_slots < 0) return fail(MPX_ERR_ARG, "mpx_griffin_lim_ola: negative count%s");
+    if (ld < fft_len / 2 + 1) return fail(MPX_ERR_ARG, "mpx_griffin_lim_ola: ld < fft_len/2 + 1%s");
+    if (n_frames == 0 || n_runs == 0 || n_slots == 0) return MPX_OK;
+    if (!tables || !sig_in || !frame_pos || !frame_left || !frame_right || !target_mag || !runs || !slot_off ||
+        !slot_runs || !pm_rel || !strips || !sig_out)
+        return fail(MPX_ERR_ARG, "mpx_griffin_lim_ola: null pointer%s");
+    if (sig_in == sig_out) return fail(MPX_ERR_ARG, "mpx_griffin_lim_ola: sig_in and sig_out must be different buffers%s");
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 pgrid((n_slots + kCompPairs - 1) / kCompPairs), pblock(kCompPairWaves * 64);
+#define MPX_LAUNCH_GL(PP)                                                                                              \
+    do {                                                                                                             \
+        auto KK = phase_out ? k_griffin_lim_pair<PP, true> : k_griffin_lim_pair<PP, false>;                          \
+        if (int rc = set_lds(KK, lds_bytes_comp_pair<PP>())) return rc;                                              \
+        hipLaunchKernelGGL(KK, pgrid, pblock, lds_bytes_comp_pair<PP>(), s, sig_in,                                  \
+                           (const long long*)frame_pos, frame_left, frame_right, (const RunDesc*)runs, slot_off,     \
+                           slot_runs, (int)n_slots, pm_rel, (const float*)tables, target_mag, phase_out, strips,     \
+                           sig_out, (long long)ld);                                                                  \
+    } while (0)
+    if (P == 32) MPX_LAUNCH_GL(32);
+    else if (P == 16) MPX_LAUNCH_GL(16);
+    else MPX_LAUNCH_GL(8);
+#undef MPX_LAUNCH_GL
     MPX_HIP_CHECK(hipGetLastError());
     return MPX_OK;
 }

@@ -1331,6 +1331,24 @@ class Engine:
                 "mpx_roundtrip_lossless_ola")
         return pcm_out
 
+    def griffin_lim_ola(self, fft_len, plan, target, sig_in, sig_out, strips, phase_out=None):
+        """One Griffin-Lim iteration (mpx_griffin_lim_ola): plan (GriffinLimPlan) frames of sig_in analysed, magnitudes
+        replaced by target's rows, overlap-added into sig_out by plan.iter's runs; ola_fixup(plan.iter, ...) afterwards."""
+        torch = _torch()
+        tab = self.tables(fft_len)
+        it = plan.iter
+        with torch.cuda.device(self.device):
+            _lib.check(
+                self.lib.mpx_griffin_lim_ola(self.stream_ptr(), int(fft_len), tab.data_ptr(), sig_in.data_ptr(),
+                                             plan.frame_pos.data_ptr(), plan.frame_left.data_ptr(),
+                                             plan.frame_right.data_ptr(), int(plan.total_frames), target.data_ptr(),
+                                             it.runs.data_ptr(), int(it.n_runs), it.slot_off.data_ptr(),
+                                             it.slot_runs.data_ptr(), int(it.n_slots), plan.pm_rel.data_ptr(),
+                                             phase_out.data_ptr() if phase_out is not None else None, strips.data_ptr(),
+                                             sig_out.data_ptr(), int(target.stride(0))),
+                "mpx_griffin_lim_ola")
+        return sig_out
+
     def ola_fixup(self, fft_len, plan, strips, pcm_out):
         torch = _torch()
         with torch.cuda.device(self.device):
@@ -1731,6 +1749,68 @@ class LosslessRoundTripPlan:
         e.roundtrip_lossless_ola(self.fft_len, a, s, feats, strips, out)
         e.ola_fixup(self.fft_len, s, strips, out)
         return feats, out
+
+
+class _OlaRuns:
+    """Run / slot tables of one overlap-add kernel over a GriffinLimPlan's frames (pm_rel shared with the plan)."""
+
+
+class GriffinLimPlan:
+    """
+    Device tables of griffin_lim (magphase.py:3320-3372) for a batch of utterances sharing fft_len: shifts -> epochs ->
+    ola bookkeeping and the analysis frame tables of every iteration (hostmath.griffin_lim_plan), the runs of the first
+    synthesis (k_synth_ola_pair's slots, mpx_synthesis_lossless_ola) and of the iterations (k_griffin_lim_pair's: the
+    round-trip kernel's slots and weights), two signal buffers (ping-pong: an iteration never reads the buffer it writes)
+    and the head strips.  run() returns (signal, phase rows or None).
+    """
+
+    def __init__(self, engine, shift_list, fft_len, frames_per_run=None):
+        self.engine = e = engine
+        self.fft_len = N = int(fft_len)
+        r = hm.griffin_lim_plan(shift_list, N)
+        self.v_pm = r["v_pm"]
+        self.out_len = [int(x) for x in r["out_len"]]
+        self.out_off_host = r["out_off"]
+        self.frame_off = r["frame_off"]
+        self.total_out = int(self.out_off_host[-1])
+        self.total_frames = int(self.frame_off[-1])
+        up = [("pm_rel", np.concatenate(r["pm_rel"]), np.int32), ("frame_pos", r["frame_pos"], np.int64),
+              ("frame_left", r["frame_left"], np.int32), ("frame_right", r["frame_right"], np.int32)]
+        for k, t in e.to_device_packed(up).items():
+            setattr(self, k, t)
+        self.synth, self.iter = _OlaRuns(), _OlaRuns()
+        starts = [int(x) for x in r["out_start"]]
+        for runs, n_slots, w in ((self.synth, e.synth_ola_slots(), e.synth_ola_slot_weights()),
+                                 (self.iter, e.synth_comp_slots(), e.synth_ola_slot_weights(comp="roundtrip"))):
+            up = []
+            _plan_ola_runs(runs, r["pm_rel"], starts, self.out_len, self.out_off_host, N, n_slots, frames_per_run, up,
+                           weights=w)
+            for k, t in e.to_device_packed(up).items():
+                setattr(runs, k, t)
+            runs.pm_rel = self.pm_rel
+        self.strips = e.empty((max(self.synth.strip_floats, self.iter.strip_floats, 1),))
+        self.bufs = (e.empty((max(self.total_out, 1),)), e.empty((max(self.total_out, 1),)))
+
+    def run(self, target, init, niters, phase_rows=False):
+        """target: device magnitude rows [F x H] (row pitch target.stride(0)); init: a LIST [mag', phasor real, phasor imag]
+        of rows of the same pitch for the first synthesis (hostmath.griffin_lim_fold), emptied once that synthesis is
+        queued -- nothing else reads them, so their memory goes back to the allocator (stream-ordered) before the
+        iterations; niters >= 1 syntheses.  phase_rows (niters >= 2): rows of the same pitch receive the phase
+        synthesised last (written by the last iteration), allocated after the init rows are released.
+        Returns (signal buffer: total_out samples, utterance u at out_off_host[u]; phase rows or None)."""
+        e, N = self.engine, self.fft_len
+        a, b = self.bufs
+        e.synthesis_lossless_ola(N, init[0], init[1], init[2], self.synth, self.strips, a)
+        e.ola_fixup(N, self.synth, self.strips, a)
+        init.clear()
+        phase = None
+        if phase_rows and niters > 1:
+            phase = e.empty((max(self.total_frames, 1), int(target.stride(0))))[:self.total_frames, :target.shape[1]]
+        for i in range(1, int(niters)):
+            e.griffin_lim_ola(N, self, target, a, b, self.strips, phase_out=phase if i == niters - 1 else None)
+            e.ola_fixup(N, self.iter, self.strips, b)
+            a, b = b, a
+        return a[:self.total_out], phase
 
 
 # ======================================================================================================

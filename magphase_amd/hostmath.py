@@ -741,3 +741,120 @@ def merlin_tables(dim, fs, pf_coef=1.4, fft_len=4096):
         cf = np.cos(np.outer(np.arange(dim), np.linspace(0, np.pi, num=dim)))
         _MERLIN_CACHE[key] = dict(c1=c1, lifter=lifter, g=fq @ dcos, wk=wk, cf=cf, alpha=alpha)
     return _MERLIN_CACHE[key]
+
+
+# ======================================================================================================
+# Griffin-Lim (magphase.py:3320-3372)
+# ======================================================================================================
+GL_FFT_LENS = (1024, 2048, 4096)
+
+
+def griffin_lim_shifts(m_mag, v_shift):
+    """
+    Host checks of griffin_lim's inputs (magphase.py:3327-3330): returns (v_shift int64 rounded as lu.round_to_int, N).
+    ValueError where the reference fails, or would fail at its first analysis (libaudio.py:122-140: np.zeros(N/2 - left)
+    and np.zeros(N/2 - right - 1)), and where the port does not go (fft lengths without a kernel, no frames, negative
+    shifts).  The right bound of the last frame is its own shift (ola's last shift repeated), of a lone frame its epoch.
+    """
+    m_mag = np.asarray(m_mag)
+    if m_mag.ndim != 2:
+        raise ValueError("griffin_lim: m_mag must be a 2-D [frames x bins] matrix")
+    nfrms, H = m_mag.shape
+    if nfrms == 0:
+        raise ValueError("griffin_lim: no frames")
+    N = 2 * (H - 1)
+    if N not in GL_FFT_LENS:
+        raise ValueError("griffin_lim: fft_len 2 (H - 1) = %d; supported: %s" % (N, GL_FFT_LENS))
+    v = np.atleast_1d(np.asarray(v_shift, dtype=np.float64))
+    if v.ndim != 1 or v.size != nfrms:
+        raise ValueError("griffin_lim: len(v_shift) = %d != m_mag.shape[0] = %d" % (v.size, nfrms))
+    if not np.all(np.isfinite(v)):
+        raise ValueError("griffin_lim: v_shift must be finite")
+    v = round_to_int(v).astype(np.int64)
+    if np.any(v < 0):
+        raise ValueError("griffin_lim: negative shifts")
+    right = np.append(v[1:], v[-1])
+    if v[0] > N // 2 or np.any(right > N // 2 - 1):
+        raise ValueError("griffin_lim: shifts outside the reference's domain (v_shift[0] <= %d, v_shift[1:] <= %d and a "
+                         "lone frame's shift <= %d: np.zeros of a negative length in frm_list_to_matrix)"
+                         % (N // 2, N // 2 - 1, N // 2 - 1))
+    return v, N
+
+
+def griffin_lim_plan(shift_list, N):
+    """
+    Bookkeeping of a batch of Griffin-Lim utterances (integer shift vectors, one fft_len N): per utterance v_pm =
+    cumsum(v_shift) (la.shift_to_pm), ola's (pm_rel, out_start, out_len) (ola_plan), the concatenated output offsets
+    out_off, and the analysis tables of windowing(v_sig, v_pm) on the concatenated signal: frame_pos = out_off[u] + pm_f,
+    frame_left / frame_right with the bounds [0, pm..., out_len - 1] (magphase.py:74-119).  In the reference's domain
+    out_start = N/2 - pm_0 >= 0, so ola puts epoch pm_f at output index pm_f: the frame tables index straight into the
+    previous iteration's output.
+    """
+    v_pm, pm_rel, starts, lens, pos, left, right, nfr = [], [], [], [], [], [], [], []
+    for v in shift_list:
+        pm = np.cumsum(np.asarray(v, dtype=np.int64))
+        rel, start, out_len = ola_plan(pm, N)
+        v_pm.append(pm), pm_rel.append(rel), starts.append(start), lens.append(out_len), nfr.append(pm.size)
+    out_off = np.concatenate(([0], np.cumsum(lens))).astype(np.int64)
+    for u, pm in enumerate(v_pm):
+        p, lft, rgt = frame_bounds(pm, lens[u])
+        pos.append(p + out_off[u]), left.append(lft), right.append(rgt)
+    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)   # noqa: E731
+    return {"v_pm": v_pm, "pm_rel": pm_rel, "out_start": np.asarray(starts, dtype=np.int64),
+            "out_len": np.asarray(lens, dtype=np.int64), "out_off": out_off,
+            "frame_off": np.concatenate(([0], np.cumsum(nfr))).astype(np.int64),
+            "frame_pos": cat(pos, np.int64), "frame_left": cat(left, np.int64), "frame_right": cat(right, np.int64)}
+
+
+def griffin_lim_initial_phase(phase_init, m_mag, rng=np.random):
+    """
+    magphase.py:3334-3352: the initial phase of one utterance as the reference builds it, before its Hermitian extension.
+    Returns (phase, full): full=True -> [F x N] (`'random'`: drawn from numpy's global generator, 'linear'), full=False ->
+    [F x H] rows that the reference extends with la.add_hermitian_half(.., 'phase') -- columns 0 and H - 1 ZEROED IN PLACE
+    (an ndarray init is the caller's array: the reference mutates it, and so does this).  'min_phase' returns None
+    (computed on the device: mpx_min_phase).
+    """
+    F, H = np.shape(m_mag)
+    N = 2 * (H - 1)
+    if isinstance(phase_init, str):
+        if phase_init == "random":
+            return 2 * np.pi * (rng.rand(F, N) - 0.5), True
+        if phase_init == "linear":
+            row = np.zeros((1, N))
+            row[:, N // 2] = 1.0
+            return np.broadcast_to(np.angle(np.fft.fft(row)), (F, N)), True
+        if phase_init == "min_phase":
+            return None, False
+    phase_init[:, 0] = 0
+    phase_init[:, -1] = 0
+    return phase_init, False
+
+
+def griffin_lim_fold(m_mag, phase, full):
+    """
+    The first synthesis of griffin_lim, frames = ifft(M e^{j phi}).real with phi not necessarily Hermitian, restated as
+    the existing lossless synthesis fftshift(ifft(hermitian(mag' . phasor))) (mpx_synthesis_lossless_ola): .real of the
+    iFFT is the iFFT of H_k = M_k (e^{j phi_k} + e^{-j phi_{N-k}}) / 2 (H_0 = M_0 cos phi_0, H_{N/2} = M_{N/2} cos phi_{N/2}),
+    H = M c; with mag' = M |c| and phasor c (-1)^k / |c| (|c| = 0: mag' = 0, phasor 0) the fftshift's (-1)^k cancels.
+    full=False: phase is [F x H] of a Hermitian extension with phi_0 = phi_{N/2} = 0 (c = e^{j phi}).
+    Returns float64 (mag', phasor real, phasor imag), each [F x H].
+    """
+    m_mag = np.asarray(m_mag, dtype=np.float64)
+    F, H = m_mag.shape
+    N = 2 * (H - 1)
+    sgn = np.where(np.arange(H) % 2 == 0, 1.0, -1.0)
+    if full:
+        ph = np.asarray(phase, dtype=np.float64)
+        mir = ph[:, (N - np.arange(H)) % N]   # phi_{N-k} for k = 0..N/2
+        cr = 0.5 * (np.cos(ph[:, :H]) + np.cos(mir))
+        ci = 0.5 * (np.sin(ph[:, :H]) - np.sin(mir))
+        cr[:, 0], ci[:, 0] = np.cos(ph[:, 0]), 0.0
+        cr[:, -1], ci[:, -1] = np.cos(ph[:, N // 2]), 0.0
+        a = np.hypot(cr, ci)
+        nz = a > 0
+        inv = np.where(nz, 1.0 / np.where(nz, a, 1.0), 0.0)
+        return m_mag * a, cr * inv * sgn, ci * inv * sgn
+    ph = np.array(phase, dtype=np.float64)
+    ph[:, 0] = 0.0
+    ph[:, -1] = 0.0
+    return m_mag.copy(), np.cos(ph) * sgn, np.sin(ph) * sgn

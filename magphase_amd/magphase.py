@@ -19,8 +19,8 @@ import numpy as np
 from . import hostmath as hm
 from . import libaudio as la
 from . import libutils as lu
-from .engine import (CompressedAnalysisPlan, CompressedSynthesisPlan, LosslessAnalysisPlan, LosslessRoundTripPlan,
-                     LosslessSynthesisPlan,
+from .engine import (CompressedAnalysisPlan, CompressedSynthesisPlan, GriffinLimPlan, LosslessAnalysisPlan,
+                     LosslessRoundTripPlan, LosslessSynthesisPlan,
                      get_engine)
 
 _epoch_provider = None
@@ -335,6 +335,138 @@ def copy_synthesis_lossless_batch(utts, fft_len=None, engine=None, return_device
             sig = h_pcm[oa:ob]
         out.append((feats + (a.v_f0[u], a.fs[u], a.v_shift[u].astype(int)), sig))
     return out
+
+
+_GL_INITS = ("random", "linear", "min_phase")
+
+
+def _griffin_lim_check(utts, win_func, phase_init, niters):
+    """All of griffin_lim_batch's argument checks, on the host, before any draw or device call.  Returns
+    (shifts, inits, N)."""
+    if win_func is not np.hanning:
+        raise ValueError("griffin_lim: only win_func=np.hanning is supported")
+    if isinstance(niters, bool) or not isinstance(niters, (int, np.integer)) or niters < 1:
+        raise ValueError("griffin_lim: niters must be an integer >= 1")
+    if isinstance(phase_init, (list, tuple)):
+        if len(phase_init) != len(utts):
+            raise ValueError("griffin_lim_batch: one phase_init per utterance")
+        inits = list(phase_init)
+    else:
+        inits = [phase_init] * len(utts)
+    shifts, N = [], None
+    for (m_mag, v_shift), init in zip(utts, inits):
+        v, n = hm.griffin_lim_shifts(m_mag, v_shift)
+        if N is not None and n != N:
+            raise ValueError("griffin_lim_batch: all utterances of a call must share fft_len (bucket by bins)")
+        N = n
+        if isinstance(init, str):
+            if init not in _GL_INITS:
+                raise ValueError("griffin_lim: unknown phase_init %r (%s or an ndarray)" % (init, ", ".join(_GL_INITS)))
+        elif isinstance(init, np.ndarray):
+            if init.shape != np.shape(m_mag):
+                raise ValueError("griffin_lim: phase_init array of shape %s for m_mag of shape %s"
+                                 % (init.shape, np.shape(m_mag)))
+        else:
+            raise ValueError("griffin_lim: phase_init must be 'random', 'linear', 'min_phase' or an ndarray")
+        shifts.append(v)
+    return shifts, inits, N
+
+
+def griffin_lim_batch(utts, win_func=np.hanning, phase_init='random', niters=30, engine=None, return_device=False):
+    """
+    griffin_lim (magphase.py:3320-3372) for a batch: utts = [(m_mag, v_shift), ...] with one fft_len per call;
+    phase_init: one of 'random' / 'linear' / 'min_phase' / an ndarray for all, or a list with one per utterance.  Equal to
+    sequential griffin_lim calls, numpy's global random draws included (one rand(F, N) per 'random' utterance, in batch
+    order; an ndarray init has its columns 0 and H - 1 zeroed in place, as the reference's la.add_hermitian_half does).
+    The first synthesis is the lossless synthesis kernel on folded inputs (hostmath.griffin_lim_fold); every further one
+    is one mpx_griffin_lim_ola launch.  Returns a list of (v_sig, m_phase) float64 (device float32 with return_device).
+    Deviation: shifts outside the reference's domain raise ValueError for every niters (the reference only fails once
+    it analyses, niters >= 2).
+    """
+    utts = list(utts)
+    if not utts:
+        return []
+    shifts, inits, N = _griffin_lim_check(utts, win_func, phase_init, niters)
+    H = N // 2 + 1
+    sizes = [np.shape(m)[0] for m, _ in utts]
+    f_off = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+    F = int(f_off[-1])
+    h_mag, h_re, h_im = (np.empty((F, H), dtype=np.float32) for _ in range(3))
+    phase0, mp_rows = [None] * len(utts), []
+    for u, ((m_mag, _), init) in enumerate(zip(utts, inits)):
+        print('Starting Griffin-Lim. It could take a while...')
+        a, b = int(f_off[u]), int(f_off[u + 1])
+        ph, full = hm.griffin_lim_initial_phase(init, m_mag)
+        if ph is None:   # 'min_phase': phasors from mpx_min_phase below
+            h_mag[a:b] = m_mag
+            mp_rows.append(np.arange(a, b))
+            continue
+        if niters == 1:
+            phase0[u] = np.array(ph[:, :H], dtype=np.float64)
+        h_mag[a:b], h_re[a:b], h_im[a:b] = hm.griffin_lim_fold(m_mag, ph, full)
+    engine = engine or get_engine()
+    torch = __import__("torch")
+    ld = int(engine.lib.mpx_spec_ld(H))
+    dev = lambda: engine.empty((max(F, 1), ld))[:F, :H]   # noqa: E731
+    tgt, i_mag, i_re, i_im = dev(), dev(), dev(), dev()
+    tgt.copy_(torch.from_numpy(np.concatenate([np.asarray(m, dtype=np.float32) for m, _ in utts])))
+    for d, h in ((i_mag, h_mag), (i_re, h_re), (i_im, h_im)):
+        d.copy_(torch.from_numpy(h))
+    del h_mag, h_re, h_im   # (the copies above are synchronous: the host rows are no longer needed)
+    mp_phase = None
+    if mp_rows:   # la.build_min_phase_from_mag_spec's phasors, bins 0 and N/2 at phase 0, (-1)^k folded in
+        idx = np.concatenate(mp_rows)
+        rows = torch.from_numpy(idx.astype(np.int32)).to(engine.device)
+        n = int(idx.size)
+        o_m, o_r, o_i = (engine.empty((n, ld)) for _ in range(3))
+        with torch.cuda.device(engine.device):
+            from . import _lib
+            _lib.check(engine.lib.mpx_min_phase(engine.stream_ptr(), N, engine.tables(N).data_ptr(), tgt.data_ptr(),
+                                                rows.data_ptr(), rows.data_ptr(),
+                                                torch.zeros(n, dtype=torch.float32, device=engine.device).data_ptr(),
+                                                n, o_m.data_ptr(), o_r.data_ptr(), o_i.data_ptr(), ld), "mpx_min_phase")
+        re, im = o_r[:, :H].clone(), o_i[:, :H].clone()
+        re[:, 0], im[:, 0], re[:, -1], im[:, -1] = 1.0, 0.0, 1.0, 0.0
+        if niters == 1:
+            mp_phase = torch.atan2(im, re)
+        sgn = torch.ones(H, dtype=torch.float32, device=engine.device)
+        sgn[1::2] = -1.0
+        ridx = rows.long()
+        i_re[ridx] = re * sgn
+        i_im[ridx] = im * sgn
+        del o_m, o_r, o_i, re, im
+    plan = GriffinLimPlan(engine, shifts, N)
+    init = [i_mag, i_re, i_im]
+    del i_mag, i_re, i_im   # plan.run releases the init rows after the first synthesis
+    sig, ph_dev = plan.run(tgt, init, niters, phase_rows=True)
+    if niters == 1:
+        if mp_phase is not None:
+            ph_dev = dev()
+            ph_dev[torch.from_numpy(np.concatenate(mp_rows)).to(engine.device)] = mp_phase
+        if return_device and ph_dev is None:
+            ph_dev = dev()
+        if ph_dev is not None:
+            for u, p in enumerate(phase0):
+                if p is not None:
+                    ph_dev[int(f_off[u]):int(f_off[u + 1])] = torch.from_numpy(p.astype(np.float32)).to(engine.device)
+    if return_device:
+        return [(sig[int(plan.out_off_host[u]):int(plan.out_off_host[u + 1])], ph_dev[int(f_off[u]):int(f_off[u + 1])])
+                for u in range(len(utts))]
+    h_sig = engine.to_host_f64(sig)
+    h_ph = engine.to_host_f64(ph_dev) if ph_dev is not None else None
+    out = []
+    for u in range(len(utts)):
+        a, b = int(f_off[u]), int(f_off[u + 1])
+        p = phase0[u] if (niters == 1 and phase0[u] is not None) else h_ph[a:b].copy()
+        out.append((h_sig[int(plan.out_off_host[u]):int(plan.out_off_host[u + 1])].copy(), p))
+    return out
+
+
+def griffin_lim(m_mag, v_shift, win_func=np.hanning, phase_init='random', niters=30):
+    """magphase.py:3320-3372 (pitch-synchronous Griffin-Lim): (v_sig, m_phase) float64.  See griffin_lim_batch."""
+    return griffin_lim_batch([(m_mag, v_shift)], win_func=win_func,
+                             phase_init=[phase_init] if isinstance(phase_init, np.ndarray) else phase_init,
+                             niters=niters)[0]
 
 
 def copy_synthesis_lossless(wav_file, fft_len=None):
