@@ -217,6 +217,28 @@ int mpx_synthesis_lossless_ola(void* stream, int fft_len, const void* tables, co
                                float* pcm_out, int64_t ld /* row pitch of mag/real/imag */);
 int mpx_ola_fixup(void* stream, int fft_len, const mpx_ola_run* runs, int32_t n_runs, const float* strips,
                   float* pcm_out);
+/*
+ * mpx_synthesis_lossless_ola with row tables (constant-rate lossless synthesis, magphase.py:2242-2252 + :1759-1776):
+ * frame f is synthesised from the row (1 - row_t[f]) x[row0[f]] + row_t[f] x[row1[f]] of each of mag / real / imag
+ * (int32 / float32 [frames]; 0 <= row0, row1 < rows of the matrices -- the caller's promise), interpolated in registers as
+ * the kernel loads the two rows.  Everything else as mpx_synthesis_lossless_ola (same slots, weights, strips;
+ * mpx_ola_fixup afterwards).
+ */
+int mpx_synthesis_lossless_ola_lerp(void* stream, int fft_len, const void* tables, const float* mag, const float* real,
+                                    const float* imag, const int32_t* row0, const int32_t* row1, const float* row_t,
+                                    const mpx_ola_run* runs, int32_t n_runs, const int32_t* slot_off,
+                                    const int32_t* slot_runs, int32_t n_slots, const int32_t* pm_rel, float* strips,
+                                    float* pcm_out, int64_t ld);
+
+/*
+ * Row interpolation of the three lossless feature streams: dst_X[c] = (1 - row_t[c]) src_X[row0[c]] + row_t[c] src_X[row1[c]]
+ * for c < n_out, bins 0..n_bins-1 (X = mag / real / imag; row pitches ld_src / ld_dst in floats, >= n_bins; row indices
+ * within the source -- the caller's promise).  Variable -> constant rate (magphase.py:2219-2239, the constant-rate lossless
+ * analysis) and constant -> variable rate (:2242-2252, the staged form of mpx_synthesis_lossless_ola_lerp).
+ */
+int mpx_rows_lerp(void* stream, int32_t n_bins, const float* src_mag, const float* src_real, const float* src_imag,
+                  int64_t ld_src, const int32_t* row0, const int32_t* row1, const float* row_t, int64_t n_out,
+                  float* dst_mag, float* dst_real, float* dst_imag, int64_t ld_dst);
 
 /*
  * Copy synthesis in one launch: analysis_lossless (magphase.py:2869-2906: windowing :74-119, analysis_with_del_comp_from_pm
@@ -418,6 +440,15 @@ int mpx_synthesis_compressed_ola_spectra(void* stream, int fft_len, const void* 
  */
 int64_t mpx_host_const_to_var_scan(const double* centres, const double* shift_c, int64_t n, double* shifts_out,
                                    double* locs_out);
+/*
+ * The same scan with an explicit capacity: shifts_out / locs_out hold `cap` elements, the scan runs until the position
+ * leaves the grid (the reference's 2n slots can run out first: more than two frames per constant-rate frame on average).
+ * Where 2n slots suffice the results equal mpx_host_const_to_var_scan's.  n == 1: one frame at the single centre.  A cap of
+ * floor((centres[n-1] - centres[0]) / min(shift_c)) + 2 is always enough for positive shifts.  Returns `start` (results
+ * are out[start .. cap)), -1 on bad arguments, -2 when cap was too small.
+ */
+int64_t mpx_host_const_to_var_scan_cap(const double* centres, const double* shift_c, int64_t n, double* shifts_out,
+                                       double* locs_out, int64_t cap);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Compressed-feature analysis (magphase.py:2490-2544 format_for_modelling, :2947-2988 analysis_compressed)

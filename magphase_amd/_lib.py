@@ -35,6 +35,8 @@ SYMBOLS = (
     "mpx_synth_ola_slot_weights",
     "mpx_ola_strip_floats",
     "mpx_synthesis_lossless_ola",
+    "mpx_synthesis_lossless_ola_lerp",
+    "mpx_rows_lerp",
     "mpx_ola_fixup",
     "mpx_roundtrip_lossless_ola",
     "mpx_roundtrip_slot_weights",
@@ -55,6 +57,7 @@ SYMBOLS = (
     "mpx_synthesis_compressed_ola",
     "mpx_synthesis_compressed_ola_spectra",
     "mpx_host_const_to_var_scan",
+    "mpx_host_const_to_var_scan_cap",
     "mpx_host_plan_analysis",
     "mpx_host_plan_analysis_batch",
     "mpx_host_plan_synthesis",
@@ -170,6 +173,11 @@ def _load_locked():
     lib.mpx_ola_strip_floats.restype = i64
     lib.mpx_ola_strip_floats.argtypes = [ctypes.c_int]
     lib.mpx_synthesis_lossless_ola.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, i64]
+    lib.mpx_synthesis_lossless_ola_lerp.restype = ctypes.c_int
+    lib.mpx_synthesis_lossless_ola_lerp.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp,
+                                                    vp, vp, i64]
+    lib.mpx_rows_lerp.restype = ctypes.c_int
+    lib.mpx_rows_lerp.argtypes = [vp, i32, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64]
     lib.mpx_roundtrip_slot_weights.restype = ctypes.c_int
     lib.mpx_roundtrip_slot_weights.argtypes = [vp, i32]
     lib.mpx_roundtrip_lossless_ola.restype = ctypes.c_int
@@ -209,6 +217,8 @@ def _load_locked():
                                                          [vp, i32, vp, vp, i32, vp, vp, i64, i32, vp])
     lib.mpx_host_const_to_var_scan.restype = i64
     lib.mpx_host_const_to_var_scan.argtypes = [vp, vp, i64, vp, vp]
+    lib.mpx_host_const_to_var_scan_cap.restype = i64
+    lib.mpx_host_const_to_var_scan_cap.argtypes = [vp, vp, i64, vp, vp, i64]
     lib.mpx_host_plan_analysis.restype = i64
     lib.mpx_host_plan_analysis.argtypes = [i32] + [vp] * 12
     lib.mpx_host_plan_synthesis.restype = i64

@@ -7,7 +7,9 @@
 //   k_synth_lossless<P>     one wavefront per frame: 3 x H coalesced loads -> unit-phase spectrum ->
 //                           Hermitian merge -> inverse FFT -> epoch-centred frame.      HBM-read bound.
 //   k_ola_gather            one thread per output sample, ascending-frame gather (deterministic PSOLA).
-//   k_synth_ola_pair<P>     the production form: synthesis + PSOLA fused, one LDS ring per wave pair (below).
+//   k_synth_ola_pair<P,L>   the production form: synthesis + PSOLA fused, one LDS ring per wave pair (below); L = LERP:
+//                           every frame interpolates two feature rows (constant -> variable frame rate) as it loads them.
+//   k_rows_lerp             one wavefront per output row: out = (1-t) rows[r0] + t rows[r1] for mag / real / imag.
 // No MFMA in this file: nothing on the lossless path is a dense contraction; the mel
 // warp / unwarp GEMMs of the compressed path (magphase_comp.hip) run on the fp32 MFMA.
 #include "mpx_common.hpp"
@@ -368,7 +370,64 @@ constexpr size_t lds_bytes_pair() {
 #endif
 }
 
-template <int P>
+// LERP arm of k_synth_ola_pair: the loads of feat_load_paired_part for two rows (r0, r1) and the interpolation
+// (1-t) x0 + t x1 = fma(x1 - x0, t, x0) in registers, in chunks of LC bin pairs: only one chunk's two rows are in flight
+// (12 x LC registers), not two copies of the part.  The compiler hoists loads of read-only memory across plain barriers
+// (and then spills), so each chunk's addresses depend on the previous chunk's results through the laundered lane.
+template <int P, int J0, int J1, bool WITH_H>
+__device__ __forceinline__ void feat_lerp_paired_part(PairFeat<P>& ff, const float* __restrict__ m0,
+                                                      const float* __restrict__ r0, const float* __restrict__ i0,
+                                                      const float* __restrict__ m1, const float* __restrict__ r1,
+                                                      const float* __restrict__ i1, float t, int lane) {
+    constexpr int M = 64 * P;
+    constexpr int LC = 6;
+    asm volatile("" : "+v"(lane));   // not above the caller's preceding barrier either
+#pragma unroll
+    for (int c = J0; c < J1; c += LC) {
+        if (c > J0) asm volatile("" : "+v"(lane) : "v"(ff.m[c - 1]), "v"(ff.bq[c - 1]));
+        float y[LC][12];
+#pragma unroll
+        for (int jj = 0; jj < LC; ++jj) {
+            const int j = c + jj;
+            if (j < J1) {
+                y[jj][0] = m0[lane + 64 * j];
+                y[jj][1] = r0[lane + 64 * j];
+                y[jj][2] = i0[lane + 64 * j];
+                y[jj][3] = m0[M - lane - 64 * j];
+                y[jj][4] = r0[M - lane - 64 * j];
+                y[jj][5] = i0[M - lane - 64 * j];
+                y[jj][6] = m1[lane + 64 * j];
+                y[jj][7] = r1[lane + 64 * j];
+                y[jj][8] = i1[lane + 64 * j];
+                y[jj][9] = m1[M - lane - 64 * j];
+                y[jj][10] = r1[M - lane - 64 * j];
+                y[jj][11] = i1[M - lane - 64 * j];
+            }
+        }
+#pragma unroll
+        for (int jj = 0; jj < LC; ++jj) {
+            const int j = c + jj;
+            if (j < J1) {
+                ff.m[j] = fmaf(y[jj][6] - y[jj][0], t, y[jj][0]);
+                ff.a[j] = fmaf(y[jj][7] - y[jj][1], t, y[jj][1]);
+                ff.b[j] = fmaf(y[jj][8] - y[jj][2], t, y[jj][2]);
+                ff.mq[j] = fmaf(y[jj][9] - y[jj][3], t, y[jj][3]);
+                ff.aq[j] = fmaf(y[jj][10] - y[jj][4], t, y[jj][4]);
+                ff.bq[j] = fmaf(y[jj][11] - y[jj][5], t, y[jj][5]);
+            }
+        }
+    }
+    if (WITH_H) {
+        if (J1 > J0) asm volatile("" : "+v"(lane) : "v"(ff.m[J1 - 1]), "v"(ff.bq[J1 - 1]));
+        const float hm0 = m0[lane + M / 2], hr0 = r0[lane + M / 2], hi0 = i0[lane + M / 2];
+        const float hm1 = m1[lane + M / 2], hr1 = r1[lane + M / 2], hi1 = i1[lane + M / 2];
+        ff.mH = fmaf(hm1 - hm0, t, hm0);
+        ff.aH = fmaf(hr1 - hr0, t, hr0);
+        ff.bH = fmaf(hi1 - hi0, t, hi0);
+    }
+}
+
+template <int P, bool LERP = false>
 __global__ __launch_bounds__(kPairWaves * 64) void k_synth_ola_pair(const float* __restrict__ mag,
                                                                     const float* __restrict__ real,
                                                                     const float* __restrict__ imag,
@@ -378,7 +437,12 @@ __global__ __launch_bounds__(kPairWaves * 64) void k_synth_ola_pair(const float*
                                                                     const int* __restrict__ pm_rel,
                                                                     const float* __restrict__ tw_g,
                                                                     float* __restrict__ strips,
-                                                                    float* __restrict__ pcm, long long ld) {
+                                                                    float* __restrict__ pcm, long long ld,
+                                                                    const int* __restrict__ row0 = nullptr,
+                                                                    const int* __restrict__ row1 = nullptr,
+                                                                    const float* __restrict__ rowt = nullptr) {
+    // LERP: frame f's feature row is (1 - rowt[f]) rows[row0[f]] + rowt[f] rows[row1[f]] (the row tables come last, so
+    // the one-row form's arguments keep their kernarg offsets)
     constexpr int M = 64 * P, N = 2 * M, R = ring_len<P>();
     constexpr bool kCompact = pair_compact<P>();
     // feature prefetch in parts (bin pairs j: six values each): j < JA and bin M/2 right after the transform, JA <= j < JB
@@ -394,7 +458,13 @@ __global__ __launch_bounds__(kPairWaves * 64) void k_synth_ola_pair(const float*
 #ifndef MPX_CH
 #define MPX_CH 8
 #endif
-    constexpr int JA = kCompact ? MPX_JA : P / 2, JB = kCompact ? MPX_JB : P / 2;
+    // LERP: two rows of a chunk in flight (feat_lerp_paired_part); a smaller first part, no part inside the ordered
+    // section (its wait for the loaded values would hold up the partner wave), the rest after it
+#ifndef MPX_JA_LERP
+#define MPX_JA_LERP 4
+#endif
+    constexpr int JA = LERP ? (MPX_JA_LERP < P / 2 ? MPX_JA_LERP : P / 2) : (kCompact ? MPX_JA : P / 2);
+    constexpr int JB = LERP ? JA : (kCompact ? MPX_JB : P / 2);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* tw = smem;
     const int lane_id = threadIdx.x & 63;
@@ -472,7 +542,11 @@ __global__ __launch_bounds__(kPairWaves * 64) void k_synth_ola_pair(const float*
     // Software pipeline over the wave's frames: the features of the wave's NEXT frame are loaded while this frame waits
     // for its ticket and overlap-adds; convert + merge of the next iteration then starts on data that is (mostly) there.
     PairFeat<P> ff;
-    {
+    if constexpr (LERP) {
+        const long long f0 = row0[cur.fi], f1 = row1[cur.fi];
+        feat_lerp_paired_part<P, 0, P / 2, true>(ff, mag + f0 * ld, real + f0 * ld, imag + f0 * ld, mag + f1 * ld,
+                                                 real + f1 * ld, imag + f1 * ld, rowt[cur.fi], lane_id);
+    } else {
         const long long f = cur.fi;
         feat_load_paired_part<P, 0, P / 2, true>(ff, mag + f * ld, real + f * ld, imag + f * ld, lane_id);
     }
@@ -564,9 +638,19 @@ __global__ __launch_bounds__(kPairWaves * 64) void k_synth_ola_pair(const float*
         // (an exhausted cursor loads row 0 -- no branch around the loads; every finishing wave reads the same 24 KB, which
         // stay in L2: re-reading its own last frame cost 75 MB of HBM fetches per launch, 5 % of the kernel's traffic)
         const long long fnx = nxt.valid ? nxt.fi : 0;
-        const float* nm = mag + fnx * ld;
-        const float* nr = real + fnx * ld;
-        const float* ni = imag + fnx * ld;
+        long long rnx = fnx, rnx1 = fnx;
+        float tnx = 0.0f;
+        if constexpr (LERP) {
+            rnx = row0[fnx];
+            rnx1 = row1[fnx];
+            tnx = rowt[fnx];
+        }
+        const float* nm = mag + rnx * ld;
+        const float* nr = real + rnx * ld;
+        const float* ni = imag + rnx * ld;
+        const float* nm1 = mag + rnx1 * ld;
+        const float* nr1 = real + rnx1 * ld;
+        const float* ni1 = imag + rnx1 * ld;
         asm volatile("" ::: "memory");
 #ifdef MPX_ABL_NOLOAD   // energy ablation: no feature loads in the loop; the registers are (re)defined by an empty asm, as a load would
 #define MPX_FEAT_LOAD(J0, J1, WH)                                                                           \
@@ -575,7 +659,11 @@ __global__ __launch_bounds__(kPairWaves * 64) void k_synth_ola_pair(const float*
             asm volatile("" : "=v"(ff.m[j_]), "=v"(ff.a[j_]), "=v"(ff.b[j_]), "=v"(ff.mq[j_]), "=v"(ff.aq[j_]), "=v"(ff.bq[j_])); \
     } while (0)
 #else
-#define MPX_FEAT_LOAD(J0, J1, WH) feat_load_paired_part<P, J0, J1, WH>(ff, nm, nr, ni, lane)
+#define MPX_FEAT_LOAD(J0, J1, WH)                                                                           \
+    do {                                                                                                    \
+        if constexpr (LERP) feat_lerp_paired_part<P, J0, J1, WH>(ff, nm, nr, ni, nm1, nr1, ni1, tnx, lane); \
+        else feat_load_paired_part<P, J0, J1, WH>(ff, nm, nr, ni, lane);                                    \
+    } while (0)
 #endif
         MPX_FEAT_LOAD(0, JA, true);
 
@@ -693,6 +781,68 @@ __global__ __launch_bounds__(256) void k_ola_gather(const float* __restrict__ fr
         acc += frames[(long long)i * N + off];
     }
     pcm[o0 + t] = acc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Row interpolation (magphase.py:2219-2239 variable -> constant rate, :2242-2252 constant -> variable rate):
+// out[c] = (1 - t[c]) rows[r0[c]] + t[c] rows[r1[c]] for the three feature streams, one wavefront per output row.  A pure
+// stream: each lane moves whole 16-byte groups of the row (64 x 16 B = 1 KB contiguous per wave-instruction; the dense
+// feature pitch leaves rows only 4-byte aligned, which dwordx4 accesses allow), the last H mod 4 columns one float each.
+// Neighbouring output rows share source rows: those re-reads come from L2.  r0 == r1 reads the row once (t x 0 = 0: the
+// result is the row itself either way).
+// ---------------------------------------------------------------------------------------------
+typedef float f4a4 __attribute__((ext_vector_type(4), aligned(4)));
+constexpr int kLerpWaves = 4;
+
+__global__ __launch_bounds__(kLerpWaves * 64) void k_rows_lerp(int H, const float* __restrict__ sm,
+                                                               const float* __restrict__ sr, const float* __restrict__ si,
+                                                               long long lds, const int* __restrict__ row0,
+                                                               const int* __restrict__ row1,
+                                                               const float* __restrict__ rowt, long long n_out,
+                                                               float* __restrict__ dm, float* __restrict__ dr,
+                                                               float* __restrict__ di, long long ldd) {
+    const long long c = (long long)blockIdx.x * kLerpWaves + (threadIdx.x >> 6);
+    if (c >= n_out) return;
+    const int lane = threadIdx.x & 63;
+    const long long a = row0[c], b = row1[c];
+    const float t = rowt[c];
+    const long long oa = a * lds, ob = b * lds, od = c * ldd;
+    const int nv = H >> 2;   // whole 16-byte groups of the row
+    if (a == b) {
+        for (int v = lane; v < nv; v += 64) {
+            const f4a4 x = *reinterpret_cast<const f4a4*>(sm + oa + 4 * v);
+            const f4a4 y = *reinterpret_cast<const f4a4*>(sr + oa + 4 * v);
+            const f4a4 z = *reinterpret_cast<const f4a4*>(si + oa + 4 * v);
+            *reinterpret_cast<f4a4*>(dm + od + 4 * v) = x;
+            *reinterpret_cast<f4a4*>(dr + od + 4 * v) = y;
+            *reinterpret_cast<f4a4*>(di + od + 4 * v) = z;
+        }
+    } else {
+        for (int v = lane; v < nv; v += 64) {
+            const f4a4 x0 = *reinterpret_cast<const f4a4*>(sm + oa + 4 * v);
+            const f4a4 y0 = *reinterpret_cast<const f4a4*>(sr + oa + 4 * v);
+            const f4a4 z0 = *reinterpret_cast<const f4a4*>(si + oa + 4 * v);
+            const f4a4 x1 = *reinterpret_cast<const f4a4*>(sm + ob + 4 * v);
+            const f4a4 y1 = *reinterpret_cast<const f4a4*>(sr + ob + 4 * v);
+            const f4a4 z1 = *reinterpret_cast<const f4a4*>(si + ob + 4 * v);
+            f4a4 x, y, z;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                x[e] = fmaf(x1[e] - x0[e], t, x0[e]);
+                y[e] = fmaf(y1[e] - y0[e], t, y0[e]);
+                z[e] = fmaf(z1[e] - z0[e], t, z0[e]);
+            }
+            *reinterpret_cast<f4a4*>(dm + od + 4 * v) = x;
+            *reinterpret_cast<f4a4*>(dr + od + 4 * v) = y;
+            *reinterpret_cast<f4a4*>(di + od + 4 * v) = z;
+        }
+    }
+    const int k = 4 * nv + lane;   // the last H mod 4 columns
+    if (k < H) {
+        dm[od + k] = fmaf(sm[ob + k] - sm[oa + k], t, sm[oa + k]);
+        dr[od + k] = fmaf(sr[ob + k] - sr[oa + k], t, sr[oa + k]);
+        di[od + k] = fmaf(si[ob + k] - si[oa + k], t, si[oa + k]);
+    }
 }
 
 // First-pass twiddle table (layout: wave_fft.hpp): row = lane l, entry i = e^{2 pi i l brev(i) / M} as (cos, sin), rows
@@ -857,6 +1007,42 @@ int64_t mpx_host_const_to_var_scan(const double* centres, const double* shift_c,
     return 0;
 }
 
+/*
+ * The same scan with an explicit output capacity `cap`: slots cap-1, cap-2, ... are filled until the position leaves the
+ * grid, so the scan always reaches the start of the grid when cap is large enough (mpx_host_const_to_var_scan stops at
+ * 2n slots, as the reference does).  Where the reference's 2n slots suffice the results are its results, element for
+ * element.  n == 1: the grid is the single centre; one frame there.  Returns the index of the first valid element
+ * (out[start .. cap)), -1 on bad arguments, -2 when cap slots were not enough.
+ */
+int64_t mpx_host_const_to_var_scan_cap(const double* centres, const double* shift_c, int64_t n, double* shifts_out,
+                                       double* locs_out, int64_t cap) {
+#pragma clang fp contract(off)
+    if (!centres || !shift_c || !shifts_out || !locs_out || n < 1 || cap < 1) return -1;
+    double pos = centres[n - 1];
+    for (int64_t i = cap - 1; i >= 0; --i) {
+        if (!(pos >= centres[0] && pos <= centres[n - 1])) return i + 1;
+        locs_out[i] = pos;
+        double y;
+        if (n == 1) {
+            y = shift_c[0];
+        } else {
+            int64_t lo = 0, hi = n;
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (centres[mid] < pos) lo = mid + 1; else hi = mid;
+            }
+            const int64_t idx = lo < 1 ? 1 : (lo > n - 1 ? n - 1 : lo);
+            const double x_lo = centres[idx - 1], x_hi = centres[idx], y_lo = shift_c[idx - 1], y_hi = shift_c[idx];
+            const double slope = (y_hi - y_lo) / (x_hi - x_lo);
+            const double prod = slope * (pos - x_lo);
+            y = prod + y_lo;
+        }
+        shifts_out[i] = y;
+        pos = pos - y;
+    }
+    return (pos >= centres[0] && pos <= centres[n - 1]) ? -2 : 0;
+}
+
 
 #ifdef MPX_PROBE_ENDTIME
 int mpx_probe_endtimes(unsigned long long* host, int n_words) {   // probe builds only (not part of the ABI)
@@ -926,6 +1112,53 @@ int mpx_synthesis_lossless_ola(void* stream, int fft_len, const void* tables, co
     else if (P == 16) MPX_LAUNCH_PAIR(16);
     else MPX_LAUNCH_PAIR(8);
 #undef MPX_LAUNCH_PAIR
+    MPX_HIP_CHECK(hipGetLastError());
+    return MPX_OK;
+}
+
+int mpx_synthesis_lossless_ola_lerp(void* stream, int fft_len, const void* tables, const float* mag, const float* real,
+                                    const float* imag, const int32_t* row0, const int32_t* row1, const float* row_t,
+                                    const mpx_ola_run* runs, int32_t n_runs, const int32_t* slot_off,
+                                    const int32_t* slot_runs, int32_t n_slots, const int32_t* pm_rel, float* strips,
+                                    float* pcm_out, int64_t ld) {
+    const int P = p_of(fft_len);
+    if (!P) return fail(MPX_ERR_ARG, "mpx_synthesis_lossless_ola_lerp: fft_len must be 1024, 2048 or 4096%s");
+    if (n_runs < 0 || n_slots < 0) return fail(MPX_ERR_ARG, "mpx_synthesis_lossless_ola_lerp: negative count%s");
+    if (ld < fft_len / 2 + 1) return fail(MPX_ERR_ARG, "mpx_synthesis_lossless_ola_lerp: ld < fft_len/2 + 1%s");
+    if (n_runs == 0 || n_slots == 0) return MPX_OK;
+    if (!tables || !mag || !real || !imag || !row0 || !row1 || !row_t || !runs || !slot_off || !slot_runs || !pm_rel ||
+        !strips || !pcm_out)
+        return fail(MPX_ERR_ARG, "mpx_synthesis_lossless_ola_lerp: null pointer%s");
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((n_slots + kPairs - 1) / kPairs), block(kPairWaves * 64);
+#define MPX_LAUNCH_PAIR(PP)                                                                                          \
+    do {                                                                                                             \
+        if (int rc = set_lds((k_synth_ola_pair<PP, true>), lds_bytes_pair<PP>())) return rc;                         \
+        hipLaunchKernelGGL((k_synth_ola_pair<PP, true>), grid, block, lds_bytes_pair<PP>(), s, mag, real, imag,        \
+                           (const RunDesc*)runs, slot_off, slot_runs, (int)n_slots, pm_rel, (const float*)tables,    \
+                           strips, pcm_out, (long long)ld, row0, row1, row_t);                                       \
+    } while (0)
+    if (P == 32) MPX_LAUNCH_PAIR(32);
+    else if (P == 16) MPX_LAUNCH_PAIR(16);
+    else MPX_LAUNCH_PAIR(8);
+#undef MPX_LAUNCH_PAIR
+    MPX_HIP_CHECK(hipGetLastError());
+    return MPX_OK;
+}
+
+int mpx_rows_lerp(void* stream, int32_t n_bins, const float* src_mag, const float* src_real, const float* src_imag,
+                  int64_t ld_src, const int32_t* row0, const int32_t* row1, const float* row_t, int64_t n_out,
+                  float* dst_mag, float* dst_real, float* dst_imag, int64_t ld_dst) {
+    if (n_bins < 1 || n_out < 0) return fail(MPX_ERR_ARG, "mpx_rows_lerp: n_bins < 1 or negative n_out%s");
+    if (ld_src < n_bins || ld_dst < n_bins) return fail(MPX_ERR_ARG, "mpx_rows_lerp: row pitch < n_bins%s");
+    if (n_out == 0) return MPX_OK;
+    if (!src_mag || !src_real || !src_imag || !row0 || !row1 || !row_t || !dst_mag || !dst_real || !dst_imag)
+        return fail(MPX_ERR_ARG, "mpx_rows_lerp: null pointer%s");
+    if ((n_out + kLerpWaves - 1) / kLerpWaves > 2147483647LL) return fail(MPX_ERR_ARG, "mpx_rows_lerp: too many rows%s");
+    const dim3 block(kLerpWaves * 64), grid((unsigned)((n_out + kLerpWaves - 1) / kLerpWaves));
+    hipLaunchKernelGGL(k_rows_lerp, grid, block, 0, (hipStream_t)stream, (int)n_bins, src_mag, src_real, src_imag,
+                       (long long)ld_src, row0, row1, row_t, (long long)n_out, dst_mag, dst_real, dst_imag,
+                       (long long)ld_dst);
     MPX_HIP_CHECK(hipGetLastError());
     return MPX_OK;
 }

@@ -1312,6 +1312,40 @@ class Engine:
                 "mpx_synthesis_lossless_ola")
         return pcm_out
 
+    def synthesis_lossless_ola_lerp(self, fft_len, mag, real, imag, rows, plan, strips, pcm_out):
+        """synthesis_lossless_ola with row tables (mpx_synthesis_lossless_ola_lerp): rows = (row0, row1, rowt) device
+        tensors, one entry per frame of plan; frame f's feature row is the interpolation of two rows of mag / real / imag."""
+        torch = _torch()
+        tab = self.tables(fft_len)
+        r0, r1, rt = rows
+        with torch.cuda.device(self.device):
+            _lib.check(
+                self.lib.mpx_synthesis_lossless_ola_lerp(self.stream_ptr(), int(fft_len), tab.data_ptr(), mag.data_ptr(),
+                                                         real.data_ptr(), imag.data_ptr(), r0.data_ptr(), r1.data_ptr(),
+                                                         rt.data_ptr(), plan.runs.data_ptr(), int(plan.n_runs),
+                                                         plan.slot_off.data_ptr(), plan.slot_runs.data_ptr(),
+                                                         int(plan.n_slots), plan.pm_rel.data_ptr(), strips.data_ptr(),
+                                                         pcm_out.data_ptr(), self.feat_ld(mag, real, imag)),
+                "mpx_synthesis_lossless_ola_lerp")
+        return pcm_out
+
+    def rows_lerp(self, src, rows, n_out, out=None):
+        """mpx_rows_lerp: src = (mag, real, imag) device rows, rows = (row0, row1, rowt) device tables of n_out entries ->
+        (mag, real, imag) [n_out x H], out[c] = (1 - rowt[c]) src[row0[c]] + rowt[c] src[row1[c]]."""
+        torch = _torch()
+        H = int(src[0].shape[1])
+        if out is None:
+            out = tuple(self.empty_feats(int(n_out), H) for _ in range(3))
+        if n_out == 0:
+            return out
+        r0, r1, rt = rows
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mpx_rows_lerp(self.stream_ptr(), H, src[0].data_ptr(), src[1].data_ptr(),
+                                              src[2].data_ptr(), self.feat_ld(*src), r0.data_ptr(), r1.data_ptr(),
+                                              rt.data_ptr(), int(n_out), out[0].data_ptr(), out[1].data_ptr(),
+                                              out[2].data_ptr(), self.feat_ld(*out)), "mpx_rows_lerp")
+        return out
+
     def roundtrip_lossless_ola(self, fft_len, plan_a, plan_s, feats, strips, pcm_out):
         """Copy synthesis in one launch (mpx_roundtrip_lossless_ola): plan_a's frames are analysed, their feature rows
         written to feats = (mag, real, imag) and overlap-added by plan_s' runs (a LosslessSynthesisPlan built for this
@@ -1749,6 +1783,196 @@ class LosslessRoundTripPlan:
         e.roundtrip_lossless_ola(self.fft_len, a, s, feats, strips, out)
         e.ola_fixup(self.fft_len, s, strips, out)
         return feats, out
+
+
+def check_const_rate_ms(const_rate_ms):
+    """A constant frame period in ms: finite and > 0 (ValueError otherwise)."""
+    if isinstance(const_rate_ms, (bool, np.bool_)) or not isinstance(const_rate_ms, (int, float, np.integer, np.floating)):
+        raise ValueError("const_rate_ms must be a number > 0, got %r" % (const_rate_ms,))
+    v = float(const_rate_ms)
+    if not np.isfinite(v) or v <= 0.0:
+        raise ValueError("const_rate_ms must be finite and > 0, got %r" % (const_rate_ms,))
+    return v
+
+
+class LosslessConstRateAnalysisPlan:
+    """
+    analysis_lossless on a constant frame rate (magphase.py:2967-2980 with const_rate_ms as a parameter, without the mel
+    warp that follows there): a LosslessAnalysisPlan (k_analysis writes the variable-rate rows into scratch), the row
+    tables of hostmath.var_to_const_rate_table offset per utterance, and f0 from _const_rate_f0_voi.  run() = k_analysis ->
+    k_rows_lerp; the scratch is released once the interpolation is queued.
+    """
+
+    def __init__(self, engine, utts, fft_len=None, const_rate_ms=5.0, prepared=None):
+        self.engine = e = engine
+        self.const_rate_ms = check_const_rate_ms(const_rate_ms)
+        self.lossless = pl = LosslessAnalysisPlan(engine, utts, fft_len=fft_len, prepared=prepared)
+        self.fft_len, self.fs, self.long_frame_lens = pl.fft_len, pl.fs, pl.long_frame_lens
+        row0, row1, rowt, self.v_f0 = [], [], [], []
+        for u in range(len(utts)):
+            base, fs = int(pl.frame_off[u]), pl.fs[u]
+            v_pm = np.cumsum(pl.v_shift[u])
+            lo, hi, t = hm.var_to_const_rate_table(v_pm, self.const_rate_ms, fs)
+            self.v_f0.append(_const_rate_f0_voi(np.asarray(pl.v_f0[u]), v_pm, fs, self.const_rate_ms))
+            row0.append(lo + base), row1.append(hi + base), rowt.append(t)
+        self.out_off = np.concatenate(([0], np.cumsum([f.size for f in self.v_f0]))).astype(np.int64)
+        self.total_out_frames = int(self.out_off[-1])
+        cat = (lambda v, dt: np.concatenate(v).astype(dt) if v else np.zeros(0, dt))   # noqa: E731
+        self.row0_host, self.row1_host, self.rowt_host = cat(row0, np.int64), cat(row1, np.int64), cat(rowt, np.float64)
+        t = e.to_device_packed([("row0", self.row0_host, np.int32), ("row1", self.row1_host, np.int32),
+                                ("rowt", self.rowt_host, np.float32)])
+        self.rows = (t["row0"], t["row1"], t["rowt"])
+
+    def run(self, out=None):
+        """Returns (mag, real, imag) [total_out_frames x H] device rows (utterance u: rows out_off[u] .. out_off[u+1])."""
+        e = self.engine
+        H = self.fft_len // 2 + 1
+        if out is None:
+            out = tuple(e.empty_feats(self.total_out_frames, H) for _ in range(3))
+        if self.total_out_frames == 0:
+            return out
+        var = self.lossless.run()
+        e.rows_lerp(var, self.rows, self.total_out_frames, out=out)
+        del var   # (stream-ordered: the allocator reuses the scratch after the interpolation)
+        return out
+
+
+def const_to_variable_scan_uncapped(v_shift_c_rate, frm_rate_ms, fs):
+    """
+    get_shifts_and_frm_locs_from_const_shifts (magphase.py:1426-1449) run to the start of the grid: the reference keeps 2n
+    slots, and an utterance that needs more than 2n - 1 pitch-synchronous frames loses its head there (a zero-shift
+    frame is left at slot 0).  mpx_host_const_to_var_scan_cap with a capacity from the grid length and the smallest shift:
+    where 2n slots suffice, the result is _const_to_variable_scan's, element for element.  n == 1: one frame at the single
+    centre; n == 0: no frame.  Shifts must be finite and > 0 (ValueError).
+    """
+    v = np.ascontiguousarray(v_shift_c_rate, dtype=np.float64)
+    n = int(v.shape[0])
+    if n == 0:
+        return np.zeros(0), np.zeros(0)
+    if not np.all(np.isfinite(v)) or np.any(v <= 0.0):
+        raise ValueError("constant-rate shifts must be finite and > 0 (f0 >= 0 and finite)")
+    step = fs * frm_rate_ms / 1000
+    centres = np.ascontiguousarray(step * np.arange(1, n + 1), dtype=np.float64)
+    cap = int((centres[-1] - centres[0]) // float(v.min())) + 4   # every step moves by at least min(v)
+    shifts, locs = np.empty(cap), np.empty(cap)
+    start = int(_lib.load().mpx_host_const_to_var_scan_cap(centres.ctypes.data, v.ctypes.data, n, shifts.ctypes.data,
+                                                           locs.ctypes.data, cap))
+    if start < 0:
+        raise _lib.MagphaseHipError("mpx_host_const_to_var_scan_cap failed (%d)" % start)
+    return shifts[start:].copy(), locs[start:].copy()
+
+
+def const_to_variable_rows(v_f0_c, v_locs, const_rate_ms, fs):
+    """Row tables of interp_from_const_to_variable_rate (magphase.py:2242-2252) at the frame locations v_locs: scipy
+    interp1d's bracketing, as plan_synthesis_numpy computes them.  Returns (row_lo, row_hi int64, t float64, v_voi bool):
+    the voicing is interp(v_f0_c > 1.0) > 0.5 (:866-868).  One row: every frame takes it."""
+    from scipy import interpolate
+
+    n = int(np.size(v_f0_c))
+    if n == 1:
+        z = np.zeros(v_locs.size, dtype=np.int64)
+        return z, z.copy(), np.zeros(v_locs.size), np.full(v_locs.size, bool(v_f0_c[0] > 1.0))
+    centres = (fs * const_rate_ms / 1000) * np.arange(1, n + 1)
+    v_voi = interpolate.interp1d(centres, v_f0_c > 1.0, axis=0, kind="linear")(v_locs) > 0.5
+    idx = np.clip(np.searchsorted(centres, v_locs), 1, n - 1)
+    lo, hi = idx - 1, idx
+    t = (v_locs - centres[lo]) / (centres[hi] - centres[lo])
+    return lo.astype(np.int64), hi.astype(np.int64), t, v_voi
+
+
+def plan_const_rate_synthesis(f0_list, fs_list, const_rate_ms):
+    """
+    Host side of LosslessConstRateSynthesisPlan, float64 (no device): per utterance with rows, f0 -> shifts
+    (magphase.py:848), const_to_variable_scan_uncapped, const_to_variable_rows, shift_to_f0 (b_smooth=False).  Returns a
+    dict of per-utterance lists over the utterances with rows ("live", their indices): v_shift, v_locs, v_voi, v_f0, and
+    the batch's row tables row0 / row1 (offset by the rows of the utterances before) and rowt; n_rows per utterance.
+    Raises ValueError on const_rate_ms <= 0 and on f0 that gives no positive finite shift.
+    """
+    cr = check_const_rate_ms(const_rate_ms)
+    n_rows = [int(np.size(f)) for f in f0_list]
+    row_base = np.concatenate(([0], np.cumsum(n_rows))).astype(np.int64)
+    r = {k: [] for k in ("live", "v_shift", "v_locs", "v_voi", "v_f0", "row0", "row1", "rowt")}
+    for u, n in enumerate(n_rows):
+        if n == 0:
+            continue
+        f0c, fs = np.asarray(f0_list[u], dtype=np.float64), fs_list[u]
+        if not np.all(np.isfinite(f0c)) or np.any(f0c < 0.0):
+            raise ValueError("v_f0 of utterance %d: values must be finite and >= 0" % u)
+        v_shift, v_locs = const_to_variable_scan_uncapped(hm.f0_to_shift(f0c, fs), cr, fs)
+        lo, hi, t, v_voi = const_to_variable_rows(f0c, v_locs, cr, fs)
+        for k, v in (("live", u), ("v_shift", v_shift), ("v_locs", v_locs), ("v_voi", v_voi),
+                     ("v_f0", hm.shift_to_f0(v_shift, v_voi, fs)), ("row0", lo + row_base[u]),
+                     ("row1", hi + row_base[u]), ("rowt", t)):
+            r[k].append(v)
+    for k in ("row0", "row1"):
+        r[k] = np.concatenate(r[k]) if r[k] else np.zeros(0, np.int64)
+    r["rowt"] = np.concatenate(r["rowt"]) if r["rowt"] else np.zeros(0)
+    r["n_rows"] = n_rows
+    return r
+
+
+class LosslessConstRateSynthesisPlan:
+    """
+    synthesis_from_lossless from constant-rate rows (the reference's constant -> variable rate steps of
+    synthesis_from_compressed, magphase.py:848, :861-870, followed by :1759-1776): per utterance f0 -> shifts, the
+    uncapped scan (const_to_variable_scan_uncapped), the row tables and voicing at the frame locations
+    (const_to_variable_rows), f0 at the variable rate (shift_to_f0, b_smooth=False); then a LosslessSynthesisPlan for the
+    PSOLA bookkeeping.  run(): the LERP arm of k_synth_ola_pair (rows interpolated as they are loaded); run_staged():
+    k_rows_lerp into variable-rate scratch rows, then k_synth_ola_pair.  Utterances without rows give empty signals.
+    """
+
+    def __init__(self, engine, f0_list, fs_list, fft_len, const_rate_ms=5.0, frames_per_run=None, host=None):
+        # host: plan_const_rate_synthesis(f0_list, fs_list, const_rate_ms) when the caller has it already
+        self.engine = e = engine
+        self.fft_len = int(fft_len)
+        self.const_rate_ms = check_const_rate_ms(const_rate_ms)
+        r = host if host is not None else plan_const_rate_synthesis(f0_list, fs_list, self.const_rate_ms)
+        self.live, self.n_rows = r["live"], r["n_rows"]
+        self.v_shift, self.v_locs, self.v_voi, self.v_f0 = r["v_shift"], r["v_locs"], r["v_voi"], r["v_f0"]
+        self.row0_host, self.row1_host, self.rowt_host = r["row0"], r["row1"], r["rowt"]
+        self.total_rows = int(sum(self.n_rows))
+        self.inner = None
+        out_len = [0] * len(self.n_rows)
+        if self.live:
+            self.inner = LosslessSynthesisPlan(e, self.v_f0, [fs_list[u] for u in self.live], self.fft_len,
+                                               frames_per_run=frames_per_run)
+            for k, u in enumerate(self.live):
+                out_len[u] = self.inner.out_len[k]
+            t = e.to_device_packed([("row0", self.row0_host, np.int32), ("row1", self.row1_host, np.int32),
+                                    ("rowt", self.rowt_host, np.float32)])
+            self.rows = (t["row0"], t["row1"], t["rowt"])
+        self.total_frames = self.inner.total_frames if self.inner is not None else 0
+        self.out_len = out_len
+        self.out_off_host = np.concatenate(([0], np.cumsum(out_len))).astype(np.int64)
+        self.total_out = int(self.out_off_host[-1])
+
+    def _check_rows(self, mag):
+        if int(mag.shape[0]) != self.total_rows:
+            raise ValueError("constant-rate rows: %d given, the plan has %d" % (int(mag.shape[0]), self.total_rows))
+
+    def run(self, mag, real, imag, strips=None, out=None):
+        """Fused: k_synth_ola_pair<P, LERP = true> + k_ola_fixup.  Returns the signals [total_out] (u at out_off_host[u])."""
+        e = self.engine
+        self._check_rows(mag)
+        if out is None:
+            out = e.empty((self.total_out,))
+        if self.inner is None:
+            return out
+        s = self.inner
+        if strips is None:
+            strips = e.empty((max(s.strip_floats, 1),))
+        e.synthesis_lossless_ola_lerp(self.fft_len, mag, real, imag, self.rows, s, strips, out)
+        return e.ola_fixup(self.fft_len, s, strips, out)
+
+    def run_staged(self, mag, real, imag, rows_out=None, out=None):
+        """Staged: k_rows_lerp into variable-rate rows [total_frames x H], then the unchanged k_synth_ola_pair."""
+        self._check_rows(mag)
+        if out is None:
+            out = self.engine.empty((self.total_out,))
+        if self.inner is None:
+            return out
+        var = self.engine.rows_lerp((mag, real, imag), self.rows, self.total_frames, out=rows_out)
+        return self.inner.run(var[0], var[1], var[2], out=out)
 
 
 class _OlaRuns:

@@ -20,8 +20,9 @@ from . import hostmath as hm
 from . import libaudio as la
 from . import libutils as lu
 from .engine import (CompressedAnalysisPlan, CompressedSynthesisPlan, GriffinLimPlan, LosslessAnalysisPlan,
-                     LosslessRoundTripPlan, LosslessSynthesisPlan,
-                     get_engine)
+                     LosslessConstRateAnalysisPlan, LosslessConstRateSynthesisPlan, LosslessRoundTripPlan,
+                     LosslessSynthesisPlan, check_const_rate_ms, get_engine,
+                     plan_const_rate_synthesis)
 
 _epoch_provider = None
 
@@ -273,10 +274,18 @@ def synthesis_from_lossless_batch(feats, engine=None):
     number of bins.  Returns a list of float64 numpy signals.
     """
     engine = engine or get_engine()
-    torch = __import__("torch")
     H = int(np.shape(feats[0][0])[1])
     fft_len = 2 * (H - 1)
     plan = LosslessSynthesisPlan(engine, [f[3] for f in feats], [f[4] for f in feats], fft_len)
+    cat = _feats_cat_device(engine, feats, H)
+    pcm = engine.to_host_f64(plan.run(cat[0], cat[1], cat[2]))
+    return [pcm[plan.out_off_host[u]:plan.out_off_host[u + 1]] for u in range(len(feats))]
+
+
+def _feats_cat_device(engine, feats, H):
+    """The mag / real / imag matrices of a batch, each stream as ONE device float32 matrix (engine.empty_feats pitch):
+    a one-utterance float32 device tensor is taken as it is, host arrays go through pinned staging in one DMA."""
+    torch = __import__("torch")
     rows = np.concatenate(([0], np.cumsum([int(np.shape(f[0])[0]) for f in feats])))
     cat = []
     for k in range(3):   # one device matrix per stream (engine.empty_feats)
@@ -293,13 +302,125 @@ def synthesis_from_lossless_batch(feats, engine=None):
             part = f[k] if torch.is_tensor(f[k]) else torch.from_numpy(np.ascontiguousarray(f[k], dtype=np.float32))
             buf[int(rows[u]):int(rows[u + 1])].copy_(part)
         cat.append(buf)
-    pcm = engine.to_host_f64(plan.run(cat[0], cat[1], cat[2]))
-    return [pcm[plan.out_off_host[u]:plan.out_off_host[u + 1]] for u in range(len(feats))]
+    return cat
 
 
 def synthesis_from_lossless(m_mag, m_real, m_imag, v_f0, fs):
     """magphase.py:1759-1776."""
     return synthesis_from_lossless_batch([(m_mag, m_real, m_imag, v_f0, fs)])[0]
+
+
+# ======================================================================================================
+# lossless features on a constant frame rate (analysis: magphase.py:2967-2980 without the mel warp; synthesis: the
+# constant -> variable rate steps of :848, :861-870 followed by :1759-1776)
+# ======================================================================================================
+def analysis_lossless_const_rate_batch(utts, fft_len=None, const_rate_ms=5.0, engine=None, return_device=False, copy=True):
+    """
+    analysis_lossless_batch with the rows on a constant frame rate: per utterance the reference's
+    interp_from_variable_to_const_frm_rate of mag / real / imag (grid arange(step, pm[-1], step), the first row held back
+    to t = 0) and f0 interpolated through the voiced points times the interpolated voicing > 0.5 (magphase.py:2967-2980,
+    const_rate_ms as a parameter).  utts: list of (v_sig, fs, v_pm_sec, v_voi), one fft_len per batch.  Returns a list of
+    (m_mag, m_real, m_imag, v_f0, fs): float64 numpy, or float32 device rows with return_device (v_f0 is float64 numpy
+    either way).  An utterance shorter than one step gives (0, H) matrices and an empty f0; one without a voiced frame
+    raises (IndexError, as analysis_compressed_batch(b_const_rate=True) does).  copy: as analysis_lossless_batch.
+    """
+    const_rate_ms = check_const_rate_ms(const_rate_ms)
+    utts = list(utts)
+    if not utts:
+        return []
+    engine = engine or get_engine()
+    plan = LosslessConstRateAnalysisPlan(engine, utts, fft_len=fft_len, const_rate_ms=const_rate_ms)
+    for lens in plan.long_frame_lens:
+        for n in lens:  # Q19: truncation warns, it does not raise (magphase.py:311-315)
+            warnings.warn(_WARN_LONG % (plan.fft_len, n))
+    mag, real, imag = plan.run()
+    if not return_device:
+        h_feats = tuple(engine.to_host_f64_many([mag, real, imag]))
+    out = []
+    for u in range(len(utts)):
+        a, b = int(plan.out_off[u]), int(plan.out_off[u + 1])
+        if return_device:
+            feats = (mag[a:b], real[a:b], imag[a:b])
+        else:
+            feats = h_feats if len(utts) == 1 else tuple((h[a:b].copy() if copy else h[a:b]) for h in h_feats)
+        out.append(feats + (plan.v_f0[u], plan.fs[u]))
+    return out
+
+
+def analysis_lossless_const_rate(wav_file, fft_len=None, out_dir=None, const_rate_ms=5.0):
+    """analysis_lossless (magphase.py:2869-2906) with the rows on a constant frame rate (see
+    analysis_lossless_const_rate_batch).  With out_dir: writes <name>.mag / .real / .imag / .f0 (float32 binfiles)."""
+    const_rate_ms = check_const_rate_ms(const_rate_ms)
+    v_sig, fs = la.read_audio_file(wav_file)
+    v_pm_sec, v_voi = _epochs_for(wav_file)
+    m_mag, m_real, m_imag, v_f0, fs = analysis_lossless_const_rate_batch([(v_sig, fs, v_pm_sec, v_voi)], fft_len=fft_len,
+                                                                         const_rate_ms=const_rate_ms)[0]
+    if type(out_dir) is str:
+        file_id = os.path.basename(wav_file).split(".")[0]
+        write_featfile(m_mag, out_dir, file_id + ".mag")
+        write_featfile(m_real, out_dir, file_id + ".real")
+        write_featfile(m_imag, out_dir, file_id + ".imag")
+        write_featfile(v_f0, out_dir, file_id + ".f0")
+        return
+    return m_mag, m_real, m_imag, v_f0, fs
+
+
+def _const_rate_synthesis_check(feats):
+    """Argument checks of synthesis_from_lossless_const_rate_batch, on the host: one bin count, row counts that agree.
+    Returns H."""
+    H = None
+    for i, f in enumerate(feats):
+        if len(f) != 5:
+            raise ValueError("feats[%d]: expected (m_mag, m_real, m_imag, v_f0, fs)" % i)
+        shapes = [tuple(np.shape(x)) for x in f[:3]]
+        if any(len(sh) != 2 for sh in shapes) or len(set(shapes)) != 1:
+            raise ValueError("feats[%d]: m_mag, m_real and m_imag must be 2-D of one shape, got %s" % (i, shapes))
+        n, h = shapes[0]
+        if np.ndim(f[3]) != 1 or np.size(f[3]) != n:
+            raise ValueError("feats[%d]: v_f0 has %d values for %d rows" % (i, np.size(f[3]), n))
+        if H is not None and h != H:
+            raise ValueError("synthesis_from_lossless_const_rate_batch: all utterances of a call must share the bin count "
+                             "(%d and %d)" % (H, h))
+        H = h
+    if H is None or 2 * (H - 1) not in (1024, 2048, 4096):
+        raise ValueError("synthesis_from_lossless_const_rate_batch: %s bins (fft_len 1024, 2048 or 4096)" % (H,))
+    return H
+
+
+def synthesis_from_lossless_const_rate_batch(feats, const_rate_ms=5.0, engine=None, return_device=False):
+    """
+    synthesis_from_lossless (magphase.py:1759-1776) from lossless features on a constant frame rate: feats is a list of
+    (m_mag, m_real, m_imag, v_f0, fs) with one row per const_rate_ms (numpy or device tensors, as
+    synthesis_from_lossless_batch takes them; one bin count per call).  Per utterance, the reference's composition
+    f0_to_shift -> get_shifts_and_frm_locs_from_const_shifts -> interp_from_const_to_variable_rate of mag / real / imag
+    and of the voicing (> 0.5) -> shift_to_f0(b_smooth=False) -> synthesis_from_lossless, except that the scan runs to
+    the start of the grid (the reference's stops after 2n slots).  Time-stretch: synthesise with
+    another const_rate_ms than the analysis used; pitch-shift: scale v_f0.  The rows are interpolated as the synthesis
+    kernel loads them.  Returns a list of float64 signals (device float32 with return_device).
+    """
+    const_rate_ms = check_const_rate_ms(const_rate_ms)
+    feats = list(feats)
+    if not feats:
+        return []
+    H = _const_rate_synthesis_check(feats)
+    f0_list = [np.asarray(f[3].cpu() if hasattr(f[3], "cpu") else f[3], dtype=np.float64) for f in feats]
+    fs_list = [f[4] for f in feats]
+    host = plan_const_rate_synthesis(f0_list, fs_list, const_rate_ms)   # (raises before any device call)
+    engine = engine or get_engine()
+    plan = LosslessConstRateSynthesisPlan(engine, f0_list, fs_list, 2 * (H - 1), const_rate_ms=const_rate_ms,
+                                          host=host)
+    cat = _feats_cat_device(engine, feats, H)
+    pcm = plan.run(cat[0], cat[1], cat[2])
+    o = plan.out_off_host
+    if return_device:
+        return [pcm[int(o[u]):int(o[u + 1])] for u in range(len(feats))]
+    h = engine.to_host_f64(pcm)
+    return [h[int(o[u]):int(o[u + 1])] for u in range(len(feats))]
+
+
+def synthesis_from_lossless_const_rate(m_mag, m_real, m_imag, v_f0, fs, const_rate_ms=5.0):
+    """synthesis_from_lossless from constant-rate lossless features (see synthesis_from_lossless_const_rate_batch)."""
+    return synthesis_from_lossless_const_rate_batch([(m_mag, m_real, m_imag, v_f0, fs)], const_rate_ms=const_rate_ms)[0]
 
 
 def copy_synthesis_lossless_batch(utts, fft_len=None, engine=None, return_device=False, with_feats=True):
