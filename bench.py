@@ -2,7 +2,7 @@
 """
 bench.py -- MagPhase hot-path benchmark on MI355X (contract: see the task statement / DESIGN.md section 6).
 
-    python bench.py --gpus 1 --steps 200 --warmup 10
+    python bench.py --gpus 1 --steps 200 --warmup 10 [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,7 +12,10 @@ k_analysis -> k_synth_ola_pair -> k_ola_fixup, with PCM and frame descriptors al
 shard across ranks with no data-path collective (weak scaling: every rank owns 64 utterances).
 Metric: frames/s (whole job) = frames processed by all ranks / max-over-ranks wall time of the K steps.
 
-ONE JSON line.  Next to the headline (metric / value / roofline / cpu_baseline) rank 0 of a 1-GPU run adds
+ONE JSON line.  A plain run does only what the headline needs: it builds the plans, takes the device out of its post-idle
+power state, runs the W warm-up and the K timed steps, writes --dump-outputs if asked, and prints metric / value /
+ms_per_step / config.  Everything else is measured with --full (a few minutes): the overlapped, from-idle and other-form
+figures, roofline, per_rank, host_contention and cpu_baseline, and rank 0 of a 1-GPU run adds
   "configs2": BASELINE configs[2] on the same 64 utterances -- analysis_compressed (mag 60 / phase 45, constant 5 ms
               rate) -> post-filter -> synthesis_from_compressed(b_const_rate): ms per step, per-kernel durations (HIP
               events) with their bound (bytes or fp32-MFMA flops), and its own cpu_baseline;
@@ -24,7 +27,7 @@ ONE JSON line.  Next to the headline (metric / value / roofline / cpu_baseline) 
 roofline carries, besides the spec-peak fraction: the HBM traffic of the dominant kernel measured IN THIS RUN (two
 rocprofv3 --pmc child passes; --traffic committed|none skips them) and this device's measured streaming read / write /
 copy ceilings (mpx_bw_probe).
---quick skips configs2 / e2e / corpus_shard / the CPU baselines / the PMC passes.
+--full --quick skips configs2 / e2e / corpus_shard / the CPU baselines / the PMC passes.
 --dump-outputs DIR writes a fixed sample of what the last timed step computed (feature rows, waveform) as DIR/*.npy.
 
     python bench.py --workload corpus --utts 10000      BASELINE configs[3] + configs[4] as the whole job: the corpus is
@@ -981,26 +984,31 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline as well: the overlapped, from-idle and other-form "
+                         "figures, roofline, per_rank, host_contention, CPU baselines, configs2, configs3_extraction_kernel, "
+                         "e2e, corpus_shard (a few minutes; --no-idle-probe, --quick, --no-cpu-baseline, --no-e2e, "
+                         "--no-power and --traffic trim it).  A plain run prints the headline only")
     ap.add_argument("--streams", type=int, default=2,
-                    help="HIP streams of the SECONDARY figure (value_overlapped / ms_per_step_overlapped): consecutive "
+                    help="HIP streams of the SECONDARY figure of --full (value_overlapped / ms_per_step_overlapped): consecutive "
                          "(independent) steps alternating between that many streams.  `value` / `ms_per_step` are always "
                          "one step at a time on one stream; 1 = no secondary figure")
     ap.add_argument("--form", choices=("one", "two"), default=os.environ.get("BENCH_FORM", "one"),
                     help="one: a step = ONE launch that analyses every frame, writes its feature rows and overlap-adds the "
                          "frame rebuilt from them (mpx_roundtrip_lossless_ola + mpx_ola_fixup); two: mpx_analysis_frames, then "
-                         "mpx_synthesis_lossless_ola reading the rows back (+ mpx_ola_fixup).  Same outputs; the other form is "
-                         "measured beside the chosen one (roofline.two_launch / roofline.one_launch)")
+                         "mpx_synthesis_lossless_ola reading the rows back (+ mpx_ola_fixup).  Same outputs; --full measures the "
+                         "other form beside the chosen one (roofline.two_launch / roofline.one_launch)")
     ap.add_argument("--no-idle-probe", action="store_true",
                     help="skip the from-idle repeat of the timed loop (profiling runs: keeps every launch in the steady state)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="headline only: no configs2 / e2e / CPU baselines")
+    ap.add_argument("--quick", action="store_true", help="with --full: no configs2 / e2e / CPU baselines / PMC passes")
     ap.add_argument("--no-e2e", action="store_true", help="skip the array-API / file-interface block (profiling runs)")
     ap.add_argument("--no-power", action="store_true",
                     help="skip the board-power loops (rocprofv3 --stats runs: their thousands of back-to-back launches of one "
                          "kernel would dominate its average duration; the steps are what the profile is about)")
     ap.add_argument("--workload", choices=("configs1", "corpus"), default="configs1",
                     help="'corpus' = BASELINE configs[3] + configs[4]: a --utts corpus, LPT-sharded over the ranks "
-                         "(tools/corpus_workload.py); the default is the headline configs[1] (+ configs2 / e2e / a corpus shard)")
+                         "(tools/corpus_workload.py); the default is the headline configs[1] (--full: + configs2 / e2e / a corpus shard)")
     ap.add_argument("--utts", type=int, default=10000, help="corpus size of --workload corpus (whole job, all ranks)")
     ap.add_argument("--traffic", choices=("live", "committed", "none"), default="live",
                     help="roofline.traffic: 'live' = rocprofv3 --pmc child passes in this run (falls back to the committed "
@@ -1143,6 +1151,8 @@ def main():
             step_form(*bufs[k])
 
     stream_pick = None
+    # A plain run sets up exactly as a --full one does (both forms' plans, every stream's buffers, the stream pick), so
+    # that its timed steps are the same launches on the same stream, streams[0].
     if n_streams > 1:      # streams that map to different hardware queues (pick_streams)
         streams, stream_pick = pick_streams(n_streams, enqueue)
     else:
@@ -1170,8 +1180,8 @@ def main():
     # The plans above were built on the host with the GPU idle, and a GPU coming out of idle goes through a power-management
     # transient of about 30 ms of busy time (tools/archive/step_curve_probe.py: the analysis launch runs 0.31 -> 0.41 -> 0.30 ms over
     # the first ~40 steps, after ANY idle period, whatever ran before it).  A corpus job is never in that state, so the
-    # device is taken out of it before the W warm-up steps; `ms_per_step_from_idle` below is the same W + K steps started
-    # 0.5 s after the last launch, for the record.
+    # device is taken out of it before the W warm-up steps; `ms_per_step_from_idle` below (--full) is the same W + K steps
+    # started 0.5 s after the last launch, for the record.
     PRECOND_STEPS = 0 if args.pmc_child else 64
     for i in range(PRECOND_STEPS):
         step(i, one_stream=True)
@@ -1182,16 +1192,17 @@ def main():
     if args.dump_outputs and rank == 0 and not args.pmc_child:   # the last timed step's outputs, before anything reuses bufs[0]
         dumped = dump_outputs(args.dump_outputs, feats, pcm_out)
     dt_ov = dt_idle = dt_two = None
-    if not args.pmc_child and not args.no_idle_probe:
+    if args.full and not args.pmc_child and not args.no_idle_probe:
         time.sleep(0.5)
         dt_idle = timed(one_stream=True)
         for i in range(PRECOND_STEPS):
             step(i, one_stream=True)
         torch.cuda.synchronize()
-    if n_streams > 1 and not args.pmc_child:   # secondary figure: consecutive (independent) steps alternating between streams
-        dt_ov = timed()                        # (the next step's analysis fills the tail of this step's launch)
-    if not args.pmc_child and not args.quick:  # the same K steps in the OTHER form (what a caller of the reference's two
-        step_other = step_two if one else step_one   # functions, analysis_lossless then synthesis_from_lossless, gets)
+    if args.full and n_streams > 1 and not args.pmc_child:   # secondary figure: consecutive (independent) steps alternating
+        dt_ov = timed()                                      # between streams (the next step's analysis fills the tail of
+                                                             # this step's launch)
+    if args.full and not args.pmc_child and not args.quick:  # the same K steps in the OTHER form (what a caller of the
+        step_other = step_two if one else step_one   # reference's two functions, analysis_lossless then synthesis_from_lossless, gets)
         with torch.cuda.stream(streams[0]):
             for _ in range(args.warmup):
                 step_other(*bufs[0])
@@ -1241,6 +1252,66 @@ def main():
         total_frames = float(fr.item())
     else:
         total_frames = float(F)
+
+    out = None
+    if rank == 0:
+        ms_step = dt / args.steps * 1e3
+        out = {
+            "metric": "frames/sec analysis+synthesis @48kHz FFT=4096",
+            "value": round(total_frames * args.steps / dt, 1),
+            "unit": "frames/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_step, 4),
+            "value_two_launch": (round(total_frames * args.steps / dt_two, 1) if (dt_two and one) else None),
+            "value_overlapped": (round(total_frames * args.steps / dt_ov, 1) if dt_ov else None),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": "configs[1]: %d synthetic 48 kHz %.0f s utterances per GPU, lossless analysis+synthesis, "
+                                   "FFT=4096, variable frame rate" % (UTTS_PER_GPU, DUR_S),
+                       "form": ("one launch per step: every frame analysed, its feature rows written, the frame rebuilt from "
+                                "them and overlap-added (mpx_roundtrip_lossless_ola + mpx_ola_fixup); --form two = "
+                                "mpx_analysis_frames, then mpx_synthesis_lossless_ola reading the rows back: roofline.two_launch"
+                                if one else "two launches per step (mpx_analysis_frames, mpx_synthesis_lossless_ola + mpx_ola_fixup)"),
+                       "frames_per_gpu": F, "audio_s_per_gpu": UTTS_PER_GPU * DUR_S,
+                       "x_realtime": round(UTTS_PER_GPU * DUR_S * world / (dt / args.steps), 1),
+                       "parallelism": "utterance-sharded x%d, no collective" % world,
+                       "streams": 1,
+                       "ms_per_step_single_stream": round(ms_step, 4),   # (== ms_per_step since round 6; kept for readers of old lines)
+                       "overlapped": ({"streams": n_streams, "stream_pick": stream_pick,
+                                       "ms_per_step_overlapped": round(dt_ov / args.steps * 1e3, 4),
+                                       "value_overlapped": round(total_frames * args.steps / dt_ov, 1),
+                                       "note": "the same K steps alternating between %d HIP streams with their own feature / "
+                                               "output buffers (the next step's analysis fills the tail of this step's launch): "
+                                               "rounds 3-5 printed THIS as `value`" % n_streams} if dt_ov else None),
+                       "other_form": ({"form": "two launches per step (mpx_analysis_frames, then mpx_synthesis_lossless_ola "
+                                               "reading the rows back, + mpx_ola_fixup): what analysis_lossless followed by "
+                                               "synthesis_from_lossless costs" if one else "one launch per step",
+                                       "ms_per_step": round(dt_two / args.steps * 1e3, 4),
+                                       "value": round(total_frames * args.steps / dt_two, 1)} if dt_two else None),
+                       "ms_per_step_from_idle": (round(dt_idle / args.steps * 1e3, 4) if dt_idle else None),
+                       "power_state_note": "%d untimed steps take the device out of its post-idle power transient before the "
+                                           "W warm-up steps (the plans are built on the host with the GPU idle; "
+                                           "tools/archive/step_curve_probe.py); ms_per_step_from_idle = the same W + K steps started "
+                                           "0.5 s after the last launch" % PRECOND_STEPS,
+                       "streams_note": "value / ms_per_step: one step at a time on one stream (the figure rocprofv3's kernel "
+                                       "durations add up to); config.overlapped: the same steps alternating between HIP streams",
+                       "ola_runs": (rt.synthesis.n_runs if one else splan.n_runs),
+                       "host_plan_build_s": round(t_plan, 4), "host_plan_build_cold_s": round(t_plan_cold, 3)},
+        }
+    if not args.full:   # a plain run: the headline line, nothing measured after the timed steps
+        if rank == 0:
+            if dumped:
+                out["dump_outputs"] = dumped
+            print(json.dumps(out))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- per-kernel durations with HIP events on the launch stream (separate, untimed-for-value loop)
     reps = max(5, min(args.steps, 20))
@@ -1486,57 +1557,7 @@ def main():
             roof["power"] = {"error": "%s: %s" % (type(e).__name__, e)}
 
     if rank == 0:
-        ms_step = dt / args.steps * 1e3
-        out = {
-            "metric": "frames/sec analysis+synthesis @48kHz FFT=4096",
-            "value": round(total_frames * args.steps / dt, 1),
-            "unit": "frames/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 4),
-            "value_two_launch": (round(total_frames * args.steps / dt_two, 1) if (dt_two and one) else None),
-            "value_overlapped": (round(total_frames * args.steps / dt_ov, 1) if dt_ov else None),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": "configs[1]: %d synthetic 48 kHz %.0f s utterances per GPU, lossless analysis+synthesis, "
-                                   "FFT=4096, variable frame rate" % (UTTS_PER_GPU, DUR_S),
-                       "form": ("one launch per step: every frame analysed, its feature rows written, the frame rebuilt from "
-                                "them and overlap-added (mpx_roundtrip_lossless_ola + mpx_ola_fixup); --form two = "
-                                "mpx_analysis_frames, then mpx_synthesis_lossless_ola reading the rows back: roofline.two_launch"
-                                if one else "two launches per step (mpx_analysis_frames, mpx_synthesis_lossless_ola + mpx_ola_fixup)"),
-                       "frames_per_gpu": F, "audio_s_per_gpu": UTTS_PER_GPU * DUR_S,
-                       "x_realtime": round(UTTS_PER_GPU * DUR_S * world / (dt / args.steps), 1),
-                       "parallelism": "utterance-sharded x%d, no collective" % world,
-                       "streams": 1,
-                       "ms_per_step_single_stream": round(ms_step, 4),   # (== ms_per_step since round 6; kept for readers of old lines)
-                       "overlapped": ({"streams": n_streams, "stream_pick": stream_pick,
-                                       "ms_per_step_overlapped": round(dt_ov / args.steps * 1e3, 4),
-                                       "value_overlapped": round(total_frames * args.steps / dt_ov, 1),
-                                       "note": "the same K steps alternating between %d HIP streams with their own feature / "
-                                               "output buffers (the next step's analysis fills the tail of this step's launch): "
-                                               "rounds 3-5 printed THIS as `value`" % n_streams} if dt_ov else None),
-                       "other_form": ({"form": "two launches per step (mpx_analysis_frames, then mpx_synthesis_lossless_ola "
-                                               "reading the rows back, + mpx_ola_fixup): what analysis_lossless followed by "
-                                               "synthesis_from_lossless costs" if one else "one launch per step",
-                                       "ms_per_step": round(dt_two / args.steps * 1e3, 4),
-                                       "value": round(total_frames * args.steps / dt_two, 1)} if dt_two else None),
-                       "ms_per_step_from_idle": (round(dt_idle / args.steps * 1e3, 4) if dt_idle else None),
-                       "power_state_note": "%d untimed steps take the device out of its post-idle power transient before the "
-                                           "W warm-up steps (the plans are built on the host with the GPU idle; "
-                                           "tools/archive/step_curve_probe.py); ms_per_step_from_idle = the same W + K steps started "
-                                           "0.5 s after the last launch" % PRECOND_STEPS,
-                       "streams_note": "value / ms_per_step: one step at a time on one stream (the figure rocprofv3's kernel "
-                                       "durations add up to); config.overlapped: the same steps alternating between HIP streams",
-                       "ola_runs": (rt.synthesis.n_runs if one else splan.n_runs),
-                       "host_plan_build_s": round(t_plan, 4), "host_plan_build_cold_s": round(t_plan_cold, 3)},
-            "roofline": roof,
-            "per_rank": per_rank,
-            "host_contention": host_contention,
-        }
+        out.update(roofline=roof, per_rank=per_rank, host_contention=host_contention)
         if dumped:
             out["dump_outputs"] = dumped
         if full and not args.no_cpu_baseline:

@@ -35,15 +35,15 @@ def _torchrun(nproc, script_args, extra_env, timeout=900):
 
 
 def test_bench_two_ranks_on_one_device():
-    one = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--quick"], cwd=ROOT,
-                         capture_output=True, text=True, timeout=900)
+    one = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--quick"],
+                         cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert one.returncode == 0, one.stderr[-2000:]
     j1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])
     assert len(j1["per_rank"]) == 1
     # the N > 1 line carries the WHOLE contract: cpu_baseline, roofline with the fraction's spread
-    # over the ranks, per_rank -- `BENCH_SHARE_DEVICE=1 python bench.py --gpus 2 --steps 20 --warmup 5` (no e2e block: the
-    # file-interface runs are covered by test_gpu_callers.py and take a minute)
-    out = _torchrun(2, ["bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5", "--no-e2e"],
+    # over the ranks, per_rank -- `BENCH_SHARE_DEVICE=1 python bench.py --gpus 2 --steps 20 --warmup 5 --full` (no e2e
+    # block: the file-interface runs are covered by test_gpu_callers.py and take a minute)
+    out = _torchrun(2, ["bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--no-e2e"],
                     {"BENCH_DIST_BACKEND": "gloo", "BENCH_SHARE_DEVICE": "1"}, timeout=1500)
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1                                             # rank 0 only

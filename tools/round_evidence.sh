@@ -17,7 +17,7 @@ bash tools/profile_round.sh $TAG > $E/profile_round.log 2>&1
 timeout 2400 python -m pytest tests -m gpu -q > $E/gpu_tests.txt 2>&1
 cp gpurun_out/tolerance_report.json $E/tolerance_report.json 2>/dev/null; tail -3 $E/gpu_tests.txt
 BENCH_SHARE_DEVICE=1 BENCH_DIST_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-    --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 8 --steps 20 --warmup 5 --no-e2e --traffic none \
+    --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 8 --steps 20 --warmup 5 --full --no-e2e --traffic none \
     --no-cpu-baseline > $E/share_device_n8.log 2> $E/share_device_n8.err
 grep '^{"metric"' $E/share_device_n8.log | tail -1 > $E/share_device_n8.json
 timeout 600 python bench.py --workload corpus --utts 1250 > $E/corpus1250.log 2> $E/corpus1250.err
