@@ -516,6 +516,20 @@ int mpx_min_phase(void* stream, int fft_len, const void* tables, const float* ma
                   float* out_imag, int64_t ld /* row pitch of mag and of the three outputs, floats */);
 
 /*
+ * True envelope (la.true_envelope, libaudio.py:295-340), one wavefront per frame.  For each row of in ([n_frames x H],
+ * H = fft_len / 2 + 1, row pitch ld_in): v = the row in dB (in_type 0: 20 log10 x, 1: x, 2: (20 / ln 10) x); then up
+ * to max_iters passes of sm = Re FFT(weights . IFFT(even extension of v))[0..H-1] (la.spectral_smoothing_rceps),
+ * stopping when sum |v - sm| < thres_db * H, else v = max(v, sm); out = the last sm, converted back (in_type 0: 10^(sm/20),
+ * 2: (ln 10 / 20) sm).  weights: float32 [fft_len], the cepstral weight of every index (hostmath.true_envelope_lifter).
+ * A row with a non-finite dB value (a zero or negative magnitude for in_type 0) is written as NaN.  iters (optional):
+ * int32 [n_frames], the passes made.  forced_iters (optional): exactly clamp(forced_iters[f], 1, max_iters) passes, no
+ * stop test.  ticket (optional): a device int32 the launch zeroes and then hands out frames from (else grid stride).
+ */
+int mpx_true_envelope(void* stream, int fft_len, const void* tables, const float* weights, const float* in,
+                      int64_t ld_in, int64_t n_frames, int32_t in_type, double thres_db, int32_t max_iters, float* out,
+                      int64_t ld_out, int32_t* iters, const int32_t* forced_iters, int32_t* ticket);
+
+/*
  * Noise gains on the device (magphase.py:902-906, Q10): per utterance u and class c (0 voiced, 1 unvoiced)
  * g = sqrt(exp( sum of out_sum over the class's frames / (n_frames_of_class * bins_per_frame) )), float64;
  * inv_gain[f] = 1/g(class of f) (float32, input of mpx_synthesis_compressed_ola); gains (optional, may be null):

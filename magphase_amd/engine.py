@@ -1259,6 +1259,44 @@ class Engine:
         m = self.to_host_f64(o_m[:, :H])
         return m * (self.to_host_f64(o_r[:, :H]) + 1j * self.to_host_f64(o_i[:, :H]))
 
+    def true_envelope(self, mats, in_type="abs", ncoeffs=60, thres_db=0.1, fade=0.7, max_iters=hm.TRUE_ENV_MAX_ITERS,
+                      forced_iters=None, want_iters=False, ticket=True):
+        """
+        la.true_envelope on a list of [F_i x H] matrices (numpy, or float32 device tensors) through ONE mpx_true_envelope
+        launch: the rows are concatenated at mpx_spec_ld(H).  -> (device out [sum F_i x ld], row offsets, device int32
+        passes per row or None).  max_iters = 1 with fade = fade_to_total is la.spectral_smoothing_rceps.
+        forced_iters (tests): int per row, exactly that many passes.  ticket: frames handed out by a device counter (the
+        faster form); False: by grid stride.
+        """
+        torch = _torch()
+        H = int(mats[0].shape[1])
+        N = hm.true_envelope_check(H, in_type, ncoeffs)
+        if any(int(m.shape[1]) != H for m in mats):
+            raise ValueError("true_envelope_batch: every matrix must have the same number of bins")
+        offs = np.concatenate(([0], np.cumsum([int(m.shape[0]) for m in mats]))).astype(np.int64)
+        F = int(offs[-1])
+        ld = int(self.lib.mpx_spec_ld(H))
+        x = self.empty((F, ld))
+        out = self.empty((F, ld))
+        for m, a, b in zip(mats, offs[:-1], offs[1:]):
+            if b > a:
+                src = m if torch.is_tensor(m) else torch.from_numpy(np.ascontiguousarray(m, dtype=np.float32))
+                x[int(a):int(b), :H].copy_(src, non_blocking=torch.is_tensor(m))
+        w = self.constant(("true_env_w", N, int(ncoeffs), float(fade)), lambda: hm.true_envelope_lifter(N, ncoeffs, fade))
+        iters = torch.empty(F, dtype=torch.int32, device=self.device) if (want_iters or forced_iters is not None) else None
+        forced = None
+        if forced_iters is not None:
+            forced = self.to_device(np.asarray(forced_iters, dtype=np.int32).reshape(F), np.int32)
+        tk = torch.empty(1, dtype=torch.int32, device=self.device) if ticket else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.mpx_true_envelope(self.stream_ptr(), N, self.tables(N).data_ptr(), w.data_ptr(),
+                                                  x.data_ptr(), ld, F, hm.TRUE_ENV_IN_TYPES.index(in_type),
+                                                  float(thres_db), int(max_iters), out.data_ptr(), ld,
+                                                  iters.data_ptr() if iters is not None else None,
+                                                  forced.data_ptr() if forced is not None else None,
+                                                  tk.data_ptr() if tk is not None else None), "mpx_true_envelope")
+        return out, offs, iters
+
     def warp_mag_matrix(self, mag_dim, H, alpha, b_mag_fbank_mel=False):
         """Device-resident [mag_dim x H] matrix of the magnitude compression and the C entry point that goes with it:
         the cepstral mel warp (la.sp_mel_warp, mpx_mel_warp) or the mel filter bank (la.sp_mel_warp_fbank,

@@ -858,3 +858,40 @@ def griffin_lim_fold(m_mag, phase, full):
     ph[:, 0] = 0.0
     ph[:, -1] = 0.0
     return m_mag.copy(), np.cos(ph) * sgn, np.sin(ph) * sgn
+
+
+TRUE_ENV_IN_TYPES = ("abs", "db", "log")   # in_type of la.true_envelope, in the order of mpx_true_envelope's codes
+TRUE_ENV_MAX_ITERS = 100                   # la.true_envelope's n_maxiter (libaudio.py:310)
+
+
+def true_envelope_lifter(N, ncoeffs, fade=0.7):
+    """
+    The weight w[n], n < N, by which la.spectral_smoothing_rceps (libaudio.py:203-238) multiplies the real cepstrum of
+    its N-point even extension: rceps_to_min_phase_rceps doubles c[1 : N/2], then c[ncoeffs:] = 0 and
+    c[ncoeffs - nf : ncoeffs] *= hanning(2 nf + 3)[nf + 2 : -1], nf = round(fade * ncoeffs) (numpy's half-to-even).
+    float64; ncoeffs = 0 gives all zeros.  ncoeffs above N/2 keeps part of the anticausal half, undoubled.
+    """
+    N, ncoeffs = int(N), int(ncoeffs)
+    if ncoeffs < 0 or ncoeffs > N:
+        raise ValueError("ncoeffs must be in 0..%d (the FFT length), got %d" % (N, ncoeffs))
+    fade = float(fade)
+    if not 0.0 <= fade <= 1.0:
+        raise ValueError("fade_to_total must be in [0, 1], got %r" % (fade,))
+    nf = int(np.round(fade * ncoeffs))
+    w = np.ones(N)
+    w[1:N // 2] = 2.0
+    w[ncoeffs:] = 0.0
+    w[ncoeffs - nf:ncoeffs] *= np.hanning(2 * nf + 3)[nf + 2:-1]
+    return w
+
+
+def true_envelope_check(H, in_type, ncoeffs):
+    """Argument checks of la.true_envelope / spectral_smoothing_rceps on [F x H] rows -> fft_len N = 2 (H - 1)."""
+    if in_type not in TRUE_ENV_IN_TYPES:
+        raise ValueError("in_type must be 'abs', 'db' or 'log', got %r" % (in_type,))
+    if int(H) - 1 not in (512, 1024, 2048):
+        raise ValueError("spectra must have 513, 1025 or 2049 bins (fft_len 1024 / 2048 / 4096), got %d" % int(H))
+    N = 2 * (int(H) - 1)
+    if int(ncoeffs) != ncoeffs or not 0 <= int(ncoeffs) <= N:
+        raise ValueError("ncoeffs must be an integer in 0..%d (the FFT length), got %r" % (N, ncoeffs))
+    return N

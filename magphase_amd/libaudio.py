@@ -440,3 +440,91 @@ def sp_mel_warp(m_sp, nbins_out, alpha=0.77, in_type=3):
     if in_type == 3:
         return np.exp(out)
     return out if in_type == 2 else out * (20 / np.log(10))
+
+
+# ---- cepstral helpers and the true envelope (libaudio.py:190-340): host float64 for the one-shot transforms, the device
+# kernel k_true_envelope (mpx_true_envelope) for the iterative estimator and the smoothing it is built from
+def rceps_to_min_phase_rceps(m_rceps):
+    """libaudio.py:190-197, quirks kept: c[:, 1 : N/2] is doubled IN PLACE, and the slice [:N/2 + 1] is over ROWS."""
+    nFFThalf = m_rceps.shape[1] // 2 + 1
+    m_rceps[:, 1:(nFFThalf - 1)] *= 2
+    return m_rceps[:nFFThalf]
+
+
+def rceps(m_data, in_type="log", out_type="compact"):
+    """libaudio.py:252-270: real cepstrum of [F x n] half spectra ('abs': protected log first; any other in_type is taken
+    as a log spectrum, as in the reference).  'compact': the first n coefficients, 1..n-3 doubled; else all 2(n-1)."""
+    m_data = np.asarray(m_data, dtype=np.float64)
+    if in_type == "abs":
+        m_data = log(m_data)
+    if out_type == "compact":
+        return hm.rceps_compact(m_data)
+    return np.fft.ifft(add_hermitian_half(m_data)).real
+
+
+def _te_inputs(mats):
+    import torch
+
+    out = []
+    for m in mats:
+        if torch.is_tensor(m):
+            if m.dim() != 2:
+                raise ValueError("true_envelope: 2-D [frames x bins] matrices expected")
+            out.append(m)
+        else:
+            m = np.asarray(m, dtype=np.float64)
+            if m.ndim != 2:
+                raise ValueError("true_envelope: 2-D [frames x bins] matrices expected")
+            out.append(m)
+    return out
+
+
+def true_envelope_batch(list_of_matrices, in_type="abs", ncoeffs=60, thres_db=0.1, return_device=False,
+                        return_iters=False):
+    """
+    la.true_envelope (libaudio.py:295-340) for many [F_i x H] matrices (numpy, or float32 device tensors) in ONE launch
+    of k_true_envelope.  H - 1 must be 512, 1024 or 2048.  Returns a list of float64 arrays (return_device: float32
+    device tensors [F_i x H], views of one buffer); return_iters: (that list, list of int32 passes per frame).
+    A row with a zero or negative magnitude ('abs') comes back all NaN, as in the reference.
+    """
+    mats = _te_inputs(list_of_matrices)
+    if not mats:
+        return ([], []) if return_iters else []
+    hm.true_envelope_check(int(mats[0].shape[1]), in_type, ncoeffs)
+    from .engine import get_engine
+
+    e = get_engine()
+    out, offs, iters = e.true_envelope(mats, in_type, int(ncoeffs), float(thres_db), want_iters=return_iters)
+    H = int(mats[0].shape[1])
+    rows = [out[int(a):int(b), :H] for a, b in zip(offs[:-1], offs[1:])]
+    if return_device:
+        res = rows
+    else:
+        host = iter(e.to_host_f64_many([r for r in rows if r.shape[0]]))
+        res = [next(host) if r.shape[0] else np.zeros((0, H)) for r in rows]
+    if not return_iters:
+        return res
+    it = iters if return_device else iters.cpu().numpy()
+    return res, [it[int(a):int(b)] for a, b in zip(offs[:-1], offs[1:])]
+
+
+def true_envelope(m_sp, in_type="abs", ncoeffs=60, thres_db=0.1):
+    """libaudio.py:295-340 on the device (k_true_envelope): the iterative cepstral envelope of [F x H] spectra, float64."""
+    return true_envelope_batch([m_sp], in_type=in_type, ncoeffs=ncoeffs, thres_db=thres_db)[0]
+
+
+def spectral_smoothing_rceps(m_sp_log, nc_total=60, fade_to_total=0.2):
+    """
+    libaudio.py:203-238 on the device (one pass of k_true_envelope, no stop test): [F x H] log spectra (any base) ->
+    float64.  The reference returns only the first N/2 + 1 rows of a matrix with more rows (its
+    rceps_to_min_phase_rceps slices rows); here every row is returned.
+    """
+    from .engine import get_engine
+
+    m = _te_inputs([m_sp_log])[0]
+    H = int(m.shape[1])
+    hm.true_envelope_check(H, "db", nc_total)
+    hm.true_envelope_lifter(2 * (H - 1), nc_total, fade_to_total)   # argument check before any device work
+    e = get_engine()
+    out, _, _ = e.true_envelope([m], "db", int(nc_total), 0.0, fade=float(fade_to_total), max_iters=1)
+    return e.to_host_f64(out[:, :H])
