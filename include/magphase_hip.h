@@ -530,6 +530,17 @@ int mpx_true_envelope(void* stream, int fft_len, const void* tables, const float
                       int64_t ld_out, int32_t* iters, const int32_t* forced_iters, int32_t* ticket);
 
 /*
+ * Per-frame gain of the type-2 analysis (analysis_with_del_comp_from_pm_type2, magphase.py:236-242), one wavefront per
+ * frame, float64.  Frames as mpx_analysis_frames takes them (frame_pos / frame_left / frame_right into sig).  voi: float32
+ * [n_frames], the epoch's voicing.  gain[f] = (voi[f] == 1) ? max |x| over the first fft_len/2 + 1 samples of the
+ * rotated, zero-padded or truncated FFT input : np.std of the whole Hann-windowed frame (all left + right + 1 samples).
+ * blocks_per_cu: workgroups of 8 waves per CU at most (<= 0: the default, 3; at most 8).
+ */
+int mpx_frame_gain(void* stream, int fft_len, const float* sig, const int64_t* frame_pos, const int32_t* frame_left,
+                   const int32_t* frame_right, const float* voi, int64_t n_frames, double* gain,
+                   int32_t blocks_per_cu);
+
+/*
  * Noise gains on the device (magphase.py:902-906, Q10): per utterance u and class c (0 voiced, 1 unvoiced)
  * g = sqrt(exp( sum of out_sum over the class's frames / (n_frames_of_class * bins_per_frame) )), float64;
  * inv_gain[f] = 1/g(class of f) (float32, input of mpx_synthesis_compressed_ola); gains (optional, may be null):

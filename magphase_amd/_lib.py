@@ -77,6 +77,7 @@ SYMBOLS = (
     "mpx_warp_phase_rows",
     "mpx_min_phase",
     "mpx_true_envelope",
+    "mpx_frame_gain",
     "mpx_noise_gains",
     "mpx_post_filter",
     "mpx_epoch_f0_track",
@@ -260,6 +261,8 @@ def _load_locked():
     lib.mpx_true_envelope.restype = ctypes.c_int
     lib.mpx_true_envelope.argtypes = [vp, ctypes.c_int, vp, vp, vp, i64, i64, i32, ctypes.c_double, i32, vp, i64, vp, vp,
                                       vp]
+    lib.mpx_frame_gain.restype = ctypes.c_int
+    lib.mpx_frame_gain.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, vp, i64, vp, i32]
     lib.mpx_noise_gains.restype = ctypes.c_int
     lib.mpx_noise_gains.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
     lib.mpx_post_filter.restype = ctypes.c_int

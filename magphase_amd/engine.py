@@ -2845,3 +2845,160 @@ def _const_rate_f0_voi(v_f0, v_pm_smpls, fs, const_rate_ms=5.0):
     v_f0_c = interp1(np.r_[v_f0[v_voi][0], v_f0[v_voi], v_f0[v_voi][-1]], np.r_[0, v_pm_smpls[v_voi], v_pm_smpls[-1]])
     v_voi_c = interp1(v_voi.astype(np.float64), v_pm_smpls) > 0.5
     return v_f0_c * v_voi_c
+
+
+TYPE2_ENV_NCOEFFS = 600   # la.true_envelope(..., ncoeffs=600, thres_db=0.1) of analysis_lossless_type2 (magphase.py:2829)
+TYPE2_ENV_THRES_DB = 0.1
+
+
+class Type2AnalysisPlan:
+    """
+    analysis_lossless_type2 (magphase.py:2793-2866) for a batch of utterances with epochs, (v_sig, fs, v_pm_sec, v_voi),
+    one fft_len.  A LosslessAnalysisPlan holds the signal and the one-period frame table (phase, f0, gain); this plan adds
+    the two-period half lengths of the same epochs (hostmath.two_period_frame_bounds: the magnitude frames), the voicing
+    of the gain and the float shifts of the unrounded epochs (hostmath.type2_shift).  Rows are those of the lossless plan:
+    utterance u's output is rows frame_off[u] + 1 .. frame_off[u + 1] (the reference drops row 0).
+    run(): k_analysis_f64 over the one-period frames (float64 transform: the mel warp of the compressed form reads the
+    phase, as in analysis_compressed), k_analysis_f64 over the two-period frames into the same magnitude rows (magnitudes
+    only: the phase rows keep the one-period values), k_frame_gain, k_true_envelope at 600 coefficients on those rows.
+    """
+
+    def __init__(self, engine, utts, fft_len=None):
+        self.engine = e = engine
+        utts = list(utts)
+        self.lossless = pl = LosslessAnalysisPlan(engine, utts, fft_len=fft_len)
+        N = self.fft_len = pl.fft_len
+        self.fs = list(pl.fs)
+        l2, r2, voi = [], [], []
+        self.v_f0, self.v_shift, self.long_frame_lens = [], [], []
+        for u, (_sig, fs, v_pm_sec, v_voi) in enumerate(utts):
+            n = int(pl.n_smpls[u])
+            pm_sec, vv = hm.clean_epochs(v_pm_sec, v_voi, check_len_smpls=n, fs=fs)
+            pm = np.asarray(pl.v_pm[u], dtype=np.int64)
+            if pm.size != vv.size:
+                raise RuntimeError("Type2AnalysisPlan: %d epochs planned, %d cleaned" % (pm.size, vv.size))
+            lft2, rgt2 = hm.two_period_frame_bounds(pm, n)
+            # the reference's warnings: the even-epoch frames, the odd ones (both incl. row 0), then the one-period ones
+            tot2 = lft2 + rgt2 + 1
+            self.long_frame_lens.append([int(x) for x in np.concatenate((tot2[0::2], tot2[1::2])) if x > N]
+                                        + list(pl.long_frame_lens[u]))
+            l2.append(lft2), r2.append(rgt2), voi.append((vv == 1).astype(np.float32))
+            self.v_f0.append(np.asarray(pl.v_f0[u], dtype=np.float64)[1:])
+            self.v_shift.append(hm.type2_shift(pm_sec * fs))
+        self.frame_off = np.asarray(pl.frame_off, dtype=np.int64)
+        F = self.total_frames = int(pl.total_frames)
+        cat = (lambda v, dt: np.concatenate(v).astype(dt) if v else np.zeros(0, dt))   # noqa: E731
+        t = e.to_device_packed([("left2", cat(l2, np.int64), np.int32), ("right2", cat(r2, np.int64), np.int32),
+                                ("voi", cat(voi, np.float32), np.float32),
+                                ("mag_only", np.zeros(F, dtype=np.float32), np.float32)])
+        self.left2, self.right2, self.voi, self.mag_only = t["left2"], t["right2"], t["voi"], t["mag_only"]
+        self.ld = int(e.lib.mpx_spec_ld(N // 2 + 1))   # one row pitch for the analysis rows and the envelope
+
+    def out_rows(self, u):
+        """Rows of utterance u in run()'s outputs: (first, end)."""
+        a, b = int(self.frame_off[u]), int(self.frame_off[u + 1])
+        return min(a + 1, b), b
+
+    def run(self, want_iters=False, forced_iters=None, gain_blocks_per_cu=0):
+        """-> (env, real, imag, gain, iters): float32 device rows [F x H] (one row pitch, self.ld; see out_rows), float64
+        device gain [F], int32 device passes per envelope row (want_iters / forced_iters) or None."""
+        e, torch = self.engine, _torch()
+        pl, N, F = self.lossless, self.fft_len, self.total_frames
+        H = N // 2 + 1
+        mag, real, imag, env = (e.empty((max(F, 1), self.ld)) for _ in range(4))
+        gain = torch.empty(max(F, 1), dtype=torch.float64, device=e.device)
+        iters = None
+        if want_iters or forced_iters is not None:
+            iters = torch.empty(max(F, 1), dtype=torch.int32, device=e.device)
+        feats = (mag[:F, :H], real[:F, :H], imag[:F, :H])
+        if F == 0:
+            return env[:0, :H], feats[1], feats[2], gain[:0], (iters[:0] if iters is not None else None)
+        pl.run(out=feats, precise=True)
+        # the two-period magnitudes overwrite the one-period ones (stream order); rows_in_use = 0: no phase row written
+        e.analysis_frames(N, pl.sig, pl.pos, self.left2, self.right2, out=feats, precise=True, rows_in_use=self.mag_only)
+        w = e.constant(("true_env_w", N, TYPE2_ENV_NCOEFFS, 0.7),
+                       lambda: hm.true_envelope_lifter(N, TYPE2_ENV_NCOEFFS, 0.7))
+        forced = None
+        if forced_iters is not None:
+            forced = e.to_device(np.asarray(forced_iters, dtype=np.int32).reshape(F), np.int32)
+        tk = torch.empty(1, dtype=torch.int32, device=e.device)
+        with torch.cuda.device(e.device):
+            _lib.check(e.lib.mpx_frame_gain(e.stream_ptr(), N, pl.sig.data_ptr(), pl.pos.data_ptr(), pl.left.data_ptr(),
+                                            pl.right.data_ptr(), self.voi.data_ptr(), F, gain.data_ptr(),
+                                            int(gain_blocks_per_cu)), "mpx_frame_gain")
+            _lib.check(e.lib.mpx_true_envelope(e.stream_ptr(), N, e.tables(N).data_ptr(), w.data_ptr(), mag.data_ptr(),
+                                               self.ld, F, hm.TRUE_ENV_IN_TYPES.index("abs"), TYPE2_ENV_THRES_DB,
+                                               hm.TRUE_ENV_MAX_ITERS, env.data_ptr(), self.ld,
+                                               iters.data_ptr() if iters is not None else None,
+                                               forced.data_ptr() if forced is not None else None, tk.data_ptr()),
+                       "mpx_true_envelope")
+        del mag   # (stream-ordered: the allocator reuses the magnitude rows after the envelope)
+        return env[:F, :H], feats[1], feats[2], gain[:F], iters
+
+
+class Type2CompressedAnalysisPlan:
+    """
+    analysis_compressed_type2 (magphase.py:3123-3196): a Type2AnalysisPlan, then format_for_modelling's two warps on its
+    device rows (mpx_mel_warp, alpha_phase = alpha), which read their input rows through row tables: at the variable
+    rate every row but row 0 of each utterance, at const_rate_ms > 0 the rows and weights of the grid
+    arange(step, pm[-1], step) over the float epochs cumsum(v_shift) (hostmath.var_to_const_rate_table); f0 / voicing by
+    _const_rate_f0_voi.  The gain is interpolated on the host (float64, as the reference).
+    """
+
+    def __init__(self, engine, utts, fft_len=None, mag_dim=60, phase_dim=45, const_rate_ms=-1.0):
+        self.engine = e = engine
+        self.t2 = t2 = Type2AnalysisPlan(engine, utts, fft_len=fft_len)
+        fs = self.fs = t2.fs[0] if t2.fs else None
+        if t2.fs.count(fs) != len(t2.fs):
+            raise ValueError("one sample rate per batch")
+        N = self.fft_len = t2.fft_len
+        H = N // 2 + 1
+        self.mag_dim, self.phase_dim = int(mag_dim), int(phase_dim)
+        self.const_rate_ms = float(const_rate_ms)
+        alpha = hm.define_alpha(fs)
+        cf, _ = hm.define_crossfade_params(fs)
+        k_full = hm.get_num_full_mel_coeffs_from_num_phase_coeffs(cf, phase_dim, alpha, fs)
+        self.w_mag = e.constant(("w_mag", self.mag_dim, H, float(alpha)), lambda: hm.warp_matrix(mag_dim, H, alpha))
+        self.w_ph = e.constant(("w_ph", int(k_full), H, float(alpha), self.phase_dim),
+                               lambda: hm.warp_matrix(k_full, H, alpha, nrows=phase_dim))
+        self.const = self.const_rate_ms > 0.0
+        row0, row1, rowt, self.f0_out, self.grid = [], [], [], [], []
+        for u in range(len(t2.v_f0)):
+            base, end = t2.out_rows(u)
+            v_f0 = t2.v_f0[u]
+            if self.const:
+                v_pm = np.cumsum(t2.v_shift[u])   # la.shift_to_pm (magphase.py:3130)
+                lo, hi, t = hm.var_to_const_rate_table(v_pm, self.const_rate_ms, fs)
+                self.grid.append(v_pm)
+                v_f0 = _const_rate_f0_voi(v_f0, v_pm, fs, self.const_rate_ms)
+            else:
+                lo = hi = np.arange(end - base, dtype=np.int64)
+                t = np.zeros(end - base)
+            row0.append(lo + base), row1.append(hi + base), rowt.append(t)
+            self.f0_out.append(v_f0)
+        self.out_off = np.concatenate(([0], np.cumsum([f.size for f in self.f0_out]))).astype(np.int64)
+        self.total_out_frames = int(self.out_off[-1])
+        f0_cat = np.concatenate(self.f0_out) if self.f0_out else np.zeros(0)
+        cat = (lambda v, dt: np.concatenate(v).astype(dt) if v else np.zeros(0, dt))   # noqa: E731
+        d = e.to_device_packed([("voi", (f0_cat > 0).astype(np.float32), np.float32),
+                                ("row0", cat(row0, np.int64), np.int32), ("row1", cat(row1, np.int64), np.int32),
+                                ("rowt", cat(rowt, np.float64), np.float32)])
+        self.voi, self.row0, self.row1, self.rowt = d["voi"], d["row0"], d["row1"], d["rowt"]
+
+    def run(self):
+        """-> ((mag [Fo x mag_dim], real, imag [Fo x phase_dim]) float32 device, gain float64 device [F]: the type-2
+        plan's rows, see Type2AnalysisPlan.out_rows)."""
+        e, torch = self.engine, _torch()
+        H = self.fft_len // 2 + 1
+        env, real, imag, gain, _ = self.t2.run()
+        Fo = self.total_out_frames
+        out = (e.empty((max(Fo, 1), self.mag_dim)), e.empty((max(Fo, 1), self.phase_dim)),
+               e.empty((max(Fo, 1), self.phase_dim)))
+        if Fo:
+            with torch.cuda.device(e.device):
+                _lib.check(e.lib.mpx_mel_warp(e.stream_ptr(), Fo, H, env.data_ptr(), real.data_ptr(), imag.data_ptr(),
+                                              self.row0.data_ptr(), self.row1.data_ptr(), self.rowt.data_ptr(),
+                                              self.w_mag.data_ptr(), self.mag_dim, self.w_ph.data_ptr(), self.phase_dim,
+                                              self.voi.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
+                                              out[2].data_ptr(), e.feat_ld(env, real, imag)), "mpx_mel_warp")
+        return tuple(o[:Fo] for o in out), gain

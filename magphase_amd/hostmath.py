@@ -72,6 +72,23 @@ def frame_bounds(v_pm_smpls, n_smpls):
     return pm.astype(np.int64), (ext[1:-1] - ext[:-2]).astype(np.int64), (ext[2:] - ext[1:-1]).astype(np.int64)
 
 
+def two_period_frame_bounds(pm, n_smpls):
+    """
+    magphase.py:2806-2816: analysis_lossless_type2 analyses the even and the odd epochs separately (windowing of each
+    subset, magphase.py:77-98) and interleaves the rows again, so frame i spans the rounded epochs i-2 .. i+2, with 0
+    and n - 1 as the outer limits.  pm: the rounded epochs (frame_bounds).  Returns (left int64[F], right int64[F]).
+    """
+    pm = np.asarray(pm, dtype=np.int64)
+    ext = np.hstack((0, 0, pm, n_smpls - 1, n_smpls - 1)).astype(np.int64)
+    return pm - ext[:-4], ext[4:] - pm
+
+
+def type2_shift(v_pm_smpls):
+    """magphase.py:2821: la.pm_to_shift(v_pm_smpls[1:]) of the UNROUNDED epochs, float64 (the first entry is pm[1])."""
+    v_pm_smpls = np.asarray(v_pm_smpls, dtype=np.float64)
+    return np.diff(np.hstack((0, v_pm_smpls[1:])))
+
+
 def shift_to_f0(v_shift, v_voi, fs):
     """magphase.py:2198-2207 with b_smooth=False (Q2)."""
     with np.errstate(divide="ignore", invalid="ignore"):

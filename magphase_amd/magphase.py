@@ -21,8 +21,8 @@ from . import libaudio as la
 from . import libutils as lu
 from .engine import (CompressedAnalysisPlan, CompressedSynthesisPlan, GriffinLimPlan, LosslessAnalysisPlan,
                      LosslessConstRateAnalysisPlan, LosslessConstRateSynthesisPlan, LosslessRoundTripPlan,
-                     LosslessSynthesisPlan, check_const_rate_ms, get_engine,
-                     plan_const_rate_synthesis)
+                     LosslessSynthesisPlan, Type2AnalysisPlan, Type2CompressedAnalysisPlan, check_const_rate_ms,
+                     get_engine, plan_const_rate_synthesis)
 
 _epoch_provider = None
 
@@ -871,6 +871,173 @@ def analysis_for_acoustic_modelling(wav_file, out_dir, fft_len=None, mag_dim=60,
     if not b_const_rate:
         write_featfile(v_shift, out_dir, file_id + '.shift')
     return
+
+
+# ======================================================================================================
+# type-2 analysis (magphase.py:2793-2866, :3123-3196): true-envelope magnitude of two-period frames, a per-frame gain
+# ======================================================================================================
+def _type2_rate(const_rate_ms):
+    """const_rate_ms of the type-2 functions: any finite number; <= 0 means the variable (pitch-synchronous) rate."""
+    if isinstance(const_rate_ms, (bool, np.bool_)) or not isinstance(const_rate_ms, (int, float, np.integer, np.floating)):
+        raise ValueError("const_rate_ms must be a finite number, got %r" % (const_rate_ms,))
+    v = float(const_rate_ms)
+    if not np.isfinite(v):
+        raise ValueError("const_rate_ms must be a finite number, got %r" % (const_rate_ms,))
+    return v
+
+
+def _type2_check(utts, fft_len):
+    """Host argument checks of the type-2 analysis: (v_sig, fs, v_pm_sec, v_voi) tuples, one fft_len the device path
+    takes (1024, 2048 or 4096) for the whole call, epochs and voicing of one length."""
+    N = None
+    for i, u in enumerate(utts):
+        if len(u) != 4:
+            raise ValueError("utts[%d]: expected (v_sig, fs, v_pm_sec, v_voi)" % i)
+        v_sig, fs, v_pm_sec, v_voi = u
+        if np.ndim(v_sig) != 1:
+            raise ValueError("utts[%d]: v_sig must be 1-D" % i)
+        if np.ndim(v_pm_sec) != 1 or np.shape(v_pm_sec) != np.shape(v_voi) or np.size(v_pm_sec) == 0:
+            raise ValueError("utts[%d]: v_pm_sec and v_voi must be non-empty 1-D vectors of one length" % i)
+        n = int(fft_len) if fft_len is not None else hm.define_fft_len(fs)
+        if n not in (1024, 2048, 4096):
+            raise ValueError("fft_len %r not supported by the HIP path (1024, 2048 or 4096)" % (n,))
+        if N is not None and n != N:
+            raise ValueError("all utterances of a call must share fft_len (bucket by sample rate)")
+        N = n
+    if N is not None:
+        hm.true_envelope_check(N // 2 + 1, "abs", 600)
+    return N
+
+
+def analysis_lossless_type2_batch(utts, fft_len=None, engine=None, return_device=False, return_iters=False):
+    """
+    Batched analysis_lossless_type2 (magphase.py:2793-2866) for utterances that already have epochs: utts = list of
+    (v_sig, fs, v_pm_sec, v_voi), one fft_len per call.  Returns a list of (m_mag_env, m_real, m_imag, v_f0, fs, v_shift,
+    v_gain): the true envelope (600 coefficients, thres_db 0.1) of the two-period magnitudes, the one-period phase, f0,
+    the float shifts of the unrounded epochs and the per-frame gain, all without the reference's row 0; float64 numpy
+    (return_device: float32 device rows for the three matrices and a float64 device gain; v_f0 / v_shift stay numpy).
+    Both transforms are float64 (k_analysis_f64), as analysis_compressed's.  A magnitude row with a zero bin gives an
+    all-NaN envelope row, as in the reference.  return_iters: each tuple gets the envelope's passes per frame (int32)
+    appended.  Engine: Type2AnalysisPlan.
+    """
+    utts = list(utts)
+    if not utts:
+        return []
+    _type2_check(utts, fft_len)
+    engine = engine or get_engine()
+    plan = Type2AnalysisPlan(engine, utts, fft_len=fft_len)
+    for lens in plan.long_frame_lens:
+        for n in lens:  # Q19: truncation warns, it does not raise (magphase.py:311-315)
+            warnings.warn(_WARN_LONG % (plan.fft_len, n))
+    env, real, imag, gain, iters = plan.run(want_iters=return_iters)
+    if not return_device:
+        h = engine.to_host_f64_many([env, real, imag]) if plan.total_frames else [np.zeros((0, env.shape[1]))] * 3
+        h_gain = gain.cpu().numpy()
+    h_iters = iters.cpu().numpy() if iters is not None else None
+    out = []
+    for u in range(len(utts)):
+        a, b = plan.out_rows(u)
+        if return_device:
+            feats = (env[a:b], real[a:b], imag[a:b])
+            g = gain[a:b]
+        else:
+            feats = tuple(x[a:b].copy() for x in h)
+            g = h_gain[a:b].copy()
+        r = feats + (plan.v_f0[u], plan.fs[u], plan.v_shift[u], g)
+        out.append(r + (h_iters[a:b].copy(),) if return_iters else r)
+    return out
+
+
+def analysis_lossless_type2(wav_file, fft_len=None, out_dir=None):
+    """magphase.py:2793-2866: (m_mag_env, m_real, m_imag, v_f0, fs, v_shift, v_gain); with out_dir: writes
+    <name>.mag (the envelope) / .real / .imag / .f0 / .shift as float32 and returns None (no gain file, as the reference)."""
+    v_sig, fs = la.read_audio_file(wav_file)
+    v_pm_sec, v_voi = _epochs_for(wav_file)
+    m_mag, m_real, m_imag, v_f0, fs, v_shift, v_gain = analysis_lossless_type2_batch([(v_sig, fs, v_pm_sec, v_voi)],
+                                                                                     fft_len=fft_len)[0]
+    if type(out_dir) is str:
+        file_id = os.path.basename(wav_file).split(".")[0]
+        write_featfile(m_mag, out_dir, file_id + ".mag")
+        write_featfile(m_real, out_dir, file_id + ".real")
+        write_featfile(m_imag, out_dir, file_id + ".imag")
+        write_featfile(v_f0, out_dir, file_id + ".f0")
+        write_featfile(v_shift, out_dir, file_id + ".shift")
+        return
+    return m_mag, m_real, m_imag, v_f0, fs, v_shift, v_gain
+
+
+def analysis_compressed_type2_batch(utts, fft_len=None, mag_dim=60, phase_dim=45, b_norm_mag=False,
+                                    const_rate_ms=-1.0, engine=None, return_device=False):
+    """
+    Batched analysis_compressed_type2 (magphase.py:3123-3196): utts = list of (v_sig, fs, v_pm_sec, v_voi), one sample
+    rate per call.  Returns a list of (m_mag_mel_log, m_real_mel, m_imag_mel, v_lf0_smth, v_shift, fs, fft_len, v_lgain).
+    const_rate_ms > 0 (any value): rows, f0 / voicing and gain on the grid of that period (v_shift stays at the variable
+    rate); <= 0: the variable rate.  v_lgain = la.log(v_gain); b_norm_mag: the mean of columns 1.. of each log-mel row is
+    subtracted, stored in column 0 and returned as v_lgain (magphase.py:3178-3182).  The three matrices are float64 numpy
+    (return_device: float32 device rows); v_lf0_smth, v_shift and v_lgain are float64 numpy.
+    """
+    const_rate_ms = _type2_rate(const_rate_ms)
+    utts = list(utts)
+    if not utts:
+        return []
+    _type2_check(utts, fft_len)
+    fs0 = utts[0][1]
+    if any(u[1] != fs0 for u in utts):
+        raise ValueError("one sample rate per batch")
+    hm.define_alpha(fs0)   # (ValueError for a sample rate the warp has no alpha for)
+    engine = engine or get_engine()
+    plan = Type2CompressedAnalysisPlan(engine, utts, fft_len=fft_len, mag_dim=mag_dim, phase_dim=phase_dim,
+                                       const_rate_ms=const_rate_ms)
+    for lens in plan.t2.long_frame_lens:
+        for n in lens:
+            warnings.warn(_WARN_LONG % (plan.fft_len, n))
+    (mag, real, imag), gain = plan.run()
+    h_gain = gain.cpu().numpy()
+    v_mean = None
+    if b_norm_mag:   # magphase.py:3178-3182, float64
+        md = mag.double()
+        v_mean = md[:, 1:].mean(dim=1)
+        md -= v_mean[:, None]
+        md[:, 0] = v_mean
+        mag.copy_(md)
+        v_mean = v_mean.cpu().numpy()
+    if not return_device:
+        h = (engine.to_host_f64_many([mag, real, imag]) if plan.total_out_frames else
+             [np.zeros((0, int(t.shape[1]))) for t in (mag, real, imag)])
+    lf0 = la.f0_to_lf0(np.concatenate([(f > 0).astype("float") * m for f, m in
+                                       zip(plan.f0_out, hm.medfilt3_batch(plan.f0_out))]))   # magphase.py:2497-2501
+    res = []
+    for u in range(len(utts)):
+        a, b = int(plan.out_off[u]), int(plan.out_off[u + 1])
+        fa, fb = plan.t2.out_rows(u)
+        v_gain = h_gain[fa:fb]
+        if plan.const:   # magphase.py:3135 (float64 on the host)
+            v_gain = interp_from_variable_to_const_frm_rate(v_gain, plan.grid[u], const_rate_ms, plan.fs)
+        v_lgain = v_mean[a:b].copy() if b_norm_mag else la.log(v_gain)
+        feats = (mag[a:b], real[a:b], imag[a:b]) if return_device else tuple(x[a:b].copy() for x in h)
+        res.append(feats + (lf0[a:b].copy(), plan.t2.v_shift[u], plan.fs, plan.fft_len, v_lgain))
+    return res
+
+
+def analysis_compressed_type2(wav_file, fft_len=None, out_dir=None, mag_dim=60, phase_dim=45, b_norm_mag=False,
+                              const_rate_ms=-1.0):
+    """magphase.py:3123-3196: (m_mag_mel_log, m_real_mel, m_imag_mel, v_lf0_smth, v_shift, fs, fft_len, v_lgain); with
+    out_dir: writes <name>.mag / .real / .imag / .lf0 (and .shift at the variable rate) and returns None."""
+    const_rate_ms = _type2_rate(const_rate_ms)
+    v_sig, fs = la.read_audio_file(wav_file)
+    v_pm_sec, v_voi = _epochs_for(wav_file)
+    r = analysis_compressed_type2_batch([(v_sig, fs, v_pm_sec, v_voi)], fft_len=fft_len, mag_dim=mag_dim,
+                                        phase_dim=phase_dim, b_norm_mag=b_norm_mag, const_rate_ms=const_rate_ms)[0]
+    if type(out_dir) is str:
+        file_id = os.path.basename(wav_file).split(".")[0]
+        write_featfile(r[0], out_dir, file_id + ".mag")
+        write_featfile(r[1], out_dir, file_id + ".real")
+        write_featfile(r[2], out_dir, file_id + ".imag")
+        write_featfile(r[3], out_dir, file_id + ".lf0")
+        if const_rate_ms <= 0.0:
+            write_featfile(r[4], out_dir, file_id + ".shift")
+        return
+    return r
 
 
 # ======================================================================================================
