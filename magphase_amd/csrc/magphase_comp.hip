@@ -1,10 +1,17 @@
-// magphase_comp.hip -- compressed-feature synthesis kernels (synthesis_from_compressed, magphase.py:825-997).
+// magphase_comp.hip -- compressed-feature synthesis kernels (synthesis_from_compressed, magphase.py:825-997), the mel warp of
+// the compressed analysis, and the kernels that overlap-add frames through a wave pair's LDS ring.
 //
-//   k_mel_unwarp_mfma / _tiled   [F x K] x [K x H] -> exp / identity: la.sp_mel_unwarp and phase_uncompress_type1_mcep as the
-//                         linear maps they are, K <= 64, on the f32 matrix instructions
-//   k_noise_stats<P>      per frame: windowed noise frame -> FFT -> sum_k (ln|Ns[k]|)^2, k = 1..N/2-1 (Q10 gain statistics)
-//   k_synth_comp_pair<P>  per chunk of frames: noise FFT (recomputed) + periodic/aperiodic spectrum assembly
-//                         (Appendix A2 steps 9-12) + inverse FFT + anti-ringing window + LDS overlap-add (as k_synth_ola_pair)
+//   k_mel_warp_mfma, k_warp_phase_rows     mel warp of the compressed analysis as a GEMM on the f32 matrix instructions
+//   k_mel_unwarp_mfma / _tiled             [F x K] x [K x H] -> exp / identity: la.sp_mel_unwarp and
+//                                          phase_uncompress_type1_mcep as the linear maps they are, K <= 64
+//   k_noise_stats<P>, k_noise_gains        per frame: windowed noise frame -> FFT -> sum_k (ln|Ns[k]|)^2 (Q10 gain statistics)
+//   k_post_filter, k_min_phase             log-mel post-filter (Q20); minimum-phase spectrum from a magnitude spectrum
+//   k_hpf_*, k_peak_abs, k_pcm16(_to_f32)  high-pass filter of the output, peak normalisation, int16 conversion
+//   the three pair kernels, built from one set of frame stages (pair_wave_setup .. pair_ordered_ola below):
+//   k_synth_comp_pair<P>                   noise FFT (recomputed or stored) + periodic/aperiodic spectrum assembly (Appendix
+//                                          A2 steps 9-12) + inverse FFT + anti-ringing window + overlap-add
+//   k_roundtrip_pair<P>                    lossless analysis and synthesis of the same frames in one launch (copy synthesis)
+//   k_griffin_lim_pair<P>                  one pitch-synchronous Griffin-Lim iteration
 #include <type_traits>
 
 #include "mpx_common.hpp"
@@ -16,6 +23,9 @@
 #ifndef MPX_COMP_DIT
 #define MPX_COMP_DIT 0   // 1: both transforms of the compact form in the DIT form (wave_fft.hpp; parity-green): -1 % on the
                          // synthesis side of configs[2], but 10 registers spill again at 12 waves per CU: off
+#endif
+#ifndef MPX_COMP_CH
+#define MPX_COMP_CH 16   // ring values in registers at a time in the pair kernels' overlap-add (ring_add_plane)
 #endif
 
 namespace mpx {
@@ -885,6 +895,197 @@ constexpr size_t lds_bytes_comp_pair() {
     return sizeof(float) * (size_t)(comp_tw_floats<P>() + kCompPairWaves * comp_xbuf_floats<P>() + kCompPairs * ring_len<P>() + 16);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Frame stages shared by the three pair kernels below (k_synth_comp_pair, k_roundtrip_pair, k_griffin_lim_pair).  Each
+// kernel is: pair_wave_setup, then per frame pair_frame_lane, its own way to a spectrum Z in registers (the two that
+// analyse a staged frame start from pair_analysis_spectrum), pair_inverse_fft_front, the start of the next frame's copy,
+// pair_inverse_fft_back, pair_ordered_ola.
+// ---------------------------------------------------------------------------------------------
+// What a wave of a pair kernel knows before its first frame.  LDS: twiddle table | one exchange buffer per wave | one ring
+// per pair | the pairs' tickets.
+struct PairWave {
+    float *tw, *xbuf, *ring;
+    int* turn;                            // the pair's ticket: index of the frame whose overlap-add is due
+    unsigned xbuf_byte, ring_byte;        // LDS byte addresses of xbuf and ring
+    int lane_id, half, wi_end;            // half: which of the pair's two waves; wi_end: end of the pair's work list
+    float wa_s0, wa_c0, ws_s0, ws_c0;     // analysis-side lane twiddle W_N^kappa and synthesis-side conj(W_N^lane)
+    PairCursor cur;                       // at the wave's first frame
+};
+
+// Fills w; false when the wave has no slot or no frame.  Contains the prologue's __syncthreads(): every wave of the
+// workgroup must reach this call before any returns.
+template <int P>
+__device__ __forceinline__ bool pair_wave_setup(PairWave& w, float* smem, const float* __restrict__ tw_g,
+                                                const RunDesc* __restrict__ runs, const int* __restrict__ slot_off,
+                                                const int* __restrict__ slot_runs, int nslots) {
+    constexpr int N = 128 * P, R = ring_len<P>();
+    const int wave = rfl((int)(threadIdx.x >> 6));
+    const int pair = wave >> 1;
+    constexpr int kRing0 = comp_tw_floats<P>() + kCompPairWaves * comp_xbuf_floats<P>();
+    static_assert(kCompPairs <= 16, "the tickets fit the 16 floats behind the rings");
+    w.tw = smem;
+    w.lane_id = threadIdx.x & 63;
+    w.half = wave & 1;
+    w.xbuf = smem + comp_tw_floats<P>() + wave * comp_xbuf_floats<P>();
+    w.xbuf_byte = 4u * (unsigned)(comp_tw_floats<P>() + wave * comp_xbuf_floats<P>());
+    w.ring = smem + kRing0 + pair * R;
+    w.ring_byte = 4u * (unsigned)(kRing0 + pair * R);
+    w.turn = reinterpret_cast<int*>(smem + kRing0 + kCompPairs * R) + pair;
+    pair_kernel_prologue<P, comp_compact<P>(), MPX_COMP_DIT != 0>(w.tw, tw_g, smem + kRing0, kCompPairs * R, w.turn - pair,
+                                                                  kCompPairs, kCompPairWaves * 64);
+    // (compact form: these constants live in the pad of the lane's table row and are read where they are used -- six
+    // registers that are not live across the frame loop)
+    sincospif(-2.0f * (float)kappa<P>(w.lane_id) / (float)N, &w.wa_s0, &w.wa_c0);
+    sincospif(2.0f * (float)w.lane_id / (float)N, &w.ws_s0, &w.ws_c0);
+    const int slot = blockIdx.x * kCompPairs + pair;
+    if (slot >= nslots) return false;
+    // cursor over this wave's frames: every second frame of every run of the pair's work list (see k_synth_ola_pair)
+    w.wi_end = slot_off[slot + 1];
+    w.cur.wi = slot_off[slot];
+    w.cur.ticket_base = 0;
+    pair_cursor_settle(w.cur, w.wi_end, w.half, runs, slot_runs);
+    return w.cur.valid != 0;
+}
+
+// A frame's samples are copied HBM -> LDS (into the exchange buffer) while the previous frame's inverse FFT finishes and
+// its overlap-add runs (same scheme as k_analysis): the first tile of frame g.
+template <int P>
+__device__ __forceinline__ void pair_stage_frame(const PairWave& w, const FrameGeom& g, int lane) {
+    stage_samples_async(g, 0, comp_compact<P>() ? 32 * P : 64 * P, w.xbuf_byte, lane);
+}
+// ... of a later frame, once the wave's own reads of the exchange buffer have returned
+template <int P>
+__device__ __forceinline__ void pair_stage_next(const PairWave& w, const FrameGeom& g, int lane) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    pair_stage_frame<P>(w, g, lane);
+}
+
+// The lane index and the lane twiddles as this frame sees them, laundered once per frame: call it INSIDE the frame loop
+// (hoisted out of it, what the compiler derives from them stays live across the loop).
+template <int P>
+__device__ __forceinline__ void pair_frame_lane(const PairWave& w, int& lane, float& wa_s, float& wa_c, float& ws_s,
+                                                float& ws_c) {
+    lane = w.lane_id;
+    wa_s = 0.0f, wa_c = 1.0f, ws_s = 0.0f, ws_c = 1.0f;
+    if constexpr (comp_compact<P>()) {
+        asm volatile("" : "+v"(lane));
+    } else {
+        wa_s = w.wa_s0, wa_c = w.wa_c0, ws_s = w.ws_s0, ws_c = w.ws_c0;
+        asm volatile("" : "+v"(lane), "+v"(wa_s), "+v"(wa_c), "+v"(ws_s), "+v"(ws_c));
+    }
+}
+
+// Analysis of the staged frame g (Hann halves): X[k] of the own bins k = lane + 64 q (no_*) and of their mirrors M - k
+// (nm_*), bin M/2 on lane 0 (nh_*).
+template <int P>
+__device__ __forceinline__ void pair_analysis_spectrum(const PairWave& w, const FrameGeom& g, int lane, float wa_c,
+                                                       float wa_s, float (&no_r)[P / 2], float (&no_i)[P / 2],
+                                                       float (&nm_r)[P / 2], float (&nm_i)[P / 2], float& nh_r, float& nh_i) {
+    constexpr bool kCompact = comp_compact<P>();
+    MPX_MARK("frame_setup");
+    staged_wait<0>();
+    noise_spectrum_paired<P, true, kCompact>(g, 0, w.tw, w.xbuf, w.xbuf_byte, lane, wa_c, wa_s, no_r, no_i, nm_r, nm_i, nh_r,
+                                             nh_i);
+    if (P != 32) {   // FFT output lanes hold bins kappa(lane) + 64 q; the rows and the merge want bins lane + 64 q
+        const int src = kappa<P>(lane);
+#pragma unroll
+        for (int q = 0; q < P / 2; ++q) {
+            no_r[q] = __shfl(no_r[q], src);
+            no_i[q] = __shfl(no_i[q], src);
+            nm_r[q] = __shfl(nm_r[q], src);
+            nm_i[q] = __shfl(nm_i[q], src);
+        }
+        nh_r = __shfl(nh_r, src);
+        nh_i = __shfl(nh_i, src);
+    }
+    mpx_pin(no_r), mpx_pin(no_i), mpx_pin(nm_r), mpx_pin(nm_i);
+}
+
+// Inverse transform of the merged spectrum, in place, in two halves.  The exchange buffer is idle once the front is
+// through: between the halves the kernel starts the copy of the next frame's samples (pair_stage_next).
+template <int P>
+__device__ __forceinline__ void pair_inverse_fft_front(const PairWave& w, float (&xr)[P], float (&xi)[P], int lane) {
+    constexpr bool kCompact = comp_compact<P>(), kDit = kCompact && MPX_COMP_DIT;
+    mpx_pin(xr), mpx_pin(xi);
+    MPX_MARK("fft_inverse");
+    if constexpr (kDit) {
+        // DIT form: its input wants register brev(j) <- bin lane + 64 j, its output is register i <-> samples 2 n, 2 n + 1
+        // with n = lane + 64 i: static renamings on both sides
+        constexpr int LBJ = ilog2(P);
+        float yr[P], yi[P];
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            yr[brev(j, LBJ)] = xr[j];
+            yi[brev(j, LBJ)] = xi[j];
+        }
+        const float4 pk = tw_half_pad<P>(w.tw, lane);
+        wave_fft_dit_compact_front<P, +1>(yr, yi, w.tw, w.xbuf, lane, pk.z, pk.w);
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+            xr[j] = yr[j];
+            xi[j] = yi[j];
+        }
+    } else if constexpr (kCompact) {
+        const float4 pk = tw_half_pad<P>(w.tw, lane);
+        wave_fft_front_compact<P, +1>(xr, xi, w.tw, w.xbuf, lane, pk.z, pk.w);
+    } else {
+        wave_fft_front<P, +1>(xr, xi, w.tw, w.xbuf, lane);
+    }
+}
+template <int P>
+__device__ __forceinline__ void pair_inverse_fft_back(float (&xr)[P], float (&xi)[P]) {
+    if constexpr (comp_compact<P>() && MPX_COMP_DIT) wave_fft_dit_back<P, +1>(xr, xi);
+    else fft_inreg<P, +1>(xr, xi);
+}
+
+// The ordered section of frame cur.fi: waits for the frame's ticket, streams out of the pair's ring what no later frame
+// reaches, adds the frame (xr = samples 2n, xi = samples 2n + 1) at its strip position, and passes the ticket on; the
+// last frame of a run streams out the rest and leaves the ring cleared.  combine(old, value, n) / live(q) as ring_add;
+// ROT: the rows are taken half a transform apart (the fftshift, see ring_add_plane).
+template <int P, bool ROT, typename CFn, typename LFn>
+__device__ __forceinline__ void pair_ordered_ola(const PairWave& w, const PairCursor& cur, float* smem,
+                                                 const RunDesc* __restrict__ runs, const int* __restrict__ pm_rel,
+                                                 float* __restrict__ strips, float* __restrict__ pcm, float (&xr)[P],
+                                                 float (&xi)[P], int lane, CFn combine, LFn live) {
+    constexpr int R = ring_len<P>();
+    constexpr bool kDit = comp_compact<P>() && MPX_COMP_DIT;
+    mpx_pin(xr), mpx_pin(xi);
+    MPX_MARK("ticket");
+    const int fi = cur.fi;
+    int* const turn = w.turn;
+    const RunDesc rd = runs[cur.ci];
+    float* strip = strips + rd.strip_off;
+    float* pcm0 = pcm + rd.out_base;
+    const int ticket = cur.ticket_base + (fi - cur.fb);
+    const int x = pm_rel[fi] - cur.x0;   // strip position of the frame's first sample
+    const int target = x & ~63;
+    const int flushed = (fi == cur.fb) ? 0 : ((pm_rel[fi - 1] - cur.x0) & ~63);
+    asm volatile("" ::"s"(x), "s"(flushed), "s"(rd.head_end), "s"(rd.out_lo), "s"(rd.out_hi), "s"(rd.flush_end));
+    while (__hip_atomic_load(turn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != ticket)
+        __builtin_amdgcn_s_sleep(1);
+    asm volatile("" ::: "memory");
+    MPX_MARK("flush");
+    if (flushed < target) flush_ring<R>(w.ring, strip, pcm0, rd.head_end, rd.out_lo, rd.out_hi, flushed, target, lane);
+    wave_sync();
+    MPX_MARK("overlap_add");
+    if constexpr (kCompPairWaves > 8 || ROT) {   // 16 ring values in registers at a time (<= 168 VGPRs)
+        constexpr int CH = (P < MPX_COMP_CH) ? P : MPX_COMP_CH;
+        const RingAddr ra = ring_addr<P>(w.ring_byte, x, lane);
+        ring_add_plane<P, 0, CH, kDit, ROT>(smem, ra, xr, lane, combine, live);
+        ring_add_plane<P, 1, CH, kDit, ROT>(smem, ra, xi, lane, combine, live);
+    } else {
+        ring_add<P>(smem, w.ring_byte, x, xr, xi, lane, combine, live);
+    }
+    wave_sync();
+    if (fi == cur.fe - 1) {   // last frame of the run: stream out the rest, leave the ring cleared
+        flush_ring<R>(w.ring, strip, pcm0, rd.head_end, rd.out_lo, rd.out_hi, target, rd.flush_end, lane);
+        wave_sync();
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __hip_atomic_store(turn, ticket + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    MPX_MARK("loop_end");
+}
+
 // LERP: every frame interpolates between two spectrum rows (row0 / row1 / rowt tables); false: one row per frame, row
 // index = frame index (variable-rate input, or rows already interpolated by mpx_mel_unwarp_rows) -- half the feature loads.
 // NPQ >= 0 (one-row-per-frame form): the caller's promise n_per <= 64 NPQ at compile time -- only the own bins of the
@@ -912,60 +1113,26 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_synth_comp_pair(const f
                                                                         float* __restrict__ strips,
                                                                         float* __restrict__ pcm, long long ld, int n_per) {
     static_assert(!SPEC || (P == 32 && !LERP), "stored noise spectra: N = 4096, one row per frame");
-    constexpr int M = 64 * P, N = 2 * M, R = ring_len<P>();
+    constexpr int M = 64 * P, N = 2 * M;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* tw = smem;
-    const int lane_id = threadIdx.x & 63;
-    const int wave = rfl((int)(threadIdx.x >> 6));
-    const int pair = wave >> 1, half = wave & 1;
     constexpr bool kCompact = comp_compact<P>();
-    float* xbuf = smem + comp_tw_floats<P>() + wave * comp_xbuf_floats<P>();
-    const unsigned xbuf_byte = 4u * (unsigned)(comp_tw_floats<P>() + wave * comp_xbuf_floats<P>());
-    constexpr int kRing0 = comp_tw_floats<P>() + kCompPairWaves * comp_xbuf_floats<P>();
-    float* ring = smem + kRing0 + pair * R;
-    const unsigned ring_byte = 4u * (unsigned)(kRing0 + pair * R);
-    int* turn = reinterpret_cast<int*>(smem + kRing0 + kCompPairs * R) + pair;
-    static_assert(kCompPairs <= 16, "the tickets fit the 16 floats behind the rings");
-    pair_kernel_prologue<P, kCompact, MPX_COMP_DIT != 0>(tw, tw_g, smem + kRing0, kCompPairs * R, turn - pair, kCompPairs,
-                                                         kCompPairWaves * 64);
+    PairWave w;
+    if (!pair_wave_setup<P>(w, smem, tw_g, runs, slot_off, slot_runs, nslots)) return;
+    float* const tw = w.tw;
+    float* const xbuf = w.xbuf;
+    const unsigned xbuf_byte = w.xbuf_byte;
+    PairCursor cur = w.cur;
 
-    float wa_s0, wa_c0, ws_s0, ws_c0;   // analysis-side lane twiddle W_N^kappa and synthesis-side conj(W_N^lane)
-    sincospif(-2.0f * (float)kappa<P>(lane_id) / (float)N, &wa_s0, &wa_c0);
-    sincospif(2.0f * (float)lane_id / (float)N, &ws_s0, &ws_c0);
-    // (compact form: these constants live in the pad of the lane's table row and are read where they are used -- six
-    // registers that are not live across the frame loop)
-    const int slot = blockIdx.x * kCompPairs + pair;
-    if (slot >= nslots) return;
-
-    // cursor over this wave's frames: every second frame of every run of the pair's work list (see k_synth_ola_pair)
-    typedef PairCursor Cursor;
-    const int wi_end = slot_off[slot + 1];
-    auto advance = [&](Cursor& c) { pair_cursor_advance(c, wi_end, half, runs, slot_runs); };
-    Cursor cur;
-    cur.wi = slot_off[slot];
-    cur.ticket_base = 0;
-    pair_cursor_settle(cur, wi_end, half, runs, slot_runs);
-
-    if (!cur.valid) return;
-
-    // the noise samples of a frame are copied HBM -> LDS (into the transpose buffer) while the previous frame's
-    // inverse FFT finishes and its overlap-add runs (same scheme as k_analysis)
-    constexpr int kTile = kCompact ? 32 * P : 64 * P;
     FrameGeom g = frame_geom(noise, tb.npos[cur.fi], tb.nleft[cur.fi], tb.nright[cur.fi], N);
-    if constexpr (!SPEC) stage_samples_async(g, 0, kTile, xbuf_byte, lane_id);
+    if constexpr (!SPEC) pair_stage_frame<P>(w, g, w.lane_id);
 
     while (cur.valid) {
-        int lane = lane_id;
-        float wa_s = 0.0f, wa_c = 1.0f, ws_s = 0.0f, ws_c = 1.0f;
+        int lane;
+        float wa_s, wa_c, ws_s, ws_c;
+        pair_frame_lane<P>(w, lane, wa_s, wa_c, ws_s, ws_c);
         constexpr float lc = 1.0f, ls = 0.0f;
-        if constexpr (kCompact) {
-            asm volatile("" : "+v"(lane));
-        } else {
-            wa_s = wa_s0, wa_c = wa_c0, ws_s = ws_s0, ws_c = ws_c0;
-            asm volatile("" : "+v"(lane), "+v"(wa_s), "+v"(wa_c), "+v"(ws_s), "+v"(ws_c));
-        }
-        Cursor nxt = cur;
-        advance(nxt);
+        PairCursor nxt = cur;
+        pair_cursor_advance(nxt, w.wi_end, w.half, runs, slot_runs);
         const int fi = cur.fi;
 
         float xr[P], xi[P];
@@ -1291,37 +1458,12 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_synth_comp_pair(const f
             }
             hermitian_merge<P>(xr, xi, xm, lane, ws_c, ws_s);
         }
-        constexpr bool kDit = kCompact && MPX_COMP_DIT;
-        if constexpr (kDit) {
-            // DIT form: its input wants register brev(j) <- bin lane + 64 j, its output is register i <-> samples 2 n, 2 n + 1
-            // with n = lane + 64 i: static renamings on both sides
-            constexpr int LBJ = ilog2(P);
-            float yr[P], yi[P];
-#pragma unroll
-            for (int j = 0; j < P; ++j) {
-                yr[brev(j, LBJ)] = xr[j];
-                yi[brev(j, LBJ)] = xi[j];
-            }
-            const float4 pk = tw_half_pad<P>(tw, lane);
-            wave_fft_dit_compact_front<P, +1>(yr, yi, tw, xbuf, lane, pk.z, pk.w);
-#pragma unroll
-            for (int j = 0; j < P; ++j) {
-                xr[j] = yr[j];
-                xi[j] = yi[j];
-            }
-        } else if constexpr (kCompact) {
-            const float4 pk = tw_half_pad<P>(tw, lane);
-            wave_fft_front_compact<P, +1>(xr, xi, tw, xbuf, lane, pk.z, pk.w);
-        } else {
-            wave_fft_front<P, +1>(xr, xi, tw, xbuf, lane);
-        }
-        if (!SPEC && nxt.valid) {   // the exchange buffer is idle from here on: start the copy of the next frame's noise
+        pair_inverse_fft_front<P>(w, xr, xi, lane);
+        if (!SPEC && nxt.valid) {
             g = frame_geom(noise, tb.npos[nxt.fi], tb.nleft[nxt.fi], tb.nright[nxt.fi], N);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            stage_samples_async(g, 0, kTile, xbuf_byte, lane);
+            pair_stage_next<P>(w, g, lane);
         }
-        if constexpr (kDit) wave_fft_dit_back<P, +1>(xr, xi);
-        else fft_inreg<P, +1>(xr, xi);
+        pair_inverse_fft_back<P>(xr, xi);
 
         // ---- anti-ringing window (magphase.py:969-973, Q14): centred asymmetric Hann, zero outside
         const int wl = tb.win_l[fi], wr = tb.win_r[fi];
@@ -1329,46 +1471,14 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_synth_comp_pair(const f
         const float inv_wr = (wr > 0) ? 1.0f / (float)wr : 0.0f;
         const int kadd = (wl == 0) ? 1 : 0;
         const int n_lo = N / 2 - wl, n_hi = N / 2 + wr;   // support [n_lo, n_hi]
-
-        // ---- ordered section: wait for this frame's ticket
-        const RunDesc rd = runs[cur.ci];
-        float* strip = strips + rd.strip_off;
-        float* pcm0 = pcm + rd.out_base;
-        const int ticket = cur.ticket_base + (fi - cur.fb);
-        const int x = tb.pm_rel[fi] - cur.x0;   // strip position of the frame's first sample
-        const int target = x & ~63;
-        const int flushed = (fi == cur.fb) ? 0 : ((tb.pm_rel[fi - 1] - cur.x0) & ~63);
-        asm volatile("" ::"s"(x), "s"(flushed), "s"(rd.head_end), "s"(rd.out_lo), "s"(rd.out_hi), "s"(rd.flush_end));
-        while (__hip_atomic_load(turn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != ticket)
-            __builtin_amdgcn_s_sleep(1);
-        asm volatile("" ::: "memory");
-        if (flushed < target) flush_ring<R>(ring, strip, pcm0, rd.head_end, rd.out_lo, rd.out_hi, flushed, target, lane);
-        wave_sync();
-        // register rows whose samples all lie outside the window support add nothing: skipped (wave-uniform)
         auto win_add = [&](float o, float v, int n) {
             const int ks = n - n_lo;
-            const float w = (ks >= 0 && n <= n_hi) ? half_window(ks, wl, wl + wr, kadd, inv_wl, inv_wr, 0) : 0.0f;
-            return fmaf(v, w, o);
+            const float w_ = (ks >= 0 && n <= n_hi) ? half_window(ks, wl, wl + wr, kadd, inv_wl, inv_wr, 0) : 0.0f;
+            return fmaf(v, w_, o);
         };
+        // register rows whose samples all lie outside the window support add nothing: skipped (wave-uniform)
         auto row_live = [&](int q) { return !(128 * q + 127 < n_lo || 128 * q > n_hi); };
-        if constexpr (kCompPairWaves > 8) {   // 16 ring values in registers at a time (<= 168 VGPRs)
-#ifndef MPX_COMP_CH
-#define MPX_COMP_CH 16
-#endif
-            constexpr int CH = (P < MPX_COMP_CH) ? P : MPX_COMP_CH;
-            const RingAddr ra = ring_addr<P>(ring_byte, x, lane);
-            ring_add_plane<P, 0, CH, kDit>(smem, ra, xr, lane, win_add, row_live);
-            ring_add_plane<P, 1, CH, kDit>(smem, ra, xi, lane, win_add, row_live);
-        } else {
-            ring_add<P>(smem, ring_byte, x, xr, xi, lane, win_add, row_live);
-        }
-        wave_sync();
-        if (fi == cur.fe - 1) {   // last frame of the run: stream out the rest, leave the ring cleared
-            flush_ring<R>(ring, strip, pcm0, rd.head_end, rd.out_lo, rd.out_hi, target, rd.flush_end, lane);
-            wave_sync();
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __hip_atomic_store(turn, ticket + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        pair_ordered_ola<P, false>(w, cur, smem, runs, tb.pm_rel, strips, pcm, xr, xi, lane, win_add, row_live);
         cur = nxt;
     }
 }
@@ -1405,80 +1515,31 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
                                                                        float* __restrict__ omag, float* __restrict__ oreal,
                                                                        float* __restrict__ oimag, float* __restrict__ strips,
                                                                        float* __restrict__ pcm, long long ld) {
-    constexpr int M = 64 * P, N = 2 * M, R = ring_len<P>(), HP = P / 2;
+    constexpr int M = 64 * P, N = 2 * M, HP = P / 2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* tw = smem;
-    const int lane_id = threadIdx.x & 63;
-    const int wave = rfl((int)(threadIdx.x >> 6));
-    const int pair = wave >> 1, half = wave & 1;
-    constexpr bool kCompact = comp_compact<P>();
-    float* xbuf = smem + comp_tw_floats<P>() + wave * comp_xbuf_floats<P>();
-    const unsigned xbuf_byte = 4u * (unsigned)(comp_tw_floats<P>() + wave * comp_xbuf_floats<P>());
-    constexpr int kRing0 = comp_tw_floats<P>() + kCompPairWaves * comp_xbuf_floats<P>();
-    float* ring = smem + kRing0 + pair * R;
-    const unsigned ring_byte = 4u * (unsigned)(kRing0 + pair * R);
-    int* turn = reinterpret_cast<int*>(smem + kRing0 + kCompPairs * R) + pair;
-    pair_kernel_prologue<P, kCompact, MPX_COMP_DIT != 0>(tw, tw_g, smem + kRing0, kCompPairs * R, turn - pair, kCompPairs,
-                                                         kCompPairWaves * 64);
+    PairWave w;
+    if (!pair_wave_setup<P>(w, smem, tw_g, runs, slot_off, slot_runs, nslots)) return;
+    PairCursor cur = w.cur;
 
-    float wa_s0, wa_c0, ws_s0, ws_c0;   // analysis-side lane twiddle W_N^kappa and synthesis-side conj(W_N^lane)
-    sincospif(-2.0f * (float)kappa<P>(lane_id) / (float)N, &wa_s0, &wa_c0);
-    sincospif(2.0f * (float)lane_id / (float)N, &ws_s0, &ws_c0);
-    const int slot = blockIdx.x * kCompPairs + pair;
-    if (slot >= nslots) return;
-
-    typedef PairCursor Cursor;
-    const int wi_end = slot_off[slot + 1];
-    auto advance = [&](Cursor& c) { pair_cursor_advance(c, wi_end, half, runs, slot_runs); };
-    Cursor cur;
-    cur.wi = slot_off[slot];
-    cur.ticket_base = 0;
-    pair_cursor_settle(cur, wi_end, half, runs, slot_runs);
-    if (!cur.valid) return;
-
-    constexpr int kTile = kCompact ? 32 * P : 64 * P;
     FrameGeom g = frame_geom(sig, fpos[cur.fi], fleft[cur.fi], fright[cur.fi], N);
-    stage_samples_async(g, 0, kTile, xbuf_byte, lane_id);
+    pair_stage_frame<P>(w, g, w.lane_id);
 
     while (cur.valid) {
-        int lane = lane_id;
-        float wa_s = 0.0f, wa_c = 1.0f, ws_s = 0.0f, ws_c = 1.0f;
-        constexpr float lc = 1.0f, ls = 0.0f;
-        if constexpr (kCompact) {
-            asm volatile("" : "+v"(lane));
-        } else {
-            wa_s = wa_s0, wa_c = wa_c0, ws_s = ws_s0, ws_c = ws_c0;
-            asm volatile("" : "+v"(lane), "+v"(wa_s), "+v"(wa_c), "+v"(ws_s), "+v"(ws_c));
-        }
-        Cursor nxt = cur;
-        advance(nxt);
+        int lane;
+        float wa_s, wa_c, ws_s, ws_c;
+        pair_frame_lane<P>(w, lane, wa_s, wa_c, ws_s, ws_c);
+        PairCursor nxt = cur;
+        pair_cursor_advance(nxt, w.wi_end, w.half, runs, slot_runs);
         const int fi = cur.fi;
 
         float xr[P], xi[P];
         {
-            // ---- analysis: X[k] of the own bins k = lane + 64 q and of their mirrors M - k, bin M/2 on lane 0
             float no_r[HP], no_i[HP], nm_r[HP], nm_i[HP], nh_r, nh_i;
-            MPX_MARK("frame_setup");
-            staged_wait<0>();
-            noise_spectrum_paired<P, true, kCompact>(g, 0, tw, xbuf, xbuf_byte, lane, wa_c, wa_s, no_r, no_i, nm_r, nm_i, nh_r,
-                                                     nh_i, lc, ls);
-            if (P != 32) {   // FFT output lanes hold bins kappa(lane) + 64 q; the rows and the merge want bins lane + 64 q
-                const int src = kappa<P>(lane);
-#pragma unroll
-                for (int q = 0; q < HP; ++q) {
-                    no_r[q] = __shfl(no_r[q], src);
-                    no_i[q] = __shfl(no_i[q], src);
-                    nm_r[q] = __shfl(nm_r[q], src);
-                    nm_i[q] = __shfl(nm_i[q], src);
-                }
-                nh_r = __shfl(nh_r, src);
-                nh_i = __shfl(nh_i, src);
-            }
+            pair_analysis_spectrum<P>(w, g, lane, wa_c, wa_s, no_r, no_i, nm_r, nm_i, nh_r, nh_i);
             // ---- per bin pair q: lossless features (magphase.py:466-474; as k_analysis: X == 0 -> all three 0), their
             // stores, and the pair's step of the Hermitian merge -- feat_merge_paired's arithmetic on the values just
             // stored (X = mag (R + jI) / |R + jI|, magphase.py:1761-1766), pair by pair so that a pair's four inputs die
             // as its four outputs appear (all 99 features at once, as k_synth_ola_pair holds them: 49 spilled registers)
-            mpx_pin(no_r), mpx_pin(no_i), mpx_pin(nm_r), mpx_pin(nm_i);
             MPX_MARK("features_stores_merge");
             auto feat = [](float x_r, float x_i, float& m, float& a, float& b) {
                 const float s2 = x_r * x_r + x_i * x_i;
@@ -1487,8 +1548,8 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
                 a = x_r * r;
                 b = x_i * r;
             };
-            if constexpr (kCompact) {   // kappa(lane) == lane: the synthesis-side twiddle is the conjugate of the split's
-                const float4 pk = tw_half_pad<P>(tw, lane);
+            if constexpr (comp_compact<P>()) {   // kappa(lane) == lane: the synthesis-side twiddle is the conjugate of the split's
+                const float4 pk = tw_half_pad<P>(w.tw, lane);
                 ws_c = pk.x;
                 ws_s = -pk.y;
             }
@@ -1542,98 +1603,27 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
                     x_i = lane0 ? 0.0f : x_i;
                     p_i = lane0 ? 0.0f : p_i;
                 }
-                const float er = x_r + p_r, ei = x_i - p_i, tr = x_r - p_r, ti = x_i + p_i;
-                const float cq = cos2p<P>(q), sq = sin2p<P>(q);
-                const float wr = ws_c * cq - ws_s * sq, wi = ws_c * sq + ws_s * cq;
-                const float orr = wr * tr - wi * ti, oi = wr * ti + wi * tr;
-                xr[q] = er - oi;
-                xi[q] = ei + orr;
-                zr[q] = er + oi;
-                zi[q] = orr - ei;
+                merge_pair_step<P>(q, x_r, x_i, p_r, p_i, ws_c, ws_s, xr[q], xi[q], zr[q], zi[q]);
             }
             float mH, aH, bH;
             feat(nh_r, nh_i, mH, aH, bH);
             mhi[-64 * (HP - 1)] = lane0 ? mH : hm;
             rhi[-64 * (HP - 1)] = lane0 ? aH : ha;
             ihi[-64 * (HP - 1)] = lane0 ? bH : hb;
-            // bin M/2 (lane 0): Z = 2 conj(X); then the hand-over of Z[M - k] to the lanes that own those registers
-            const float hr = 2.0f * nh_r, hi = -2.0f * nh_i;
-            const int src_lane = (64 - lane) & 63;
-#pragma unroll
-            for (int r = HP; r < P; ++r) {
-                const float pr = lane0 ? ((r == HP) ? hr : zr[P - r]) : zr[P - 1 - r];
-                const float pi = lane0 ? ((r == HP) ? hi : zi[P - r]) : zi[P - 1 - r];
-                xr[r] = __shfl(pr, src_lane);
-                xi[r] = __shfl(pi, src_lane);
-            }
+            // bin M/2 (lane 0): Z = 2 conj(X)
+            merge_handover<P>(zr, zi, 2.0f * nh_r, -2.0f * nh_i, xr, xi, lane);
         }
-        mpx_pin(xr), mpx_pin(xi);
-        MPX_MARK("fft_inverse");
-        constexpr bool kDit = kCompact && MPX_COMP_DIT;
-        if constexpr (kDit) {
-            constexpr int LBJ = ilog2(P);
-            float yr[P], yi[P];
-#pragma unroll
-            for (int j = 0; j < P; ++j) {
-                yr[brev(j, LBJ)] = xr[j];
-                yi[brev(j, LBJ)] = xi[j];
-            }
-            const float4 pk = tw_half_pad<P>(tw, lane);
-            wave_fft_dit_compact_front<P, +1>(yr, yi, tw, xbuf, lane, pk.z, pk.w);
-#pragma unroll
-            for (int j = 0; j < P; ++j) {
-                xr[j] = yr[j];
-                xi[j] = yi[j];
-            }
-        } else if constexpr (kCompact) {
-            const float4 pk = tw_half_pad<P>(tw, lane);
-            wave_fft_front_compact<P, +1>(xr, xi, tw, xbuf, lane, pk.z, pk.w);
-        } else {
-            wave_fft_front<P, +1>(xr, xi, tw, xbuf, lane);
-        }
-        if (nxt.valid) {   // the exchange buffer is idle from here on: start the copy of the next frame's samples
+        pair_inverse_fft_front<P>(w, xr, xi, lane);
+        if (nxt.valid) {
             g = frame_geom(sig, fpos[nxt.fi], fleft[nxt.fi], fright[nxt.fi], N);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            stage_samples_async(g, 0, kTile, xbuf_byte, lane);
+            pair_stage_next<P>(w, g, lane);
         }
-        if constexpr (kDit) wave_fft_dit_back<P, +1>(xr, xi);
-        else fft_inreg<P, +1>(xr, xi);
-
-        // ---- ordered section: wait for this frame's ticket
-        mpx_pin(xr), mpx_pin(xi);
-        MPX_MARK("ticket");
-        const RunDesc rd = runs[cur.ci];
-        float* strip = strips + rd.strip_off;
-        float* pcm0 = pcm + rd.out_base;
-        const int ticket = cur.ticket_base + (fi - cur.fb);
-        const int x = pm_rel[fi] - cur.x0;   // strip position of the frame's first sample
-        const int target = x & ~63;
-        const int flushed = (fi == cur.fb) ? 0 : ((pm_rel[fi - 1] - cur.x0) & ~63);
-        asm volatile("" ::"s"(x), "s"(flushed), "s"(rd.head_end), "s"(rd.out_lo), "s"(rd.out_hi), "s"(rd.flush_end));
-        while (__hip_atomic_load(turn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != ticket)
-            __builtin_amdgcn_s_sleep(1);
-        asm volatile("" ::: "memory");
-        MPX_MARK("flush");
-        if (flushed < target) flush_ring<R>(ring, strip, pcm0, rd.head_end, rd.out_lo, rd.out_hi, flushed, target, lane);
-        wave_sync();
-        MPX_MARK("overlap_add");
+        pair_inverse_fft_back<P>(xr, xi);
         constexpr float kScale = 0.5f / (float)M;   // the inverse transform's scale, on the overlap-add's multiply-add
         auto plain_add = [](float o, float v, int) { return fmaf(v, kScale, o); };
         auto all_rows = [](int) { return true; };
-        {   // 16 ring values in registers at a time (<= 168 VGPRs); rows taken half a transform apart: the fftshift
-            constexpr int CH = (P < MPX_COMP_CH) ? P : MPX_COMP_CH;
-            const RingAddr ra = ring_addr<P>(ring_byte, x, lane);
-            ring_add_plane<P, 0, CH, kDit, true>(smem, ra, xr, lane, plain_add, all_rows);
-            ring_add_plane<P, 1, CH, kDit, true>(smem, ra, xi, lane, plain_add, all_rows);
-        }
-        wave_sync();
-        if (fi == cur.fe - 1) {   // last frame of the run: stream out the rest, leave the ring cleared
-            flush_ring<R>(ring, strip, pcm0, rd.head_end, rd.out_lo, rd.out_hi, target, rd.flush_end, lane);
-            wave_sync();
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __hip_atomic_store(turn, ticket + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        MPX_MARK("loop_end");
+        // ROT: rows taken half a transform apart, the fftshift
+        pair_ordered_ola<P, true>(w, cur, smem, runs, pm_rel, strips, pcm, xr, xi, lane, plain_add, all_rows);
         cur = nxt;
     }
 }
@@ -1649,7 +1639,8 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
 // (the reference's angle(0) = 0) becomes the phasor (-1)^k, never NaN.  phase_out (null except on the last iteration)
 // receives angle(X_ref) for bins 0..M with np.angle's range, rows `ld` floats apart like the target magnitudes.
 // No feature rows are written; target magnitudes are float32 rows of pitch ld.  sig_in and sig_out must not overlap.
-// A separate kernel rather than a template arm of k_roundtrip_pair so that kernel's code stays as it is.
+// A kernel of its own, built from the same frame stages as k_roundtrip_pair, rather than a template arm of it: only the
+// middle of the frame loop (what is done to the spectrum) is this kernel's.
 // ---------------------------------------------------------------------------------------------
 template <int P, bool PHASE>   // PHASE: phase_out is written (the last launch of a run of iterations)
 __global__ __launch_bounds__(kCompPairWaves * 64) void k_griffin_lim_pair(const float* __restrict__ sig,
@@ -1665,76 +1656,27 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_griffin_lim_pair(const 
                                                                          float* __restrict__ phase_out,
                                                                          float* __restrict__ strips,
                                                                          float* __restrict__ pcm, long long ld) {
-    constexpr int M = 64 * P, N = 2 * M, R = ring_len<P>(), HP = P / 2;
+    constexpr int M = 64 * P, N = 2 * M, HP = P / 2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* tw = smem;
-    const int lane_id = threadIdx.x & 63;
-    const int wave = rfl((int)(threadIdx.x >> 6));
-    const int pair = wave >> 1, half = wave & 1;
-    constexpr bool kCompact = comp_compact<P>();
-    float* xbuf = smem + comp_tw_floats<P>() + wave * comp_xbuf_floats<P>();
-    const unsigned xbuf_byte = 4u * (unsigned)(comp_tw_floats<P>() + wave * comp_xbuf_floats<P>());
-    constexpr int kRing0 = comp_tw_floats<P>() + kCompPairWaves * comp_xbuf_floats<P>();
-    float* ring = smem + kRing0 + pair * R;
-    const unsigned ring_byte = 4u * (unsigned)(kRing0 + pair * R);
-    int* turn = reinterpret_cast<int*>(smem + kRing0 + kCompPairs * R) + pair;
-    pair_kernel_prologue<P, kCompact, MPX_COMP_DIT != 0>(tw, tw_g, smem + kRing0, kCompPairs * R, turn - pair, kCompPairs,
-                                                         kCompPairWaves * 64);
+    PairWave w;
+    if (!pair_wave_setup<P>(w, smem, tw_g, runs, slot_off, slot_runs, nslots)) return;
+    PairCursor cur = w.cur;
 
-    float wa_s0, wa_c0, ws_s0, ws_c0;   // analysis-side lane twiddle W_N^kappa and synthesis-side conj(W_N^lane)
-    sincospif(-2.0f * (float)kappa<P>(lane_id) / (float)N, &wa_s0, &wa_c0);
-    sincospif(2.0f * (float)lane_id / (float)N, &ws_s0, &ws_c0);
-    const int slot = blockIdx.x * kCompPairs + pair;
-    if (slot >= nslots) return;
-
-    typedef PairCursor Cursor;
-    const int wi_end = slot_off[slot + 1];
-    auto advance = [&](Cursor& c) { pair_cursor_advance(c, wi_end, half, runs, slot_runs); };
-    Cursor cur;
-    cur.wi = slot_off[slot];
-    cur.ticket_base = 0;
-    pair_cursor_settle(cur, wi_end, half, runs, slot_runs);
-    if (!cur.valid) return;
-
-    constexpr int kTile = kCompact ? 32 * P : 64 * P;
     FrameGeom g = frame_geom(sig, fpos[cur.fi], fleft[cur.fi], fright[cur.fi], N);
-    stage_samples_async(g, 0, kTile, xbuf_byte, lane_id);
+    pair_stage_frame<P>(w, g, w.lane_id);
 
     while (cur.valid) {
-        int lane = lane_id;
-        float wa_s = 0.0f, wa_c = 1.0f, ws_s = 0.0f, ws_c = 1.0f;
-        constexpr float lc = 1.0f, ls = 0.0f;
-        if constexpr (kCompact) {
-            asm volatile("" : "+v"(lane));
-        } else {
-            wa_s = wa_s0, wa_c = wa_c0, ws_s = ws_s0, ws_c = ws_c0;
-            asm volatile("" : "+v"(lane), "+v"(wa_s), "+v"(wa_c), "+v"(ws_s), "+v"(ws_c));
-        }
-        Cursor nxt = cur;
-        advance(nxt);
+        int lane;
+        float wa_s, wa_c, ws_s, ws_c;
+        pair_frame_lane<P>(w, lane, wa_s, wa_c, ws_s, ws_c);
+        PairCursor nxt = cur;
+        pair_cursor_advance(nxt, w.wi_end, w.half, runs, slot_runs);
         const int fi = cur.fi;
 
         float xr[P], xi[P];
         {
-            // ---- analysis: X[k] of the own bins k = lane + 64 q and of their mirrors M - k, bin M/2 on lane 0
             float no_r[HP], no_i[HP], nm_r[HP], nm_i[HP], nh_r, nh_i;
-            MPX_MARK("frame_setup");
-            staged_wait<0>();
-            noise_spectrum_paired<P, true, kCompact>(g, 0, tw, xbuf, xbuf_byte, lane, wa_c, wa_s, no_r, no_i, nm_r, nm_i, nh_r,
-                                                     nh_i, lc, ls);
-            if (P != 32) {   // FFT output lanes hold bins kappa(lane) + 64 q; the merge wants bins lane + 64 q
-                const int src = kappa<P>(lane);
-#pragma unroll
-                for (int q = 0; q < HP; ++q) {
-                    no_r[q] = __shfl(no_r[q], src);
-                    no_i[q] = __shfl(no_i[q], src);
-                    nm_r[q] = __shfl(nm_r[q], src);
-                    nm_i[q] = __shfl(nm_i[q], src);
-                }
-                nh_r = __shfl(nh_r, src);
-                nh_i = __shfl(nh_i, src);
-            }
-            mpx_pin(no_r), mpx_pin(no_i), mpx_pin(nm_r), mpx_pin(nm_i);
+            pair_analysis_spectrum<P>(w, g, lane, wa_c, wa_s, no_r, no_i, nm_r, nm_i, nh_r, nh_i);
             MPX_MARK("magnitude_merge");
             // ---- per bin pair q: Y = T X / |X| (X == 0 -> T (-1)^k), then the pair's step of the Hermitian merge as in
             // k_roundtrip_pair.  Bin k = lane + 64 q and its mirror M - k share the parity of lane (M is even).
@@ -1766,8 +1708,8 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_griffin_lim_pair(const 
                 x_r = z ? t * s : t * (u_r * r);
                 x_i = z ? 0.0f : t * (u_i * r);
             };
-            if constexpr (kCompact) {   // kappa(lane) == lane: the synthesis-side twiddle is the conjugate of the split's
-                const float4 pk = tw_half_pad<P>(tw, lane);
+            if constexpr (comp_compact<P>()) {   // kappa(lane) == lane: the synthesis-side twiddle is the conjugate of the split's
+                const float4 pk = tw_half_pad<P>(w.tw, lane);
                 ws_c = pk.x;
                 ws_s = -pk.y;
             }
@@ -1782,95 +1724,22 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_griffin_lim_pair(const 
                     x_i = lane0 ? 0.0f : x_i;
                     p_i = lane0 ? 0.0f : p_i;
                 }
-                const float er = x_r + p_r, ei = x_i - p_i, tr = x_r - p_r, ti = x_i + p_i;
-                const float cq = cos2p<P>(q), sq = sin2p<P>(q);
-                const float wr = ws_c * cq - ws_s * sq, wi = ws_c * sq + ws_s * cq;
-                const float orr = wr * tr - wi * ti, oi = wr * ti + wi * tr;
-                xr[q] = er - oi;
-                xi[q] = ei + orr;
-                zr[q] = er + oi;
-                zi[q] = orr - ei;
+                merge_pair_step<P>(q, x_r, x_i, p_r, p_i, ws_c, ws_s, xr[q], xi[q], zr[q], zi[q]);
             }
-            // bin M/2 (lane 0; M/2 = 32 P is even): Y, then Z = 2 conj(Y); then the hand-over of Z[M - k] to the lanes
-            // that own those registers
+            // bin M/2 (lane 0; M/2 = 32 P is even): Y, then Z = 2 conj(Y)
             replace(nh_r, nh_i, trow[M / 2], 1.0f);
-            const float hr = 2.0f * nh_r, hi = -2.0f * nh_i;
-            const int src_lane = (64 - lane) & 63;
-#pragma unroll
-            for (int r = HP; r < P; ++r) {
-                const float pr = lane0 ? ((r == HP) ? hr : zr[P - r]) : zr[P - 1 - r];
-                const float pi = lane0 ? ((r == HP) ? hi : zi[P - r]) : zi[P - 1 - r];
-                xr[r] = __shfl(pr, src_lane);
-                xi[r] = __shfl(pi, src_lane);
-            }
+            merge_handover<P>(zr, zi, 2.0f * nh_r, -2.0f * nh_i, xr, xi, lane);
         }
-        mpx_pin(xr), mpx_pin(xi);
-        MPX_MARK("fft_inverse");
-        constexpr bool kDit = kCompact && MPX_COMP_DIT;
-        if constexpr (kDit) {
-            constexpr int LBJ = ilog2(P);
-            float yr[P], yi[P];
-#pragma unroll
-            for (int j = 0; j < P; ++j) {
-                yr[brev(j, LBJ)] = xr[j];
-                yi[brev(j, LBJ)] = xi[j];
-            }
-            const float4 pk = tw_half_pad<P>(tw, lane);
-            wave_fft_dit_compact_front<P, +1>(yr, yi, tw, xbuf, lane, pk.z, pk.w);
-#pragma unroll
-            for (int j = 0; j < P; ++j) {
-                xr[j] = yr[j];
-                xi[j] = yi[j];
-            }
-        } else if constexpr (kCompact) {
-            const float4 pk = tw_half_pad<P>(tw, lane);
-            wave_fft_front_compact<P, +1>(xr, xi, tw, xbuf, lane, pk.z, pk.w);
-        } else {
-            wave_fft_front<P, +1>(xr, xi, tw, xbuf, lane);
-        }
-        if (nxt.valid) {   // the exchange buffer is idle from here on: start the copy of the next frame's samples
+        pair_inverse_fft_front<P>(w, xr, xi, lane);
+        if (nxt.valid) {
             g = frame_geom(sig, fpos[nxt.fi], fleft[nxt.fi], fright[nxt.fi], N);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            stage_samples_async(g, 0, kTile, xbuf_byte, lane);
+            pair_stage_next<P>(w, g, lane);
         }
-        if constexpr (kDit) wave_fft_dit_back<P, +1>(xr, xi);
-        else fft_inreg<P, +1>(xr, xi);
-
-        // ---- ordered section: wait for this frame's ticket (as k_roundtrip_pair)
-        mpx_pin(xr), mpx_pin(xi);
-        MPX_MARK("ticket");
-        const RunDesc rd = runs[cur.ci];
-        float* strip = strips + rd.strip_off;
-        float* pcm0 = pcm + rd.out_base;
-        const int ticket = cur.ticket_base + (fi - cur.fb);
-        const int x = pm_rel[fi] - cur.x0;   // strip position of the frame's first sample
-        const int target = x & ~63;
-        const int flushed = (fi == cur.fb) ? 0 : ((pm_rel[fi - 1] - cur.x0) & ~63);
-        asm volatile("" ::"s"(x), "s"(flushed), "s"(rd.head_end), "s"(rd.out_lo), "s"(rd.out_hi), "s"(rd.flush_end));
-        while (__hip_atomic_load(turn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != ticket)
-            __builtin_amdgcn_s_sleep(1);
-        asm volatile("" ::: "memory");
-        MPX_MARK("flush");
-        if (flushed < target) flush_ring<R>(ring, strip, pcm0, rd.head_end, rd.out_lo, rd.out_hi, flushed, target, lane);
-        wave_sync();
-        MPX_MARK("overlap_add");
+        pair_inverse_fft_back<P>(xr, xi);
         constexpr float kScale = 0.5f / (float)M;   // the inverse transform's scale, on the overlap-add's multiply-add
         auto plain_add = [](float o, float v, int) { return fmaf(v, kScale, o); };
         auto all_rows = [](int) { return true; };
-        {
-            constexpr int CH = (P < MPX_COMP_CH) ? P : MPX_COMP_CH;
-            const RingAddr ra = ring_addr<P>(ring_byte, x, lane);
-            ring_add_plane<P, 0, CH, kDit, true>(smem, ra, xr, lane, plain_add, all_rows);
-            ring_add_plane<P, 1, CH, kDit, true>(smem, ra, xi, lane, plain_add, all_rows);
-        }
-        wave_sync();
-        if (fi == cur.fe - 1) {   // last frame of the run: stream out the rest, leave the ring cleared
-            flush_ring<R>(ring, strip, pcm0, rd.head_end, rd.out_lo, rd.out_hi, target, rd.flush_end, lane);
-            wave_sync();
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __hip_atomic_store(turn, ticket + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        MPX_MARK("loop_end");
+        pair_ordered_ola<P, true>(w, cur, smem, runs, pm_rel, strips, pcm, xr, xi, lane, plain_add, all_rows);
         cur = nxt;
     }
 }

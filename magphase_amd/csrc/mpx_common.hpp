@@ -335,6 +335,40 @@ __device__ __forceinline__ void feat_load_paired_part(PairFeat<P>& ff, const flo
     }
 }
 
+// One step of the Hermitian merge in the paired layout: from X[k] = x of an own bin k = lane + 64 q and X[M - k] = p of its
+// mirror, Z[k] (out_*) and Z[M - k] (z_*).  E = X + conj(Xp), T = X - conj(Xp), O = conj(W_N^k) T with
+// conj(W_N^k) = e^{+2 pi i (lane/N + q/2P)}, (wl_c, wl_s) = e^{+2 pi i lane/N}.
+template <int P>
+__device__ __forceinline__ void merge_pair_step(int q, float x_r, float x_i, float p_r, float p_i, float wl_c, float wl_s,
+                                                float& out_r, float& out_i, float& z_r, float& z_i) {
+    const float er = x_r + p_r, ei = x_i - p_i, tr = x_r - p_r, ti = x_i + p_i;
+    const float cq = cos2p<P>(q), sq = sin2p<P>(q);
+    const float wr = wl_c * cq - wl_s * sq, wi = wl_c * sq + wl_s * cq;
+    const float orr = wr * tr - wi * ti, oi = wr * ti + wi * tr;
+    out_r = er - oi;
+    out_i = ei + orr;
+    z_r = er + oi;
+    z_i = orr - ei;
+}
+
+// Hand-over of the mirrors after the P/2 steps: register r >= P/2 of lane l' comes from lane (64 - l') & 63, which
+// publishes Z[M - k] of its q = P-1-r; lane 0 serves itself: register P/2 = bin M/2 (hr, hi), register r > P/2 = mirror
+// of its q = P - r.
+template <int P>
+__device__ __forceinline__ void merge_handover(const float (&zr)[P / 2], const float (&zi)[P / 2], float hr, float hi,
+                                               float (&xr)[P], float (&xi)[P], int lane) {
+    constexpr int HP = P / 2;
+    const bool lane0 = (lane == 0);
+    const int src_lane = (64 - lane) & 63;
+#pragma unroll
+    for (int r = HP; r < P; ++r) {
+        const float pr = lane0 ? ((r == HP) ? hr : zr[P - r]) : zr[P - 1 - r];
+        const float pi = lane0 ? ((r == HP) ? hi : zi[P - r]) : zi[P - 1 - r];
+        xr[r] = __shfl(pr, src_lane);
+        xi[r] = __shfl(pi, src_lane);
+    }
+}
+
 template <int P>
 __device__ __forceinline__ void feat_merge_paired(const PairFeat<P>& ff, float (&xr)[P], float (&xi)[P], int lane,
                                                   float wl_c, float wl_s) {
@@ -355,30 +389,12 @@ __device__ __forceinline__ void feat_merge_paired(const PairFeat<P>& ff, float (
             x_i = lane0 ? 0.0f : x_i;
             p_i = lane0 ? 0.0f : p_i;
         }
-        // E = X + conj(Xp), T = X - conj(Xp), O = conj(W_N^k) T   (conj(W_N^k) = e^{+2 pi i (lane/N + j/2P)})
-        const float er = x_r + p_r, ei = x_i - p_i, tr = x_r - p_r, ti = x_i + p_i;
-        const float cq = cos2p<P>(j), sq = sin2p<P>(j);
-        const float wr = wl_c * cq - wl_s * sq, wi = wl_c * sq + wl_s * cq;
-        const float orr = wr * tr - wi * ti, oi = wr * ti + wi * tr;
-        xr[j] = er - oi;
-        xi[j] = ei + orr;
-        zr[j] = er + oi;
-        zi[j] = orr - ei;
+        merge_pair_step<P>(j, x_r, x_i, p_r, p_i, wl_c, wl_s, xr[j], xi[j], zr[j], zi[j]);
     }
     // bin M/2 (lane 0): Z = 2 conj(X); M/2 is even and so is lane 0: sgn_scale is +0.5/M there
     const float sH = ff.aH * ff.aH + ff.bH * ff.bH;
     const float gH = 2.0f * ff.mH * sgn_scale * __builtin_amdgcn_rsqf(fmaxf(sH, 1.0e-37f));
-    const float hr = ff.aH * gH, hi = -ff.bH * gH;
-    // hand-over: register r >= P/2 of lane l' comes from lane (64 - l') & 63, which publishes Z[M - k] of its
-    // j = P-1-r; lane 0 serves itself: register P/2 = bin M/2, register r > P/2 = mirror of its j = P - r.
-    const int src_lane = (64 - lane) & 63;
-#pragma unroll
-    for (int r = HP; r < P; ++r) {
-        const float pr = lane0 ? ((r == HP) ? hr : zr[P - r]) : zr[P - 1 - r];
-        const float pi = lane0 ? ((r == HP) ? hi : zi[P - r]) : zi[P - 1 - r];
-        xr[r] = __shfl(pr, src_lane);
-        xi[r] = __shfl(pi, src_lane);
-    }
+    merge_handover<P>(zr, zi, ff.aH * gH, -ff.bH * gH, xr, xi, lane);
 }
 
 // feat_merge_paired's second half for spectra that are already complex (k_synth_comp_pair): xo = X[k] of the own bins
@@ -388,30 +404,11 @@ __device__ __forceinline__ void merge_paired_complex(const float (&xo_r)[P / 2],
                                                      const float (&xm_r)[P / 2], const float (&xm_i)[P / 2], float xh_r,
                                                      float xh_i, float (&xr)[P], float (&xi)[P], int lane, float wl_c,
                                                      float wl_s) {
-    constexpr int HP = P / 2;
-    const bool lane0 = (lane == 0);
-    float zr[HP], zi[HP];   // Z[M - k]
+    float zr[P / 2], zi[P / 2];   // Z[M - k]
 #pragma unroll
-    for (int j = 0; j < HP; ++j) {
-        // E = X + conj(Xp), T = X - conj(Xp), O = conj(W_N^k) T   (conj(W_N^k) = e^{+2 pi i (lane/N + j/2P)})
-        const float er = xo_r[j] + xm_r[j], ei = xo_i[j] - xm_i[j], tr = xo_r[j] - xm_r[j], ti = xo_i[j] + xm_i[j];
-        const float cq = cos2p<P>(j), sq = sin2p<P>(j);
-        const float wr = wl_c * cq - wl_s * sq, wi = wl_c * sq + wl_s * cq;
-        const float orr = wr * tr - wi * ti, oi = wr * ti + wi * tr;
-        xr[j] = er - oi;
-        xi[j] = ei + orr;
-        zr[j] = er + oi;
-        zi[j] = orr - ei;
-    }
-    const float hr = 2.0f * xh_r, hi = -2.0f * xh_i;   // bin M/2 (lane 0): Z = 2 conj(X)
-    const int src_lane = (64 - lane) & 63;
-#pragma unroll
-    for (int r = HP; r < P; ++r) {
-        const float pr = lane0 ? ((r == HP) ? hr : zr[P - r]) : zr[P - 1 - r];
-        const float pi = lane0 ? ((r == HP) ? hi : zi[P - r]) : zi[P - 1 - r];
-        xr[r] = __shfl(pr, src_lane);
-        xi[r] = __shfl(pi, src_lane);
-    }
+    for (int j = 0; j < P / 2; ++j)
+        merge_pair_step<P>(j, xo_r[j], xo_i[j], xm_r[j], xm_i[j], wl_c, wl_s, xr[j], xi[j], zr[j], zi[j]);
+    merge_handover<P>(zr, zi, 2.0f * xh_r, -2.0f * xh_i, xr, xi, lane);   // bin M/2 (lane 0): Z = 2 conj(X)
 }
 
 // Ring of R strip elements, stored as two halves: even strip positions b in ringE[b/2 mod R/2], odd ones in
@@ -442,7 +439,8 @@ struct RunDesc {
 static_assert(sizeof(RunDesc) == 56, "RunDesc must match mpx_ola_run");
 
 // ---------------------------------------------------------------------------------------------
-// Shared front of the pair kernels (k_synth_comp_pair, k_roundtrip_pair): LDS tables and the cursor over a wave's frames.
+// Shared front of the pair kernels (k_synth_comp_pair, k_roundtrip_pair, k_griffin_lim_pair; their other shared stages,
+// which depend on the kernels' LDS layout, are in magphase_comp.hip): LDS tables and the cursor over a wave's frames.
 // ---------------------------------------------------------------------------------------------
 // First-pass twiddle table into LDS -- COMPACT: the half table (wave_fft.hpp: the even registers' twiddles, or with DIT the
 // first P/2 in natural register order) with this lane's constants in the pad of its row (tw_half_pad: W_N^{-lane} and
@@ -657,9 +655,6 @@ __device__ __forceinline__ void ring_add_plane(float* smem_base, const RingAddr&
         // the kernel is bound by VALU issue (tools/archive/endtime_probe.py: 2.8 cycles per instruction and SIMD at 3 waves).
         constexpr int RH = ring_len<P>() / 2;
         const int cu = PL ? ra.cu1 : ra.cu0;
-#ifndef MPX_RING_ADDR_MODE
-#define MPX_RING_ADDR_MODE 2
-#endif
 #if MPX_RING_ADDR_MODE == 1   // lane mask per row on the scalar unit (8 SALU) + one v_cndmask
         auto addr = [&](int q) -> unsigned {
             const int thr = RH - cu - 64 * q;
