@@ -430,6 +430,22 @@ int mpx_synthesis_compressed_ola_spectra(void* stream, int fft_len, const void* 
                                  const int32_t* slot_off, const int32_t* slot_runs, int32_t n_slots,
                                  float* strips, float* pcm_out, int64_t ld, int32_t n_per_bins,
                                  const float* spectra /* as stored by mpx_noise_stats_spectra */);
+/*
+ * The same launch for synthesis_from_compressed_type2 (magphase.py:1556-1597): the DC and Nyquist bins keep their signed
+ * real part with a zero imaginary part (la.add_hermitian_half(.., 'complex'), :1567) instead of the modulus.  What else
+ * differs from type 1 arrives as data: inv_gain = 1 / rms of the utterance's noise spectra for every frame
+ * (mpx_noise_power + mpx_noise_rms), per_v / ap_v / ap_u = hostmath.type2_synthesis_bin_curves (plain crossfade, the
+ * hf_slope line).  Arguments, tables and dispatch as mpx_synthesis_compressed_ola; no stored-spectra form.
+ */
+int mpx_synthesis_compressed_type2_ola(void* stream, int fft_len, const void* tables, const float* mag, const float* real,
+                                 const float* imag, const float* noise, const int64_t* noise_pos,
+                                 const int32_t* noise_left, const int32_t* noise_right, const int32_t* noise_wtype,
+                                 const int32_t* voiced, const float* inv_gain, const int32_t* row0,
+                                 const int32_t* row1, const float* row_t, const int32_t* win_left,
+                                 const int32_t* win_right, const int32_t* pm_rel, const float* per_v,
+                                 const float* ap_v, const float* ap_u, const mpx_ola_run* runs, int32_t n_runs,
+                                 const int32_t* slot_off, const int32_t* slot_runs, int32_t n_slots,
+                                 float* strips, float* pcm_out, int64_t ld, int32_t n_per_bins);
 
 /*
  * HOST function (no device work, no stream): the serial constant -> variable frame-rate scan of
@@ -548,6 +564,21 @@ int mpx_frame_gain(void* stream, int fft_len, const float* sig, const int64_t* f
  */
 int mpx_noise_gains(void* stream, const float* sums, const int32_t* voiced, const int32_t* utt_frame_off,
                     int32_t n_utts, int32_t bins_per_frame, float* inv_gain, double* gains);
+
+/*
+ * Noise statistic of the type-2 synthesis (synthesis_from_compressed_type2, magphase.py:1530-1541), without a transform.
+ * mpx_noise_power: one wavefront per frame; noise / frame_pos / frame_left / frame_right / frame_wtype as mpx_noise_stats
+ * takes them; power[f] (float64) = sum over the fft_len/2 + 1 bins of |Ns[k]|^2 of the windowed noise frame
+ * = (fft_len sum x^2 + (sum x)^2 + (sum (-1)^n x[n])^2) / 2, the three sums in float64 over the frame's samples.
+ * mpx_noise_rms: per utterance u, rms[u] = sqrt(sum of power over its frames / (frames * (fft_len/2 + 1))) (float64,
+ * optional, may be null; NaN for an utterance without frames), inv_gain[f] = 1 / rms[u] (float32, input of
+ * mpx_synthesis_compressed_type2_ola).  The frames are added in a fixed order: an utterance's rms does not depend on
+ * the batch it is in.
+ */
+int mpx_noise_power(void* stream, int fft_len, const float* noise, const int64_t* frame_pos, const int32_t* frame_left,
+                    const int32_t* frame_right, const int32_t* frame_wtype, int64_t n_frames, double* power);
+int mpx_noise_rms(void* stream, int fft_len, const double* power, const int32_t* utt_frame_off, int32_t n_utts,
+                  float* inv_gain, double* rms);
 
 /*
  * MagPhase post-filter (magphase.py:2300-2378, Q20) on [n_frames x dim] log-mel magnitudes.  half_len: int32

@@ -55,6 +55,7 @@ SYMBOLS = (
     "mpx_synth_comp_slots",
     "mpx_synth_comp_slot_weights",
     "mpx_synthesis_compressed_ola",
+    "mpx_synthesis_compressed_type2_ola",
     "mpx_synthesis_compressed_ola_spectra",
     "mpx_host_const_to_var_scan",
     "mpx_host_const_to_var_scan_cap",
@@ -79,6 +80,8 @@ SYMBOLS = (
     "mpx_true_envelope",
     "mpx_frame_gain",
     "mpx_noise_gains",
+    "mpx_noise_power",
+    "mpx_noise_rms",
     "mpx_post_filter",
     "mpx_epoch_f0_track",
     "mpx_epoch_zff",
@@ -214,6 +217,8 @@ def _load_locked():
     lib.mpx_synth_comp_slots.argtypes = []
     lib.mpx_synthesis_compressed_ola.restype = ctypes.c_int
     lib.mpx_synthesis_compressed_ola.argtypes = [vp, ctypes.c_int, vp] + [vp] * 19 + [vp, i32, vp, vp, i32, vp, vp, i64, i32]
+    lib.mpx_synthesis_compressed_type2_ola.restype = ctypes.c_int
+    lib.mpx_synthesis_compressed_type2_ola.argtypes = lib.mpx_synthesis_compressed_ola.argtypes
     lib.mpx_synthesis_compressed_ola_spectra.restype = ctypes.c_int
     lib.mpx_synthesis_compressed_ola_spectra.argtypes = ([vp, ctypes.c_int, vp] + [vp] * 19 +
                                                          [vp, i32, vp, vp, i32, vp, vp, i64, i32, vp])
@@ -265,6 +270,10 @@ def _load_locked():
     lib.mpx_frame_gain.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, vp, i64, vp, i32]
     lib.mpx_noise_gains.restype = ctypes.c_int
     lib.mpx_noise_gains.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
+    lib.mpx_noise_power.restype = ctypes.c_int
+    lib.mpx_noise_power.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, vp, i64, vp]
+    lib.mpx_noise_rms.restype = ctypes.c_int
+    lib.mpx_noise_rms.argtypes = [vp, ctypes.c_int, vp, vp, i32, vp, vp]
     lib.mpx_post_filter.restype = ctypes.c_int
     lib.mpx_post_filter.argtypes = [vp, vp, i64, i32, vp, i32, i32, vp, vp]
     lib.mpx_epoch_f0_track.restype = ctypes.c_int

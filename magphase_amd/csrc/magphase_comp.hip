@@ -1096,7 +1096,10 @@ __device__ __forceinline__ void pair_ordered_ola(const PairWave& w, const PairCu
 // and the freed registers allow batches of (8, 8) = 56 / 32 loads: two exposed load latencies per frame instead of four.
 // NPQ < 0: anything goes (run-time tests only).
 // SPEC: the noise spectra come from HBM (tb.nspec, stored by k_noise_stats) instead of a second transform of the frame.
-template <int P, bool LERP, int NPQ = -1, bool SPEC = false>
+// T2: the assembly of synthesis_from_compressed_type2 (magphase.py:1556-1567) -- the DC and Nyquist bins keep their signed
+// real part with a zero imaginary part (la.add_hermitian_half(.., 'complex')) instead of the modulus.  Everything else
+// that differs in type 2 (one gain per utterance, other curves) arrives as data: tb.inv_gain, per_v, ap_v, ap_u.
+template <int P, bool LERP, int NPQ = -1, bool SPEC = false, bool T2 = false>
 __global__ __launch_bounds__(kCompPairWaves * 64) void k_synth_comp_pair(const float* __restrict__ mag,
                                                                         const float* __restrict__ real,
                                                                         const float* __restrict__ imag,
@@ -1113,6 +1116,7 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_synth_comp_pair(const f
                                                                         float* __restrict__ strips,
                                                                         float* __restrict__ pcm, long long ld, int n_per) {
     static_assert(!SPEC || (P == 32 && !LERP), "stored noise spectra: N = 4096, one row per frame");
+    static_assert(!(SPEC && T2), "type 2 has no stored-spectra form");
     constexpr int M = 64 * P, N = 2 * M;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr bool kCompact = comp_compact<P>();
@@ -1202,8 +1206,8 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_synth_comp_pair(const f
                         vr = n_r * apf;
                         vi = n_i * apf;
                     }
-                    if (real_only) {   // DC and Nyquist: X = |X| (magphase.py:958-961)
-                        vr = __builtin_sqrtf(vr * vr + vi * vi);
+                    if (real_only) {   // DC and Nyquist: X = |X| (magphase.py:958-961); type 2: Re X (:1567)
+                        if constexpr (!T2) vr = __builtin_sqrtf(vr * vr + vi * vi);
                         vi = 0.0f;
                     }
                     o_r = vr * sgn_scale;
@@ -1432,15 +1436,15 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_synth_comp_pair(const f
                     const float u = (s > 0.0f) ? m * cpv[jj] * pvs * __builtin_amdgcn_rsqf(s) : 0.0f;
                     const float apf = m * cap[jj] * ig;
                     float vr = fmaf(xr[j], apf, a * u), vi = fmaf(xi[j], apf, b * u);
-                    if (j == 0 && lane == 0) {   // DC: X = |X| (magphase.py:958-961)
-                        vr = __builtin_sqrtf(vr * vr + vi * vi);
+                    if (j == 0 && lane == 0) {   // DC: X = |X| (magphase.py:958-961); type 2: Re X (:1567)
+                        if constexpr (!T2) vr = __builtin_sqrtf(vr * vr + vi * vi);
                         vi = 0.0f;
                     }
                     xr[j] = vr * sgn_scale;
                     xi[j] = vi * sgn_scale;
                 }
             }
-            if (lane == 0) {   // Nyquist bin: the noise spectrum is real there; X = |X|
+            if (lane == 0) {   // Nyquist bin: the noise spectrum is real there; X = |X| (type 2: Re X)
                 const float m = LERP ? fmaf(m1p[M] - m0p[M], rt, m0p[M]) : m0p[M];
                 const float a = LERP ? fmaf(a1p[M] - a0p[M], rt, a0p[M]) : a0p[M];
                 const float b = LERP ? fmaf(b1p[M] - b0p[M], rt, b0p[M]) : b0p[M];
@@ -1448,7 +1452,7 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_synth_comp_pair(const f
                 const float u = (s > 0.0f) ? m * per_v[M] * pvs * __builtin_amdgcn_rsqf(s) : 0.0f;
                 const float apf = m * apc[M] * ig;
                 const float vr = fmaf(nM, apf, a * u), vi = b * u;
-                xm = __builtin_sqrtf(vr * vr + vi * vi) * (0.5f / (float)M);   // (-1)^M = +1
+                xm = (T2 ? vr : __builtin_sqrtf(vr * vr + vi * vi)) * (0.5f / (float)M);   // (-1)^M = +1
             }
 
             if constexpr (kCompact) {
@@ -2476,7 +2480,10 @@ int mpx_synth_comp_slot_weights(float* weights_host, int32_t n_slots) {
     return MPX_OK;
 }
 
-static int synthesis_compressed_ola_impl(void* stream, int fft_len, const void* tables, const float* mag, const float* real,
+// T2: the type-2 arm of k_synth_comp_pair (mpx_synthesis_compressed_type2_ola); who: the entry's name for the messages
+extern "C++" {
+template <bool T2>
+static int synthesis_compressed_ola_impl(const char* who, void* stream, int fft_len, const void* tables, const float* mag, const float* real,
                                  const float* imag, const float* noise, const int64_t* noise_pos,
                                  const int32_t* noise_left, const int32_t* noise_right, const int32_t* noise_wtype,
                                  const int32_t* voiced, const float* inv_gain, const int32_t* row0,
@@ -2487,22 +2494,22 @@ static int synthesis_compressed_ola_impl(void* stream, int fft_len, const void* 
                                  float* strips, float* pcm_out, int64_t ld, int32_t n_per_bins,
                                  const float* spectra) {
     const int P = p_of(fft_len);
-    if (!P) return fail(MPX_ERR_ARG, "mpx_synthesis_compressed_ola: fft_len must be 1024, 2048 or 4096%s");
+    if (!P) return fail(MPX_ERR_ARG, "%s: fft_len must be 1024, 2048 or 4096", who);
     const int n_per = (n_per_bins <= 0 || n_per_bins > fft_len / 2 + 1) ? fft_len / 2 + 1 : (int)n_per_bins;
-    if (n_runs < 0 || n_slots < 0) return fail(MPX_ERR_ARG, "mpx_synthesis_compressed_ola: negative count%s");
+    if (n_runs < 0 || n_slots < 0) return fail(MPX_ERR_ARG, "%s: negative count", who);
     if (n_runs == 0 || n_slots == 0) return MPX_OK;
     if (!tables || !mag || !real || !imag || !noise || !noise_pos || !noise_left || !noise_right || !noise_wtype ||
         !voiced || !inv_gain || !win_left || !win_right || !pm_rel || !per_v || !ap_v ||
         !ap_u || !runs || !slot_off || !slot_runs || !strips || !pcm_out)
-        return fail(MPX_ERR_ARG, "mpx_synthesis_compressed_ola: null pointer%s");
+        return fail(MPX_ERR_ARG, "%s: null pointer", who);
     const bool lerp = row0 || row1 || row_t;   // all three null: one spectrum row per frame, row index = frame index
     if (lerp && (!row0 || !row1 || !row_t))
-        return fail(MPX_ERR_ARG, "mpx_synthesis_compressed_ola: row0 / row1 / row_t must be given together%s");
+        return fail(MPX_ERR_ARG, "%s: row0 / row1 / row_t must be given together", who);
     CompFrameTabs tb{(const long long*)noise_pos, noise_left, noise_right, noise_wtype, voiced, inv_gain,
                      row0, row1, row_t, win_left, win_right, pm_rel, spectra};
     hipStream_t s = (hipStream_t)stream;
     const dim3 pgrid((n_slots + kCompPairs - 1) / kCompPairs), pblock(kCompPairWaves * 64);
-    if (spectra) {   // stored noise spectra (mpx_noise_stats_spectra): N = 4096, one row per frame
+    if (spectra) {   // stored noise spectra (mpx_noise_stats_spectra): N = 4096, one row per frame; never given for type 2
         if (P != 32 || lerp)
             return fail(MPX_ERR_ARG, "mpx_synthesis_compressed_ola_spectra: fft_len 4096 and one row per frame only%s");
         if (n_per <= 512) {
@@ -2521,8 +2528,9 @@ static int synthesis_compressed_ola_impl(void* stream, int fft_len, const void* 
     }
 #define MPX_LAUNCH_COMP(PP, LL)                                                                                        \
     do {                                                                                                             \
-        if (int rc = set_lds(k_synth_comp_pair<PP, LL>, lds_bytes_comp_pair<PP>())) return rc;                       \
-        hipLaunchKernelGGL((k_synth_comp_pair<PP, LL>), pgrid, pblock, lds_bytes_comp_pair<PP>(), s, mag, real, imag, \
+        if (int rc = set_lds(k_synth_comp_pair<PP, LL, -1, false, T2>, lds_bytes_comp_pair<PP>())) return rc;        \
+        hipLaunchKernelGGL((k_synth_comp_pair<PP, LL, -1, false, T2>), pgrid, pblock, lds_bytes_comp_pair<PP>(), s,  \
+                           mag, real, imag,                                                                          \
                            noise, tb, per_v, ap_v, ap_u, (const RunDesc*)runs, slot_off, slot_runs, (int)n_slots,    \
                            (const float*)tables, strips, pcm_out, (long long)ld, n_per);                 \
     } while (0)
@@ -2532,8 +2540,8 @@ static int synthesis_compressed_ola_impl(void* stream, int fft_len, const void* 
         else MPX_LAUNCH_COMP(8, true);
     } else {
         if (P == 32 && n_per <= 512) {   // the crossfade ends at or below bin 512 (48 / 44.1 kHz): the NPQ == 8 schedule
-            if (int rc = set_lds(k_synth_comp_pair<32, false, 8>, lds_bytes_comp_pair<32>())) return rc;
-            hipLaunchKernelGGL((k_synth_comp_pair<32, false, 8>), pgrid, pblock, lds_bytes_comp_pair<32>(), s, mag, real, imag,
+            if (int rc = set_lds(k_synth_comp_pair<32, false, 8, false, T2>, lds_bytes_comp_pair<32>())) return rc;
+            hipLaunchKernelGGL((k_synth_comp_pair<32, false, 8, false, T2>), pgrid, pblock, lds_bytes_comp_pair<32>(), s, mag, real, imag,
                                noise, tb, per_v, ap_v, ap_u, (const RunDesc*)runs, slot_off, slot_runs, (int)n_slots,
                                (const float*)tables, strips, pcm_out, (long long)ld, n_per);
         } else if (P == 32) MPX_LAUNCH_COMP(32, false);
@@ -2544,6 +2552,7 @@ static int synthesis_compressed_ola_impl(void* stream, int fft_len, const void* 
     MPX_HIP_CHECK(hipGetLastError());
     return MPX_OK;
 }
+}  // extern "C++"
 
 int mpx_synthesis_compressed_ola(void* stream, int fft_len, const void* tables, const float* mag, const float* real,
                                  const float* imag, const float* noise, const int64_t* noise_pos,
@@ -2554,9 +2563,25 @@ int mpx_synthesis_compressed_ola(void* stream, int fft_len, const void* tables, 
                                  const float* ap_v, const float* ap_u, const mpx_ola_run* runs, int32_t n_runs,
                                  const int32_t* slot_off, const int32_t* slot_runs, int32_t n_slots,
                                  float* strips, float* pcm_out, int64_t ld, int32_t n_per_bins) {
-    return synthesis_compressed_ola_impl(stream, fft_len, tables, mag, real, imag, noise, noise_pos, noise_left, noise_right,
-                                         noise_wtype, voiced, inv_gain, row0, row1, row_t, win_left, win_right, pm_rel, per_v,
-                                         ap_v, ap_u, runs, n_runs, slot_off, slot_runs, n_slots, strips, pcm_out, ld, n_per_bins, nullptr);
+    return synthesis_compressed_ola_impl<false>("mpx_synthesis_compressed_ola", stream, fft_len, tables, mag, real, imag, noise,
+                                                noise_pos, noise_left, noise_right, noise_wtype, voiced, inv_gain, row0, row1,
+                                                row_t, win_left, win_right, pm_rel, per_v, ap_v, ap_u, runs, n_runs, slot_off,
+                                                slot_runs, n_slots, strips, pcm_out, ld, n_per_bins, nullptr);
+}
+
+int mpx_synthesis_compressed_type2_ola(void* stream, int fft_len, const void* tables, const float* mag, const float* real,
+                                       const float* imag, const float* noise, const int64_t* noise_pos,
+                                       const int32_t* noise_left, const int32_t* noise_right, const int32_t* noise_wtype,
+                                       const int32_t* voiced, const float* inv_gain, const int32_t* row0,
+                                       const int32_t* row1, const float* row_t, const int32_t* win_left,
+                                       const int32_t* win_right, const int32_t* pm_rel, const float* per_v,
+                                       const float* ap_v, const float* ap_u, const mpx_ola_run* runs, int32_t n_runs,
+                                       const int32_t* slot_off, const int32_t* slot_runs, int32_t n_slots,
+                                       float* strips, float* pcm_out, int64_t ld, int32_t n_per_bins) {
+    return synthesis_compressed_ola_impl<true>("mpx_synthesis_compressed_type2_ola", stream, fft_len, tables, mag, real, imag,
+                                               noise, noise_pos, noise_left, noise_right, noise_wtype, voiced, inv_gain, row0,
+                                               row1, row_t, win_left, win_right, pm_rel, per_v, ap_v, ap_u, runs, n_runs,
+                                               slot_off, slot_runs, n_slots, strips, pcm_out, ld, n_per_bins, nullptr);
 }
 
 int mpx_synthesis_compressed_ola_spectra(void* stream, int fft_len, const void* tables, const float* mag, const float* real,
@@ -2570,9 +2595,10 @@ int mpx_synthesis_compressed_ola_spectra(void* stream, int fft_len, const void* 
                                  float* strips, float* pcm_out, int64_t ld, int32_t n_per_bins, const float* spectra) {
     if (!spectra && n_runs > 0 && n_slots > 0)
         return fail(MPX_ERR_ARG, "mpx_synthesis_compressed_ola_spectra: null pointer%s");
-    return synthesis_compressed_ola_impl(stream, fft_len, tables, mag, real, imag, noise, noise_pos, noise_left, noise_right,
-                                         noise_wtype, voiced, inv_gain, row0, row1, row_t, win_left, win_right, pm_rel, per_v,
-                                         ap_v, ap_u, runs, n_runs, slot_off, slot_runs, n_slots, strips, pcm_out, ld, n_per_bins, spectra);
+    return synthesis_compressed_ola_impl<false>("mpx_synthesis_compressed_ola_spectra", stream, fft_len, tables, mag, real,
+                                                imag, noise, noise_pos, noise_left, noise_right, noise_wtype, voiced, inv_gain,
+                                                row0, row1, row_t, win_left, win_right, pm_rel, per_v, ap_v, ap_u, runs, n_runs,
+                                                slot_off, slot_runs, n_slots, strips, pcm_out, ld, n_per_bins, spectra);
 }
 
 // Slot weights of k_roundtrip_pair (see mpx_synth_comp_slot_weights: pairs of the oldest / middle / youngest waves of the

@@ -1172,16 +1172,17 @@ class Engine:
                        "mpx_post_filter_merlin")
         return out[:F]
 
-    def output_hpf(self, pcm, out_off_host, fs):
+    def output_hpf(self, pcm, out_off_host, fs, design="butter40"):
         """
         magphase.py:981-995 on the device: float32 pcm [total] (utterances concatenated at out_off_host) ->
         float64 tensor, every utterance filtered from a zero state (mpx_output_hpf: cascade of biquads, blocked scan).
+        design: hostmath.hpf_tables' -- 'butter40' (type 1) or 'ellip60' (synthesis_from_compressed_type2, :1599-1604).
         """
         torch = _torch()
         block = int(self.lib.mpx_hpf_block())
-        key = ("hpf", int(fs))
+        key = ("hpf", int(fs)) if design == "butter40" else ("hpf", int(fs), design)
         if key not in self._tables:
-            sos, pm, g = hm.hpf_tables(fs, block)
+            sos, pm, g = hm.hpf_tables(fs, block, design)
             self._tables[key] = (sos, self.to_device(pm, np.float64), self.to_device(g, np.float64))
         sos, d_pm, d_g = self._tables[key]
         out_off_host = np.asarray(out_off_host, dtype=np.int64)
@@ -2086,6 +2087,12 @@ class CompressedSynthesisPlan:
     noise windows) and :969-976 (anti-ringing lengths, ola) -- all index math in float64/int on the host.
     """
 
+    # what Type2SynthesisPlan changes: the planner for a grid the native one does not know, the phase unwarp matrix and
+    # the per-bin curves, the noise statistic and the entry of the pair kernel
+    _native_planner = True      # Engine.prepare_synthesis / hostplan.plan_synthesis serve this plan's frame tables
+    _n_per_key = "n_per"
+    _ola_entry = "mpx_synthesis_compressed_ola"
+
     def __init__(self, engine, utts, fs, fft_len=None, b_voi_ap_win=True, b_const_rate=False, alpha_phase=None,
                  noise=None, frames_per_run=None, per_phase_type="magphase", post_filter=False, b_fbank_mel=False,
                  noise_mode="reference", noise_seeds=None, defer_rng=False, noise_spectra=None, prepared=None):
@@ -2132,7 +2139,7 @@ class CompressedSynthesisPlan:
         self.unwarp_rows = self.b_const_rate or os.environ.get("MAGPHASE_UNWARP_ROWS_VAR", "1") != "0"
         # the native whole-launch planner (Engine.prepare_synthesis; `prepared`: built ahead, e.g. on the planner thread) takes
         # the plain case: ndarray coefficient matrices, the default run planner
-        if (prepared is None and frames_per_run is None and hasattr(e, "prepare_synthesis")
+        if (prepared is None and frames_per_run is None and self._native_planner and hasattr(e, "prepare_synthesis")
                 and not os.environ.get("MAGPHASE_OLA_FRAMES_PER_RUN") and os.environ.get("MAGPHASE_NATIVE_PREPARE", "1") != "0"):
             prepared = e.prepare_synthesis(utts, fs, fft_len=fft_len, b_voi_ap_win=b_voi_ap_win, b_const_rate=b_const_rate,
                                            wait=False)
@@ -2157,10 +2164,7 @@ class CompressedSynthesisPlan:
         else:
             self.u_mag = e.constant(("u_mag", self.mag_dim, H, float(alpha)),
                                     lambda: hm.unwarp_matrix(self.mag_dim, H, alpha))
-        self.u_phase = e.constant(("u_phase", self.phase_dim, N, int(fs), float(self.alpha_phase)),
-                                  lambda: hm.phase_unwarp_matrix(self.phase_dim, N, fs, self.alpha_phase))
-        self.per_v, self.ap_v, self.ap_u = (
-            e.constant(("bin_curve", k, int(fs), N), lambda k=k: hm.synthesis_bin_curves(fs, N)[k]) for k in range(3))
+        self._phase_and_curve_constants()
         self._gains_dev = None
         # "noise spectra once" (opt-in): see run()
         self.noise_spectra = ((os.environ.get("MAGPHASE_NOISE_SPECTRA", "recompute") == "store")
@@ -2174,6 +2178,29 @@ class CompressedSynthesisPlan:
                                                    self.noise.data_ptr()), "mpx_noise_uniform")
         elif mt_device:
             self.noise = e.numpy_global_uniform(int(sum(self.ns_len)), defer=bool(defer_rng))
+
+    def _phase_and_curve_constants(self):
+        e, fs, N = self.engine, self.fs, self.fft_len
+        self.u_phase = e.constant(("u_phase", self.phase_dim, N, int(fs), float(self.alpha_phase)),
+                                  lambda: hm.phase_unwarp_matrix(self.phase_dim, N, fs, self.alpha_phase))
+        self.per_v, self.ap_v, self.ap_u = (
+            e.constant(("bin_curve", k, int(fs), N), lambda k=k: hm.synthesis_bin_curves(fs, N)[k]) for k in range(3))
+
+    def _bin_curves_host(self):
+        return hm.synthesis_bin_curves(self.fs, self.fft_len)
+
+    def _n_per(self):
+        """Bins from n_per on have no periodic component (the curve is exactly zero there)."""
+        return self.engine.host_constant((self._n_per_key, int(self.fs), self.fft_len), lambda: _first_all_zero_from(
+            np.asarray(self._bin_curves_host()[0], dtype=np.float32)))
+
+    def _plan_tables(self, lf0s, b_voi_ap_win):
+        """The batch's frame tables (hostplan.plan_synthesis' layout)."""
+        fs, N, b_const_rate = self.fs, self.fft_len, self.b_const_rate
+        try:    # index arithmetic of the whole batch in one native call (hostplan / csrc/magphase_plan.cpp) ...
+            return hostplan.plan_synthesis([np.exp(l) for l in lf0s], fs, N, b_const_rate, b_voi_ap_win)   # :846
+        except hostplan.PlanFallback:   # ... or utterance by utterance in numpy: the same arithmetic, spelled out
+            return plan_synthesis_numpy(lf0s, fs, N, b_const_rate, b_voi_ap_win)
 
     def _mt_device(self, noise, noise_mode, mt_total):
         """Reference noise (np.random.uniform from numpy's GLOBAL generator, magphase.py:883) for more than a few utterances
@@ -2211,8 +2238,7 @@ class CompressedSynthesisPlan:
         self.n_runs, self.n_slots = p.n_runs, p.n_slots
         self.runs_host = p.runs_host
         self.strip_floats = self.n_runs * (self.fft_len + 64)
-        self.n_per = e.host_constant(("n_per", int(self.fs), self.fft_len), lambda: _first_all_zero_from(
-            np.asarray(hm.synthesis_bin_curves(self.fs, self.fft_len)[0], dtype=np.float32)))
+        self.n_per = self._n_per()
         mt_device = self._mt_device(noise, noise_mode, int(p.ns_len.sum()))
         slot, p.slot = p.slot, None
         sd, dd, ev = e._slot_upload(slot, p.stage_bytes, p.desc_bytes)
@@ -2282,10 +2308,7 @@ class CompressedSynthesisPlan:
             a_mag.append(mml), a_real.append(rm), a_imag.append(im), lf0s.append(lf0)
             row_base += n_rows
 
-        try:    # index arithmetic of the whole batch in one native call (hostplan / csrc/magphase_plan.cpp) ...
-            r = hostplan.plan_synthesis([np.exp(l) for l in lf0s], fs, N, b_const_rate, b_voi_ap_win)   # :846
-        except hostplan.PlanFallback:   # ... or utterance by utterance in numpy: the same arithmetic, spelled out
-            r = plan_synthesis_numpy(lf0s, fs, N, b_const_rate, b_voi_ap_win)
+        r = self._plan_tables(lf0s, b_voi_ap_win)
         fo = r["frame_off"]
         mt_total = int(np.sum(r["ns_len"]))
         mt_device = self._mt_device(noise, noise_mode, mt_total)
@@ -2350,8 +2373,7 @@ class CompressedSynthesisPlan:
         _up.append(("out_off", self.out_off_host, np.int64))
         # bins from n_per on have no periodic component (the crossfade mask is exactly zero there): their phase rows are
         # neither unwarped nor read
-        self.n_per = e.host_constant(("n_per", int(fs), N), lambda: _first_all_zero_from(
-            np.asarray(hm.synthesis_bin_curves(fs, N)[0], dtype=np.float32)))
+        self.n_per = self._n_per()
         # OLA runs
         n_slots = e.synth_comp_slots() if hasattr(e, "synth_comp_slots") else 1024
         _plan_ola_runs(self, pm_rel, starts, self.out_len, self.out_off_host, N, n_slots, frames_per_run, _up,
@@ -2440,6 +2462,34 @@ class CompressedSynthesisPlan:
                 b["spec_v"] = tuple(e.empty((F, ld))[:, :H] for _ in range(3))
         return b
 
+    def _launch_noise_statistic(self, st, tab, buf, mark):
+        """The noise statistic of the utterances and buf["inv_gain"] from it; returns the stored noise spectra, or None."""
+        e, lib, N = self.engine, self.engine.lib, self.fft_len
+        H = N // 2 + 1
+        sums, inv_gain = buf["sums"], buf["inv_gain"]
+        nspec = None
+        if N == 4096 and self.total_frames > 0 and self.noise_spectra:
+            nspec = buf.get("nspec")
+            if nspec is None:
+                nspec = buf["nspec"] = e.empty((int(lib.mpx_noise_spectra_floats(N, self.total_frames)),))
+        if nspec is not None:
+            _lib.check(lib.mpx_noise_stats_spectra(st, N, tab.data_ptr(), self.noise.data_ptr(), self.npos.data_ptr(),
+                                                   self.nleft.data_ptr(), self.nright.data_ptr(),
+                                                   self.wtype.data_ptr(), self.total_frames, sums.data_ptr(),
+                                                   nspec.data_ptr()), "mpx_noise_stats_spectra")
+        else:
+            _lib.check(lib.mpx_noise_stats(st, N, tab.data_ptr(), self.noise.data_ptr(), self.npos.data_ptr(),
+                                           self.nleft.data_ptr(), self.nright.data_ptr(), self.wtype.data_ptr(),
+                                           self.total_frames, sums.data_ptr()), "mpx_noise_stats")
+        mark("k_noise_stats")
+        # two gains per utterance (Q10): float64 reduction on the device, no host round trip
+        self._gains_dev = buf["gains"]
+        _lib.check(lib.mpx_noise_gains(st, sums.data_ptr(), self.voiced.data_ptr(), self.utt_frame_off.data_ptr(),
+                                       self.n_utts, H - 2, inv_gain.data_ptr(), self._gains_dev.data_ptr()),
+                   "mpx_noise_gains")
+        mark("k_noise_gains")
+        return nspec
+
     def run(self, out=None, keep=False, mark=None):
         """mark: optional callable(name), called after every kernel launch has been enqueued (bench.py: HIP events)."""
         e, lib, N = self.engine, self.engine.lib, self.fft_len
@@ -2485,27 +2535,7 @@ class CompressedSynthesisPlan:
             # "noise spectra once" (opt-in, MAGPHASE_NOISE_SPECTRA=store; N = 4096): the statistics launch
             # stores every frame's noise spectrum and the synthesis launch loads it instead of a second transform --
             # 17.4 KB per frame each way for the arithmetic of one forward FFT (measured: docs/LAB_NOTES.md, round 5)
-            nspec = None
-            if N == 4096 and self.total_frames > 0 and self.noise_spectra:
-                nspec = buf.get("nspec")
-                if nspec is None:
-                    nspec = buf["nspec"] = e.empty((int(lib.mpx_noise_spectra_floats(N, self.total_frames)),))
-            if nspec is not None:
-                _lib.check(lib.mpx_noise_stats_spectra(st, N, tab.data_ptr(), self.noise.data_ptr(), self.npos.data_ptr(),
-                                                       self.nleft.data_ptr(), self.nright.data_ptr(),
-                                                       self.wtype.data_ptr(), self.total_frames, sums.data_ptr(),
-                                                       nspec.data_ptr()), "mpx_noise_stats_spectra")
-            else:
-                _lib.check(lib.mpx_noise_stats(st, N, tab.data_ptr(), self.noise.data_ptr(), self.npos.data_ptr(),
-                                               self.nleft.data_ptr(), self.nright.data_ptr(), self.wtype.data_ptr(),
-                                               self.total_frames, sums.data_ptr()), "mpx_noise_stats")
-            mark("k_noise_stats")
-            # two gains per utterance (Q10): float64 reduction on the device, no host round trip
-            self._gains_dev = buf["gains"]
-            _lib.check(lib.mpx_noise_gains(st, sums.data_ptr(), self.voiced.data_ptr(), self.utt_frame_off.data_ptr(),
-                                           self.n_utts, H - 2, inv_gain.data_ptr(), self._gains_dev.data_ptr()),
-                       "mpx_noise_gains")
-            mark("k_noise_gains")
+            nspec = self._launch_noise_statistic(st, tab, buf, mark)
             if self.per_phase_type != "magphase":
                 # periodic component's phase is not the transmitted one (magphase.py:933-938):
                 #   'min_phase': complex-cepstrum minimum phase of the magnitude, per frame
@@ -2534,7 +2564,7 @@ class CompressedSynthesisPlan:
                 _lib.check(lib.mpx_synthesis_compressed_ola_spectra(*ola_args, nspec.data_ptr()),
                            "mpx_synthesis_compressed_ola_spectra")
             else:
-                _lib.check(lib.mpx_synthesis_compressed_ola(*ola_args), "mpx_synthesis_compressed_ola")
+                _lib.check(getattr(lib, self._ola_entry)(*ola_args), self._ola_entry)
             mark("k_synth_comp_pair")
         e.ola_fixup(N, self, strips, pcm)
         mark("k_ola_fixup")
@@ -2549,12 +2579,15 @@ def _first_all_zero_from(v):
     return int(nz[-1]) + 1 if nz.size else 0
 
 
-def plan_synthesis_numpy(lf0s, fs, N, b_const_rate, b_voi_ap_win):
+def plan_synthesis_numpy(lf0s, fs, N, b_const_rate, b_voi_ap_win, const_rate_ms=5.0, type2=False):
     """
     The per-utterance index arithmetic of synthesis_from_compressed in numpy, reference line by reference line; returns
     the batch's tables in hostplan.plan_synthesis' layout.  The native planner (csrc/magphase_plan.cpp) is this, for the
     whole batch in one call; this form raises what the reference's arithmetic raises and is what the tests compare the
     native one with.
+    const_rate_ms: the grid's period (the native planner knows 5 ms only).  type2: the voicing rules of
+    synthesis_from_compressed_type2 (magphase.py:1511-1512, :1524) -- on the grid f0 > 0.0 counts as voiced, and after
+    the interpolation a frame is voiced when fs / shift of a voiced frame exceeds 1.
     """
     from scipy import interpolate
 
@@ -2570,10 +2603,14 @@ def plan_synthesis_numpy(lf0s, fs, N, b_const_rate, b_voi_ap_win):
         v_voi = v_f0 > 1.0                                         # :847
         v_shift = hm.f0_to_shift(v_f0, fs)                         # :848
         if b_const_rate:                                           # :861-870
-            v_shift, v_locs = _const_to_variable_scan(v_shift, 5.0, fs)
-            step = fs * 5.0 / 1000
+            if type2:
+                v_voi = v_f0 > 0.0                                 # :1511
+            v_shift, v_locs = _const_to_variable_scan(v_shift, const_rate_ms, fs)
+            step = fs * const_rate_ms / 1000
             centres = step * np.arange(1, n_rows + 1)
             v_voi = interpolate.interp1d(centres, v_voi, axis=0, kind="linear")(v_locs) > 0.5
+            if type2:
+                v_voi = (v_voi * fs / v_shift.astype("float64")) > 1   # :1512 (shift_to_f0), :1524
             idx = np.clip(np.searchsorted(centres, v_locs), 1, n_rows - 1)   # scipy's _call_linear bracketing
             lo, hi = idx - 1, idx
             t = (v_locs - centres[lo]) / (centres[hi] - centres[lo])
@@ -2583,6 +2620,8 @@ def plan_synthesis_numpy(lf0s, fs, N, b_const_rate, b_voi_ap_win):
         v_shift = v_shift.astype(int)                              # :879
         v_pm = np.cumsum(v_shift)                                  # :880
         n = v_pm.size
+        if type2 and n < 2:   # (the reference indexes v_pm[-2], :1519)
+            raise ValueError("utterance %d: fewer than two synthesis frames" % len(nfr))
         ns_len = int(v_pm[-1] + (v_pm[-1] - v_pm[-2]))             # :882
         _, lft, rgt = hm.frame_bounds(v_pm, ns_len)                # windowing(v_ns, v_pm): magphase.py:77-98
         if np.any(lft > N // 2) or np.any(rgt + 1 > N // 2):
@@ -2647,6 +2686,85 @@ def _const_to_variable_scan_scipy(v_shift_c_rate, frm_rate_ms, fs):
         pos = pos - shifts[i]
     return shifts, locs
 
+
+
+class Type2SynthesisPlan(CompressedSynthesisPlan):
+    """
+    synthesis_from_compressed_type2 (magphase.py:1452-1597, the output filter excluded) for a batch of utterances: the
+    type-1 plan's tables, buffers and launch sequence with
+      * the grid's period as a parameter (const_rate_ms > 0; <= 0: the variable rate) and type 2's voicing rules on it
+        (plan_synthesis_numpy(type2=True); the variable rate keeps the native planner, its arithmetic is type 1's),
+      * the phase coefficients extended to mag_dim columns and unwarped at alpha (hm.type2_phase_unwarp_matrix),
+      * the plain crossfade curves and the hf_slope line (hm.type2_synthesis_bin_curves),
+      * one noise gain per utterance, rms of the noise spectra over all frames and bins, from mpx_noise_power +
+        mpx_noise_rms (no transform) instead of mpx_noise_stats + mpx_noise_gains,
+      * the type-2 arm of the pair kernel (mpx_synthesis_compressed_type2_ola: signed real DC / Nyquist bins).
+    Constants are cached under keys of their own and the gain buffers belong to the plan: running a type-2 plan leaves
+    nothing behind that a type-1 plan on the same engine reads.
+    """
+    _n_per_key = "n_per_t2"
+    _ola_entry = "mpx_synthesis_compressed_type2_ola"
+
+    def __init__(self, engine, utts, fs, fft_len=None, hf_slope_coeff=1.0, b_voi_ap_win=True, const_rate_ms=-1.0,
+                 noise=None, frames_per_run=None, noise_mode="reference", noise_seeds=None, defer_rng=False):
+        self.const_rate_ms = float(const_rate_ms)
+        self.hf_slope_coeff = float(hf_slope_coeff)
+        const = self.const_rate_ms > 0.0
+        self._native_planner = not const
+        super().__init__(engine, utts, fs, fft_len=fft_len, b_voi_ap_win=b_voi_ap_win, b_const_rate=const, noise=noise,
+                         frames_per_run=frames_per_run, noise_mode=noise_mode, noise_seeds=noise_seeds,
+                         defer_rng=defer_rng, noise_spectra=False)
+        self._rms_dev = None
+
+    def _plan_tables(self, lf0s, b_voi_ap_win):
+        if not self.b_const_rate:
+            return super()._plan_tables(lf0s, b_voi_ap_win)
+        return plan_synthesis_numpy(lf0s, self.fs, self.fft_len, True, b_voi_ap_win, const_rate_ms=self.const_rate_ms,
+                                    type2=True)
+
+    def _bin_curves_host(self):
+        return hm.type2_synthesis_bin_curves(self.fs, self.fft_len, self.hf_slope_coeff)
+
+    def _phase_and_curve_constants(self):
+        e, fs, N = self.engine, self.fs, self.fft_len
+        H, alpha = N // 2 + 1, hm.define_alpha(fs)
+        self.u_phase = e.constant(("u_phase_t2", self.phase_dim, self.mag_dim, H, float(alpha)),
+                                  lambda: hm.type2_phase_unwarp_matrix(self.phase_dim, self.mag_dim, H, alpha))
+        self.per_v, self.ap_v, self.ap_u = (
+            e.constant(("bin_curve_t2", k, int(fs), N, self.hf_slope_coeff), lambda k=k: self._bin_curves_host()[k])
+            for k in range(3))
+
+    @property
+    def gains(self):
+        """Type 2 has one gain per utterance: see rms."""
+        return None
+
+    @property
+    def rms(self):
+        """[rms_noise] per utterance (float64, magphase.py:1539), fetched from the device on demand."""
+        return None if self._rms_dev is None else [float(x) for x in self._rms_dev.cpu().numpy()]
+
+    def _buffers(self):
+        b = getattr(self, "_buf", None)
+        if b is None:
+            b = super()._buffers()
+            torch = _torch()
+            b["power"] = torch.empty((max(self.total_frames, 1),), dtype=torch.float64, device=self.engine.device)
+            b["rms"] = torch.empty((self.n_utts,), dtype=torch.float64, device=self.engine.device)
+        return b
+
+    def _launch_noise_statistic(self, st, tab, buf, mark):
+        lib, N = self.engine.lib, self.fft_len
+        power, inv_gain = buf["power"], buf["inv_gain"]
+        _lib.check(lib.mpx_noise_power(st, N, self.noise.data_ptr(), self.npos.data_ptr(), self.nleft.data_ptr(),
+                                       self.nright.data_ptr(), self.wtype.data_ptr(), self.total_frames,
+                                       power.data_ptr()), "mpx_noise_power")
+        mark("k_noise_power")
+        self._rms_dev = buf["rms"]
+        _lib.check(lib.mpx_noise_rms(st, N, power.data_ptr(), self.utt_frame_off.data_ptr(), self.n_utts,
+                                     inv_gain.data_ptr(), self._rms_dev.data_ptr()), "mpx_noise_rms")
+        mark("k_noise_rms")
+        return None
 
 
 # ======================================================================================================

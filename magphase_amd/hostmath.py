@@ -444,13 +444,27 @@ def phase_unwarp_matrix(phase_dim, fft_len, fs, alpha):
     return u
 
 
-def crossfade_lowpass_curve(nbins_half, cut_off, bw, fs):
-    """libaudio.py:160-186 for (ones, zeros): 1 below bin_l, falling Hann half on [bin_l, bin_r], 0 above."""
+def _crossfade_bins(nbins_half, cut_off, bw, fs):
+    """libaudio.py:165-169: the crossfade's lower and upper edge as bins."""
     nfft = (nbins_half - 1) * 2
     bin_l = int(round_to_int((cut_off - bw / 2.0) * nfft / float(fs)))
     bin_r = int(round_to_int((cut_off + bw / 2.0) * nfft / float(fs)))
+    return bin_l, bin_r
+
+
+def crossfade_lowpass_curve(nbins_half, cut_off, bw, fs):
+    """libaudio.py:160-186 for (ones, zeros): 1 below bin_l, falling Hann half on [bin_l, bin_r], 0 above."""
+    bin_l, bin_r = _crossfade_bins(nbins_half, cut_off, bw, fs)
     bw_bin = bin_r - bin_l
     return np.hstack((np.ones(bin_l), np.hanning(2 * bw_bin + 1)[bw_bin:], np.zeros(nbins_half - bin_r - 1)))
+
+
+def crossfade_highpass_curve(nbins_half, cut_off, bw, fs):
+    """libaudio.py:160-186 for (zeros, ones): 0 below bin_l, rising Hann half on [bin_l, bin_r], 1 above -- the
+    low-pass curve's window mirrored (np.hanning is symmetric), not 1 - low-pass, which differs in the last bit."""
+    bin_l, bin_r = _crossfade_bins(nbins_half, cut_off, bw, fs)
+    fall = crossfade_lowpass_curve(nbins_half, cut_off, bw, fs)[bin_l:bin_r + 1]
+    return np.hstack((np.zeros(bin_l), fall[::-1], np.ones(nbins_half - bin_r - 1)))
 
 
 def synthesis_bin_curves(fs, fft_len):
@@ -468,6 +482,36 @@ def synthesis_bin_curves(fs, fft_len):
     tilt_v = 10 ** (build_mel_curve(0.6, half, amp=2.0) / 20)
     tilt_u = 10 ** ((build_mel_curve(alpha, half, amp=3.5) - 3.5) / 20)
     return tilt_v * mask ** 0.5, (1 - mask) ** 0.5, tilt_u
+
+
+def type2_synthesis_bin_curves(fs, fft_len, hf_slope_coeff=1.0):
+    """
+    Per-bin constant vectors of synthesis_from_compressed_type2 (magphase.py:1544-1553), float64:
+      per_v = crossfade low-pass            periodic component of voiced frames (la.spectral_crossfade(mag, 0): plain Hann)
+      ap_v  = crossfade high-pass           aperiodic component of voiced frames (la.spectral_crossfade(0, mag / rms))
+      ap_u  = linspace(1, hf_slope_coeff)   aperiodic component of unvoiced frames (:1547-1548)
+    No square root of the mask and no spectral tilt, unlike synthesis_bin_curves.  per_v is zero from the crossfade's
+    upper edge on, ap_v below its lower edge.
+    """
+    half = fft_len // 2 + 1
+    cf, bw = define_crossfade_params(fs)
+    return (crossfade_lowpass_curve(half, cf, bw, fs), crossfade_highpass_curve(half, cf, bw, fs),
+            np.linspace(1, hf_slope_coeff, num=half))
+
+
+def type2_phase_unwarp_matrix(phase_dim, mag_dim, nbins_out, alpha):
+    """
+    magphase.py:1494-1501 as a matrix [phase_dim x nbins_out]: nearest-neighbour extension of the phase coefficients to
+    mag_dim columns (the last coefficient repeated) followed by the mag_dim-coefficient unwarp at alpha, so rows
+    >= phase_dim - 1 of the unwarp matrix fold into the last row, as in phase_unwarp_matrix.  phase_dim > mag_dim: the
+    extension only reads the first mag_dim coefficients (interp1d(...)(np.arange(mag_dim))): the other rows are zero.
+    """
+    u_full = unwarp_matrix(mag_dim, nbins_out, alpha)
+    if phase_dim >= mag_dim:
+        return np.vstack((u_full, np.zeros((phase_dim - mag_dim, u_full.shape[1]))))
+    u = u_full[:phase_dim].copy()
+    u[phase_dim - 1] += u_full[phase_dim:].sum(axis=0)
+    return u
 
 
 # ======================================================================================================
@@ -646,16 +690,28 @@ def post_filter_tables(mag_dim, fs, av_len_at_zero=None, av_len_at_nyq=None, boo
     return int(v_nx[0]), int(v_nx[-1]), (v_lens // 2).astype(np.int64), np.linspace(b0, bn, mag_dim)
 
 
-def hpf_tables(fs, block):
+HPF_DESIGNS = ("butter40", "ellip60")
+
+
+def hpf_tables(fs, block, design="butter40"):
     """
-    Output high-pass of synthesis_from_compressed (magphase.py:981-995): Butterworth order 4 at 40 Hz as two
-    second-order sections (the same design, scipy output='sos') and, per section, the tables of the blocked scan of
-    mpx_output_hpf: the direct-form-II-transposed state update z' = A z + Bx x with A = [[-a1, 1], [-a2, 0]],
+    Output high-pass as two second-order sections (scipy output='sos') and, per section, the tables of the blocked scan
+    of mpx_output_hpf: the direct-form-II-transposed state update z' = A z + Bx x with A = [[-a1, 1], [-a2, 0]],
     y = z0 + b0 x.  Returns (sos [2 x 6], A^block [2 x 4], G [2 x block x 2] with G[n] = [1, 0] A^n), float64.
+    design: 'butter40' = Butterworth order 4 at 40 Hz (synthesis_from_compressed, magphase.py:981-995); 'ellip60' =
+    elliptic order 4, 0.5 dB ripple, 80 dB stop band, 60 Hz (synthesis_from_compressed_type2, :1599-1604).  A^block and
+    G depend on the sections' poles only; the zeros (on the unit circle for the elliptic design, at z = 1 for
+    Butterworth) enter through b0, b1, b2 in the kernels' recurrence.
     """
     from scipy import signal
 
-    sos = np.ascontiguousarray(signal.butter(4, 40 / (fs / 2.0), btype='highpass', output='sos'), dtype=np.float64)
+    if design == "butter40":
+        sos = signal.butter(4, 40 / (fs / 2.0), btype='highpass', output='sos')
+    elif design == "ellip60":
+        sos = signal.ellip(4, 0.5, 80, 60 / (fs / 2.0), btype='highpass', output='sos')
+    else:
+        raise ValueError("hpf design must be one of %r, not %r" % (HPF_DESIGNS, design))
+    sos = np.ascontiguousarray(sos, dtype=np.float64)
     pm = np.zeros((2, 4))
     g = np.zeros((2, block, 2))
     for sec in range(2):

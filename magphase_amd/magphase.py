@@ -21,8 +21,8 @@ from . import libaudio as la
 from . import libutils as lu
 from .engine import (CompressedAnalysisPlan, CompressedSynthesisPlan, GriffinLimPlan, LosslessAnalysisPlan,
                      LosslessConstRateAnalysisPlan, LosslessConstRateSynthesisPlan, LosslessRoundTripPlan,
-                     LosslessSynthesisPlan, Type2AnalysisPlan, Type2CompressedAnalysisPlan, check_const_rate_ms,
-                     get_engine, plan_const_rate_synthesis)
+                     LosslessSynthesisPlan, Type2AnalysisPlan, Type2CompressedAnalysisPlan, Type2SynthesisPlan,
+                     check_const_rate_ms, get_engine, plan_const_rate_synthesis)
 
 _epoch_provider = None
 
@@ -1038,6 +1038,77 @@ def analysis_compressed_type2(wav_file, fft_len=None, out_dir=None, mag_dim=60, 
             write_featfile(r[4], out_dir, file_id + ".shift")
         return
     return r
+
+
+# ======================================================================================================
+# type-2 synthesis from compressed features (magphase.py:1452-1606)
+# ======================================================================================================
+def _type2_synthesis_check(utts, fs, fft_len, hf_slope_coeff):
+    """Host argument checks of the type-2 synthesis, before any device work; returns fft_len."""
+    n = int(fft_len) if fft_len is not None else hm.define_fft_len(fs)
+    if n not in (1024, 2048, 4096):
+        raise ValueError("fft_len %r not supported by the HIP path (1024, 2048 or 4096)" % (n,))
+    hm.define_alpha(fs)   # (ValueError for a sample rate the warp has no alpha for)
+    if isinstance(hf_slope_coeff, (bool, np.bool_)) or not np.isscalar(hf_slope_coeff) or not np.isfinite(hf_slope_coeff):
+        raise ValueError("hf_slope_coeff must be a finite number, got %r" % (hf_slope_coeff,))
+    for i, u in enumerate(utts):
+        if len(u) != 4:
+            raise ValueError("utts[%d]: expected (m_mag_mel_log, m_real_mel, m_imag_mel, v_lf0)" % i)
+        mag, real, imag, lf0 = u
+        if np.ndim(mag) != 2 or np.ndim(real) != 2 or np.ndim(imag) != 2 or np.ndim(lf0) != 1:
+            raise ValueError("utts[%d]: m_mag_mel_log / m_real_mel / m_imag_mel must be 2-D and v_lf0 1-D" % i)
+        rows = [int(np.shape(x)[0]) for x in (mag, real, imag, lf0)]
+        if len(set(rows)) != 1:
+            raise ValueError("utts[%d]: mag / real / imag / lf0 have %d / %d / %d / %d rows" % ((i,) + tuple(rows)))
+        if np.shape(real)[1] != np.shape(imag)[1]:
+            raise ValueError("utts[%d]: m_real_mel and m_imag_mel have different widths (%d, %d)"
+                             % (i, np.shape(real)[1], np.shape(imag)[1]))
+        if np.shape(mag)[1] < 1 or np.shape(real)[1] < 1:
+            raise ValueError("utts[%d]: empty coefficient rows" % i)
+        if rows[0] < 2:   # the reference indexes v_pm[-2] (magphase.py:1519)
+            raise ValueError("utts[%d]: fewer than two synthesis frames (%d rows)" % (i, rows[0]))
+        if not np.all(np.isfinite(np.asarray(lf0, dtype=np.float64))):
+            raise ValueError("utts[%d]: v_lf0 has non-finite values (unvoiced frames carry a finite log, e.g. -1e10)" % i)
+    return n
+
+
+def synthesis_from_compressed_type2_batch(utts, fs, fft_len=None, hf_slope_coeff=1.0, b_voi_ap_win=True,
+                                          const_rate_ms=-1.0, noise=None, noise_mode='reference', noise_seeds=None,
+                                          engine=None, pcm16_norm=False, defer_rng=False):
+    """
+    Batched synthesis_from_compressed_type2 (magphase.py:1452-1606); utts: list of (m_mag_mel_log, m_real_mel,
+    m_imag_mel, v_lf0) as analysis_compressed_type2 returns them, one sample rate per call.  const_rate_ms > 0: the rows
+    lie on a grid of that period (any value); <= 0: the variable rate.  hf_slope_coeff: the aperiodic spectrum of
+    unvoiced frames is multiplied by np.linspace(1, hf_slope_coeff, fft_len/2 + 1).  The output always passes the
+    reference's elliptic high-pass (order 4, 60 Hz).  noise, noise_mode, noise_seeds, pcm16_norm and defer_rng as in
+    synthesis_from_compressed_batch.  Returns a list of float64 signals (int16 with pcm16_norm).  Engine:
+    Type2SynthesisPlan.
+    """
+    const_rate_ms = _type2_rate(const_rate_ms)
+    utts = list(utts)
+    if not utts:
+        return []
+    _type2_synthesis_check(utts, fs, fft_len, hf_slope_coeff)
+    engine = engine or get_engine()
+    plan = Type2SynthesisPlan(engine, utts, fs, fft_len=fft_len, hf_slope_coeff=hf_slope_coeff,
+                              b_voi_ap_win=b_voi_ap_win, const_rate_ms=const_rate_ms, noise=noise,
+                              noise_mode=noise_mode, noise_seeds=noise_seeds, defer_rng=defer_rng)
+    pcm_dev = engine.output_hpf(plan.run(), plan.out_off_host, fs, design="ellip60")   # magphase.py:1599-1604
+    if pcm16_norm is not False:
+        pcm = engine.output_pcm16(pcm_dev, plan.out_off_host, norm=pcm16_norm)
+    else:
+        pcm = pcm_dev.cpu().numpy()
+    return [pcm[plan.out_off_host[u]:plan.out_off_host[u + 1]] for u in range(len(utts))]
+
+
+def synthesis_from_compressed_type2(m_mag_mel_log, m_real_mel, m_imag_mel, v_lf0, fs, fft_len=None, hf_slope_coeff=1.0,
+                                    b_voi_ap_win=True, b_norm_mag=False, v_lgain=None, const_rate_ms=-1.0):
+    """magphase.py:1452-1606.  b_norm_mag and v_lgain are accepted and ignored, as in the reference (it overwrites
+    b_norm_mag with False at :1467 and its gain block, :1578-1594, is commented out): features written with
+    b_norm_mag=True synthesise as they do there, wrongly scaled."""
+    return synthesis_from_compressed_type2_batch([(m_mag_mel_log, m_real_mel, m_imag_mel, v_lf0)], fs, fft_len=fft_len,
+                                                 hf_slope_coeff=hf_slope_coeff, b_voi_ap_win=b_voi_ap_win,
+                                                 const_rate_ms=const_rate_ms)[0]
 
 
 # ======================================================================================================
