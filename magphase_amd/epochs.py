@@ -22,8 +22,6 @@ unvoiced regions (REAPER's `-u 0.005`) -- in two stages, both batched HIP kernel
 """
 import numpy as np
 
-from . import _lib
-
 
 ZFF_ADVANCE_SMPLS = 1.5   # four inclusive cumulative sums (-0.5 sample each) and one first difference (+0.5)
 
@@ -54,7 +52,6 @@ def track_epochs_batch(sigs, fs, engine=None, unvoiced_step_s=0.005, nccf_min=0.
     from .engine import get_engine
 
     e = engine or get_engine()
-    lib = e.lib
     U = len(sigs)
     if U == 0:
         return []
@@ -81,11 +78,8 @@ def track_epochs_batch(sigs, fs, engine=None, unvoiced_step_s=0.005, nccf_min=0.
     xd = torch.empty(max(int(doff[-1]), 1), dtype=torch.float64, device=e.device)
     means = torch.empty(2 * U, dtype=torch.float64, device=e.device)
     f0_d, pk_d, en_d = (torch.empty(max(int(foff[-1]), 1), dtype=torch.float32, device=e.device) for _ in range(3))
-    with torch.cuda.device(e.device):
-        _lib.check(lib.mpx_epoch_f0_track(e.stream_ptr(), sig.data_ptr(), d["off"].data_ptr(), U, dec, d["doff"].data_ptr(),
-                                          int(nd.max()), xd.data_ptr(), means.data_ptr(), d["foff"].data_ptr(), int(T.max()),
-                                          hop, win, l_min, n_lags, float(fs_d), f0_d.data_ptr(), pk_d.data_ptr(),
-                                          en_d.data_ptr()), "mpx_epoch_f0_track")
+    e.launch("mpx_epoch_f0_track", sig, d["off"], U, dec, d["doff"], int(nd.max()), xd, means, d["foff"], int(T.max()), hop,
+             win, l_min, n_lags, float(fs_d), f0_d, pk_d, en_d)
     f0_all, pk_all, en_all = (t.cpu().numpy().astype(np.float64) for t in (f0_d, pk_d, en_d))
     hop_s, win_s = hop / fs_d, win / fs_d
 
@@ -112,11 +106,8 @@ def track_epochs_batch(sigs, fs, engine=None, unvoiced_step_s=0.005, nccf_min=0.
     c_idx = torch.zeros(2 * U * cap, dtype=torch.int32, device=e.device)
     c_slope, c_score, c_frac = (torch.zeros(2 * U * cap, dtype=torch.float32, device=e.device) for _ in range(3))
     d_half = e.to_device(half_win, np.int32)
-    with torch.cuda.device(e.device):
-        _lib.check(lib.mpx_epoch_zff(e.stream_ptr(), sig.data_ptr(), d["off"].data_ptr(), U, n_max, d_half.data_ptr(), w,
-                                     bufs[0].data_ptr(), bufs[1].data_ptr(), bufs[2].data_ptr(), cap, counts.data_ptr(),
-                                     c_idx.data_ptr(), c_slope.data_ptr(), c_score.data_ptr(), c_frac.data_ptr()),
-                   "mpx_epoch_zff")
+    e.launch("mpx_epoch_zff", sig, d["off"], U, n_max, d_half, w, bufs[0], bufs[1], bufs[2], cap, counts, c_idx, c_slope,
+             c_score, c_frac)
     cnt = counts.cpu().numpy()
     idx_h = c_idx.cpu().numpy().reshape(2 * U, cap)
     slope_h = c_slope.cpu().numpy().reshape(2 * U, cap).astype(np.float64)

@@ -662,6 +662,102 @@ def var_to_const_rate_table(v_pm_smpls, const_rate_ms, fs):
     return node_row[lo].astype(np.int64), node_row[hi].astype(np.int64), t
 
 
+def check_const_rate_ms(const_rate_ms):
+    """A constant frame period in ms: finite and > 0 (ValueError otherwise)."""
+    if isinstance(const_rate_ms, (bool, np.bool_)) or not isinstance(const_rate_ms, (int, float, np.integer, np.floating)):
+        raise ValueError("const_rate_ms must be a number > 0, got %r" % (const_rate_ms,))
+    v = float(const_rate_ms)
+    if not np.isfinite(v) or v <= 0.0:
+        raise ValueError("const_rate_ms must be finite and > 0, got %r" % (const_rate_ms,))
+    return v
+
+
+def _const_rate_f0_voi(v_f0, v_pm_smpls, fs, const_rate_ms=5.0):
+    """magphase.py:2975-2980: f0 interpolated through the voiced points only, voicing by interpolation > 0.5."""
+    from scipy import interpolate
+
+    step = fs * const_rate_ms / 1000
+
+    def interp1(y, x):
+        centres = np.arange(step, x[-1], step)
+        if x[0] > 0:
+            f = interpolate.interp1d(np.r_[0, x], np.r_[y[0], y], axis=0, kind='linear')
+        else:
+            f = interpolate.interp1d(x, y, axis=0, kind='linear')
+        return f(centres)
+
+    v_voi = v_f0 > 1.0
+    v_f0_c = interp1(np.r_[v_f0[v_voi][0], v_f0[v_voi], v_f0[v_voi][-1]], np.r_[0, v_pm_smpls[v_voi], v_pm_smpls[-1]])
+    v_voi_c = interp1(v_voi.astype(np.float64), v_pm_smpls) > 0.5
+    return v_f0_c * v_voi_c
+
+
+def var_to_const_rate_batch(shift_list, f0_list, row_bases, fs, const_rate_ms):
+    """
+    Variable -> constant rate for a batch: per utterance the epochs cumsum(shifts), var_to_const_rate_table on them (rows
+    offset by the utterance's base row) and _const_rate_f0_voi.  fs: one rate, or one per utterance.  Returns
+    (row0, row1 int64, rowt float64: the batch's tables, concatenated; f0 per utterance at the constant rate; out_off
+    int64[U + 1]: utterance u's constant-rate rows are out_off[u] .. out_off[u + 1]).
+    """
+    fs_list = fs if isinstance(fs, (list, tuple, np.ndarray)) else [fs] * len(shift_list)
+    row0, row1, rowt, f0_out = [], [], [], []
+    for v_shift, v_f0, base, fs_u in zip(shift_list, f0_list, row_bases, fs_list):
+        v_pm = np.cumsum(v_shift)
+        lo, hi, t = var_to_const_rate_table(v_pm, const_rate_ms, fs_u)
+        f0_out.append(_const_rate_f0_voi(np.asarray(v_f0), v_pm, fs_u, const_rate_ms))
+        row0.append(lo + int(base)), row1.append(hi + int(base)), rowt.append(t)
+    cat = (lambda v, dt: np.concatenate(v).astype(dt) if v else np.zeros(0, dt))   # noqa: E731
+    out_off = np.concatenate(([0], np.cumsum([f.size for f in f0_out]))).astype(np.int64)
+    return cat(row0, np.int64), cat(row1, np.int64), cat(rowt, np.float64), f0_out, out_off
+
+
+def const_to_variable_rows(v_voi_c, v_locs, const_rate_ms, fs):
+    """Row tables of interp_from_const_to_variable_rate (magphase.py:2242-2252) from the grid's n rows to the frame
+    locations v_locs, with scipy interp1d's bracketing.  v_voi_c: the voicing on the grid (bool[n]: f0 > 1.0 for type 1,
+    magphase.py:847; f0 > 0.0 for type 2, :1511).  Returns (row_lo, row_hi int64, t float64, v_voi bool): the voicing at
+    v_locs is interp(v_voi_c) > 0.5 (:866-868).  A grid of one row is what scipy makes of one point: the callers that take
+    that row for every frame do so themselves (hostplan.plan_const_rate_synthesis)."""
+    from scipy import interpolate
+
+    if np.asarray(v_voi_c).dtype != np.bool_:
+        raise TypeError("const_to_variable_rows: v_voi_c is the voicing mask on the grid (bool), not f0")
+    n = int(np.size(v_voi_c))
+    centres = (fs * const_rate_ms / 1000) * np.arange(1, n + 1)
+    v_voi = interpolate.interp1d(centres, v_voi_c, axis=0, kind="linear")(v_locs) > 0.5
+    idx = np.clip(np.searchsorted(centres, v_locs), 1, n - 1)   # scipy's _call_linear bracketing
+    lo, hi = idx - 1, idx
+    t = (v_locs - centres[lo]) / (centres[hi] - centres[lo])
+    return lo.astype(np.int64), hi.astype(np.int64), t, v_voi
+
+
+def _const_to_variable_scan_scipy(v_shift_c_rate, frm_rate_ms, fs):
+    """The constant -> variable rate scan (magphase.py:1426-1449) written like the reference: one scipy interp1d call per
+    step (8 us each).  hostplan._const_to_variable_scan is the native form the tests compare with this one."""
+    from scipy import interpolate
+
+    n = np.size(v_shift_c_rate, 0)
+    step = fs * frm_rate_ms / 1000
+    centres = step * np.arange(1, n + 1)
+    f = interpolate.interp1d(centres, v_shift_c_rate, axis=0, kind="linear")
+    shifts, locs = np.zeros(n * 2), np.zeros(n * 2)
+    pos = centres[-1]
+    for i in range(2 * n - 1, 0, -1):
+        locs[i] = pos
+        try:
+            shifts[i] = f(pos)
+        except ValueError:
+            locs, shifts = locs[i + 1:], shifts[i + 1:]
+            break
+        pos = pos - shifts[i]
+    return shifts, locs
+
+
+def _first_all_zero_from(v):
+    """Smallest n with v[k] == 0 for every k >= n."""
+    nz = np.flatnonzero(np.asarray(v) != 0)
+    return int(nz[-1]) + 1 if nz.size else 0
+
+
 def post_filter_tables(mag_dim, fs, av_len_at_zero=None, av_len_at_nyq=None, boost_at_zero=None, boost_at_nyq=None):
     """
     Host tables of the MagPhase post-filter (magphase.py:2300-2347, Q20): defaults per sample rate (same warnings /

@@ -19,10 +19,12 @@ import numpy as np
 from . import hostmath as hm
 from . import libaudio as la
 from . import libutils as lu
-from .engine import (CompressedAnalysisPlan, CompressedSynthesisPlan, GriffinLimPlan, LosslessAnalysisPlan,
-                     LosslessConstRateAnalysisPlan, LosslessConstRateSynthesisPlan, LosslessRoundTripPlan,
-                     LosslessSynthesisPlan, Type2AnalysisPlan, Type2CompressedAnalysisPlan, Type2SynthesisPlan,
-                     check_const_rate_ms, get_engine, plan_const_rate_synthesis)
+from .engine import get_engine
+from .hostmath import check_const_rate_ms
+from .hostplan import plan_const_rate_synthesis
+from .plans import (CompressedAnalysisPlan, CompressedSynthesisPlan, GriffinLimPlan, LosslessAnalysisPlan,
+                    LosslessConstRateAnalysisPlan, LosslessConstRateSynthesisPlan, LosslessRoundTripPlan,
+                    LosslessSynthesisPlan, Type2AnalysisPlan, Type2CompressedAnalysisPlan, Type2SynthesisPlan)
 
 _epoch_provider = None
 
@@ -163,10 +165,10 @@ def ola(m_frm, v_pm, win_func=None, device=None):
 def get_shifts_and_frm_locs_from_const_shifts(v_shift_c_rate, frm_rate_ms, fs, interp_type='linear'):
     """magphase.py:1426-1449 (Q16): the serial backward scan from the last constant-rate centre, in the library's host
     function (scipy interp1d's float64 operation sequence, bit-identical: golden G7)."""
-    from .engine import _const_to_variable_scan, _const_to_variable_scan_scipy
+    from .hostplan import _const_to_variable_scan
 
     if interp_type != 'linear':
-        return _const_to_variable_scan_scipy(v_shift_c_rate, frm_rate_ms, fs)
+        return hm._const_to_variable_scan_scipy(v_shift_c_rate, frm_rate_ms, fs)
     return _const_to_variable_scan(v_shift_c_rate, frm_rate_ms, fs)
 
 
@@ -540,12 +542,8 @@ def griffin_lim_batch(utts, win_func=np.hanning, phase_init='random', niters=30,
         rows = torch.from_numpy(idx.astype(np.int32)).to(engine.device)
         n = int(idx.size)
         o_m, o_r, o_i = (engine.empty((n, ld)) for _ in range(3))
-        with torch.cuda.device(engine.device):
-            from . import _lib
-            _lib.check(engine.lib.mpx_min_phase(engine.stream_ptr(), N, engine.tables(N).data_ptr(), tgt.data_ptr(),
-                                                rows.data_ptr(), rows.data_ptr(),
-                                                torch.zeros(n, dtype=torch.float32, device=engine.device).data_ptr(),
-                                                n, o_m.data_ptr(), o_r.data_ptr(), o_i.data_ptr(), ld), "mpx_min_phase")
+        engine.launch("mpx_min_phase", N, engine.tables(N), tgt, rows, rows,
+                      torch.zeros(n, dtype=torch.float32, device=engine.device), n, o_m, o_r, o_i, ld)
         re, im = o_r[:, :H].clone(), o_i[:, :H].clone()
         re[:, 0], im[:, 0], re[:, -1], im[:, -1] = 1.0, 0.0, 1.0, 0.0
         if niters == 1:

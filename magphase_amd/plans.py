@@ -1,0 +1,1337 @@
+"""
+Batch plans: host float64 index arithmetic (hostmath / hostplan) -> descriptor tensors resident in HBM -> run(), the
+launch sequence of one batch.  A plan talks to the Engine object it is handed (uploads, allocations, Engine.launch) and
+imports nothing from engine.py; LosslessAnalysisPlan and LosslessSynthesisPlan build on any object that offers
+to_device / to_device_packed (the hasattr guards are for that).
+"""
+import ctypes
+import os
+
+import numpy as np
+
+from . import _lib, hostmath as hm, hostplan
+
+
+def _torch():
+    import torch
+
+    return torch
+
+
+TYPE2_ENV_NCOEFFS = 600   # la.true_envelope(..., ncoeffs=600, thres_db=0.1) of analysis_lossless_type2 (magphase.py:2829)
+TYPE2_ENV_THRES_DB = 0.1
+
+
+class _FlatRows:
+    """A list of per-utterance rows kept as ONE array + offsets; iterating / indexing cuts the views."""
+
+    def __init__(self, flat, off):
+        self.flat, self.off = flat, np.asarray(off, dtype=np.int64)
+        self._o = self.off.tolist()
+
+    def __len__(self):
+        return len(self._o) - 1
+
+    def __getitem__(self, u):
+        if u < 0:
+            u += len(self._o) - 1
+        return self.flat[self._o[u]:self._o[u + 1]]
+
+    def __iter__(self):
+        return (self[u] for u in range(len(self)))
+
+
+def _plan_ola_runs(plan, pm_rel_list, starts, out_lens, out_off_host, fft_len, n_slots, frames_per_run, up, weights=None):
+    """Shared by the two synthesis plans: runs + slot work lists (hostmath.ola_runs / balance_chunks) -> upload list.
+    weights: the slots' relative speeds (Engine.synth_ola_slot_weights) or None for equal shares."""
+    fpr = frames_per_run or int(os.environ.get("MAGPHASE_OLA_FRAMES_PER_RUN", 0)) or None
+    try:
+        if fpr:
+            raise hostplan.PlanFallback()      # per-utterance run lengths (tests, tuning): the numpy planner only
+        if isinstance(pm_rel_list, _FlatRows):   # already one array + offsets (CompressedSynthesisPlan)
+            rel_cat, f_off = np.asarray(pm_rel_list.flat, dtype=np.int64), pm_rel_list.off
+            sizes = np.diff(f_off)
+        else:
+            sizes = [int(np.size(r)) for r in pm_rel_list]
+            rel_cat = np.concatenate([np.asarray(r, dtype=np.int64) for r in pm_rel_list]) if pm_rel_list else np.zeros(0, np.int64)
+            f_off = np.concatenate(([0], np.cumsum(sizes)))
+        runs, slot_off, slot_runs = hostplan.ola_runs(rel_cat, f_off, starts, out_lens,
+                                                      np.asarray(out_off_host)[:len(sizes)], fft_len, n_slots,
+                                                      weights=weights)
+    except hostplan.PlanFallback:
+        runs, slot_off, slot_runs = hm.ola_runs(pm_rel_list, starts, out_lens, out_off_host, fft_len, n_slots,
+                                                frames_per_run=fpr, weights=None if fpr else weights)
+    plan.n_runs = int(runs.size)
+    plan.runs_host = runs
+    plan.strip_floats = plan.n_runs * (int(fft_len) + 64)
+    plan.n_slots = int(slot_off.size - 1)
+    up.append(("runs", runs.view(np.uint8), np.uint8))
+    up.append(("slot_off", slot_off, np.int32))
+    up.append(("slot_runs", slot_runs, np.int32))
+
+
+def _run_ola(engine, entry, fft_len, runs, strips, out, total_out):
+    """What every fused overlap-add run does: strips / out allocated when the caller brought none, entry(strips, out)
+    launches the pair kernel over `runs` (a plan with run tables: every output sample written once, and the runs' head
+    strips), ola_fixup completes the run boundaries.  Returns out."""
+    if strips is None:
+        strips = engine.empty((max(runs.strip_floats, 1),))
+    if out is None:
+        out = engine.empty((total_out,))
+    entry(strips, out)
+    return engine.ola_fixup(fft_len, runs, strips, out)
+
+
+def _upload_rows(engine, rows, head=(), tail=()):
+    """ONE packed upload of the row tables rows = (row0, row1, rowt) host arrays (-> int32, int32, float32) with the items
+    `head` in front of and `tail` behind them in the same copy.  Returns ((row0, row1, rowt) device, {name: tensor} of
+    the other items)."""
+    d = engine.to_device_packed(list(head) + [("row0", rows[0], np.int32), ("row1", rows[1], np.int32),
+                                              ("rowt", rows[2], np.float32)] + list(tail))
+    return (d.pop("row0"), d.pop("row1"), d.pop("rowt")), d
+
+
+def _check_prepared(prepared, engine, utts):
+    """A Prepared* handed to a plan constructor must be the host side of these utterances on this engine."""
+    if prepared.n_utts != len(utts) or prepared.engine is not engine:
+        prepared.release()
+        raise ValueError("prepared: not the host side of this batch on this engine")
+
+
+def _wait_ready(plan):
+    """A plan may be run on another stream than the one it was built on (bench.py alternates streams): that stream
+    waits for the plan's uploads too (the build stream already does)."""
+    ev = getattr(plan, "_ready", None)
+    if ev is not None:
+        _torch().cuda.current_stream(plan.engine.device).wait_event(ev)
+
+
+def _widen_pcm16(engine, raw, total):
+    """16-bit samples on the device (two per float32 of `raw`, or bytes) -> float32 [total] (mpx_pcm16_to_f32)."""
+    sig = engine.empty((max(total, 1),))
+    engine.launch("mpx_pcm16_to_f32", raw, total, sig)
+    return sig[:total]
+
+
+# ======================================================================================================
+# lossless features
+# ======================================================================================================
+class LosslessAnalysisPlan:
+    """
+    Frame descriptors of a batch of utterances for mpx_analysis_frames.
+    utts: list of (v_sig float array in [-1,1) or int16 PCM, fs, v_pm_sec, v_voi).  All must share fft_len.
+    Host math follows magphase.py:2877-2879 (pm_sec*fs), libaudio.py:435-447, magphase.py:77-98, :2198-2199.
+    """
+
+    def __init__(self, engine, utts, fft_len=None, prepared=None):
+        # prepared: a PreparedAnalysis of these utterances (Engine.prepare_analysis, e.g. from the planner thread); None:
+        # prepared here when the batch is in the plain shape the native path takes, else the generic path below
+        self.engine = engine
+        if prepared is None and hasattr(engine, "prepare_analysis") and os.environ.get("MAGPHASE_NATIVE_PREPARE", "1") != "0":
+            prepared = engine.prepare_analysis(utts, fft_len, wait=False)
+        if prepared is not None:
+            self._from_prepared(prepared, utts)
+            return
+        pos, left, right = [], [], []
+        self.v_shift, self.v_f0, self.fs, self.n_frames, self.n_smpls, self.v_pm = [], [], [], [], [], []
+        # the samples of all utterances go straight into ONE float32 buffer (page-locked when the engine has one):
+        # int16 PCM * 2^-15 and float64 -> float32 are each a single pass, no per-utterance temporaries, no concatenate
+        total = int(sum(np.shape(u[0])[0] for u in utts))
+        staged = hasattr(engine, "host_staging")
+        # a batch of 16-bit wavs (what the batch scripts read) is staged and uploaded as int16 and widened on the
+        # device (mpx_pcm16_to_f32): half the PCIe bytes and no host pass over the samples
+        all_i16 = staged and len(utts) > 0 and all(np.asarray(u[0]).dtype == np.int16 for u in utts)
+        if all_i16:
+            buf = engine.host_staging((total + 1) // 2 + 2).view(np.int16)
+        else:
+            buf = engine.host_staging(total) if staged else np.empty(total, dtype=np.float32)
+        off = 0
+        if all_i16 and len(utts) > 1:   # 16-bit PCM of the whole batch into the staging buffer on a few native threads
+            arrs = [np.ascontiguousarray(u[0]) for u in utts]
+            k = len(arrs)
+            src = (ctypes.c_void_p * k)(*[a.ctypes.data for a in arrs])
+            nb = np.asarray([a.nbytes for a in arrs], dtype=np.int64)
+            doff = np.concatenate(([0], np.cumsum(nb)[:-1])).astype(np.int64)
+            n_thr = engine.host_threads(int(nb.sum())) if hasattr(engine, "host_threads") else 8
+
+            def _copy(arrs=arrs, src=src, nb=nb, doff=doff):   # (keeps the arrays alive until the copy is done)
+                if engine.lib.mpx_host_copy_many(len(arrs), src, nb.ctypes.data, doff.ctypes.data, buf.ctypes.data, n_thr) != 0:
+                    raise _lib.MagphaseHipError("mpx_host_copy_many failed")
+
+            copy_done = engine.background(_copy) if hasattr(engine, "background") else None
+            if copy_done is None:
+                _copy()
+            copied = True
+        else:
+            copied, copy_done = False, None
+        try:
+            self._build_generic(engine, utts, fft_len, buf, off, copied, all_i16, staged, total, pos, left, right)
+        except BaseException:
+            # Whatever goes wrong between the submit and the upload (a malformed utterance, an fft_len mismatch): the native
+            # copy must have stopped writing into the page-locked staging buffer before this constructor is left --
+            # iobatch retries a failed batch one utterance at a time straight away, and host_staging would hand the same
+            # buffer out again while the copy still runs (silent corruption of the retry's samples)
+            if copy_done is not None:
+                try:
+                    copy_done.result()
+                except BaseException:
+                    pass
+            raise
+        if copy_done is not None:
+            copy_done.result()   # the staged samples are in place (the copy ran beside the index arithmetic)
+        self._upload_generic(engine, buf, all_i16, staged, total, pos, left, right)
+
+    def _build_generic(self, engine, utts, fft_len, buf, off, copied, all_i16, staged, total, pos, left, right):
+        for (v_sig, fs, v_pm_sec, v_voi) in utts:
+            v_sig = np.asarray(v_sig)
+            n = v_sig.shape[0]
+            if copied:
+                pass
+            elif all_i16:
+                buf[off:off + n] = v_sig
+            elif v_sig.dtype == np.int16:
+                np.multiply(v_sig, np.float32(1.0 / 32768.0), out=buf[off:off + n])   # exact: == astype(f32) / 32768
+            else:
+                buf[off:off + n] = v_sig
+            N = fft_len if fft_len is not None else hm.define_fft_len(fs)
+            if not hasattr(self, "fft_len"):
+                self.fft_len = N
+            elif N != self.fft_len:
+                raise ValueError("all utterances of a plan must share fft_len (bucket by sample rate)")
+            self.fs.append(fs)
+            self.n_smpls.append(n)
+            off += n
+        sig_off = np.concatenate(([0], np.cumsum(self.n_smpls)))[:-1] if utts else np.zeros(0)
+        try:     # the index arithmetic of the whole batch in one native call (hostplan / csrc/magphase_plan.cpp) ...
+            r = hostplan.plan_analysis([u[2] for u in utts], [u[3] for u in utts], self.n_smpls, self.fs, sig_off)
+            fo = r["frame_off"]
+            for u in range(len(utts)):
+                a, b = int(fo[u]), int(fo[u + 1])
+                self.v_shift.append(r["left"][a:b]), self.v_pm.append(r["pm"][a:b]), self.v_f0.append(r["f0"][a:b])
+                self.n_frames.append(b - a)
+            pos[:], left[:], right[:] = [r["pos"]], [r["left"]], [r["right"]]
+        except hostplan.PlanFallback:   # ... or utterance by utterance in numpy (same arithmetic; raises what it raises)
+            for (v_sig, fs, v_pm_sec, v_voi), n, o in zip(utts, self.n_smpls, sig_off):
+                pm_sec, voi = hm.clean_epochs(v_pm_sec, v_voi, check_len_smpls=n, fs=fs)
+                pm, lft, rgt = hm.frame_bounds(pm_sec * fs, n)
+                pos.append(pm + int(o))
+                left.append(lft)
+                right.append(rgt)
+                self.v_shift.append(lft)
+                self.v_pm.append(pm)
+                self.v_f0.append(hm.shift_to_f0(lft, voi, fs))
+                self.n_frames.append(pm.size)
+        self.total_frames = int(sum(self.n_frames))
+        self.frame_off = np.concatenate(([0], np.cumsum(self.n_frames))).astype(np.int64)
+        right_cat = np.concatenate(right) if right else np.zeros(0, dtype=np.int64)
+        # frames longer than fft_len (the reference warns once per such frame): rare -- one pass over the batch, the
+        # per-utterance lists only where there is something to list
+        self.long_frame_lens = [[] for _ in self.v_shift]
+        if right_cat.size:
+            left_cat = np.concatenate(left) if len(left) > 1 else np.asarray(left[0])
+            tot = left_cat + right_cat + 1
+            hit = np.flatnonzero(tot > self.fft_len)
+            if hit.size:
+                utt_of = np.searchsorted(self.frame_off, hit, side="right") - 1
+                for i, u in zip(hit.tolist(), utt_of.tolist()):
+                    self.long_frame_lens[u].append(int(tot[i]))
+        self.total_smpls = int(off)
+
+    def _upload_generic(self, engine, buf, all_i16, staged, total, pos, left, right):
+        e = engine
+        if all_i16:
+            self.sig = _widen_pcm16(e, e.upload_staged((total + 1) // 2 + 2), total)
+        else:
+            self.sig = e.upload_staged(total) if staged else e.to_device(buf, np.float32)
+        desc = e.to_device_packed([("pos", np.concatenate(pos) if pos else np.zeros(0), np.int64),     # one H2D copy
+                                   ("left", np.concatenate(left) if left else np.zeros(0), np.int32),
+                                   ("right", np.concatenate(right) if right else np.zeros(0), np.int32)])
+        self.pos, self.left, self.right = desc["pos"], desc["left"], desc["right"]
+
+    def _from_prepared(self, p, utts):
+        """Takes over a PreparedAnalysis: two DMAs (samples, tables) and, for 16-bit input, the widening kernel."""
+        e, torch = self.engine, _torch()
+        _check_prepared(p, e, utts)
+        self.fft_len, self.fs = p.fft_len, p.fs
+        self.n_smpls = [int(u[0].shape[0]) for u in utts]
+        fo = self.frame_off = p.frame_off
+        self.total_frames, self.total_smpls = p.total_frames, p.total_smpls
+        self.n_frames = np.diff(fo).tolist()
+        self.v_shift, self.v_pm, self.v_f0 = _FlatRows(p.left64, fo), _FlatRows(p.pm, fo), _FlatRows(p.f0, fo)
+        self.f0_med_flat = p.f0_med
+        self.long_frame_lens = [[] for _ in range(p.n_utts)]
+        if p.long:
+            utt_of = np.searchsorted(fo, [i for i, _n in p.long], side="right") - 1
+            for (i, n), u in zip(p.long, utt_of.tolist()):
+                self.long_frame_lens[u].append(n)
+        F, total = p.total_frames, p.total_smpls
+        o_pos, o_left, o_right, o_voi = p.offs
+        slot, p.slot = p.slot, None          # from here on the upload's event guards the slot
+        sd, dd, ev = e._slot_upload(slot, p.stage_bytes, p.desc_bytes)
+        self._ready = ev
+        if p.all_i16:
+            self.sig = _widen_pcm16(e, sd, total)
+        else:
+            self.sig = sd[:4 * total].view(torch.float32)
+        self.pos = dd[o_pos:o_pos + 8 * F].view(torch.int64)
+        self.left = dd[o_left:o_left + 4 * F].view(torch.int32)
+        self.right = dd[o_right:o_right + 4 * F].view(torch.int32)
+        self.voi_dev = dd[o_voi:o_voi + 4 * F].view(torch.float32)    # (f0 > 0): CompressedAnalysisPlan's voicing row
+
+    def run(self, out=None, precise=False, rows_in_use=None):
+        _wait_ready(self)
+        return self.engine.analysis_frames(self.fft_len, self.sig, self.pos, self.left, self.right, out=out,
+                                           precise=precise, rows_in_use=rows_in_use if precise else None)
+
+
+class LosslessSynthesisPlan:
+    """
+    PSOLA bookkeeping for a batch: per utterance v_f0 (float64) -> shift -> pm (magphase.py:1771-1772, Q2/Q3)
+    -> ola() offsets and trimming (magphase.py:34-62) -> runs of frames for the fused overlap-add (hostmath.ola_runs).
+    All float64/int host math; device gets int tables.
+    """
+
+    def __init__(self, engine, f0_list, fs_list, fft_len, frames_per_run=None, comp_slots=False):
+        # comp_slots: the slot count and weights of the compressed / round-trip pair kernels (mpx_synth_comp_slots)
+        self.engine = engine
+        self.fft_len = fft_len
+        pm_rel, starts, lens, nfr = [], [], [], []
+        self.v_pm = []
+        try:
+            r = hostplan.plan_lossless_synthesis(f0_list, fs_list, fft_len)
+            fo = r["frame_off"]
+            for u in range(len(f0_list)):
+                a, b = int(fo[u]), int(fo[u + 1])
+                self.v_pm.append(r["v_pm"][a:b]), pm_rel.append(r["pm_rel"][a:b])
+                starts.append(int(r["out_start"][u])), lens.append(int(r["out_len"][u])), nfr.append(b - a)
+        except hostplan.PlanFallback:
+            for v_f0, fs in zip(f0_list, fs_list):
+                v_pm = np.cumsum(hm.f0_to_shift(np.asarray(v_f0, dtype=np.float64), fs)).astype(int)
+                rel, start, out_len = hm.ola_plan(v_pm, fft_len)
+                self.v_pm.append(v_pm)
+                pm_rel.append(rel)
+                starts.append(start)
+                lens.append(out_len)
+                nfr.append(v_pm.size)
+        self.out_len = [int(x) for x in lens]
+        self.out_off_host = np.concatenate(([0], np.cumsum(lens))).astype(np.int64)
+        self.total_out = int(self.out_off_host[-1])
+        self.max_out_len = int(max(lens)) if lens else 0
+        self.total_frames = int(sum(nfr))
+        e = engine
+        _up = []   # (attribute, host array, dtype): uploaded together (Engine.to_device_packed)
+        _up.append(("utt_frame_off", np.concatenate(([0], np.cumsum(nfr))), np.int32))
+        _up.append(("pm_rel", np.concatenate(pm_rel) if pm_rel else np.zeros(0), np.int32))
+        _up.append(("out_start", np.asarray(starts), np.int32))
+        _up.append(("out_off", self.out_off_host, np.int64))
+        if comp_slots:   # True: the compressed synthesis kernel's slots and shares; "roundtrip": k_roundtrip_pair's
+            n_slots = e.synth_comp_slots()
+            weights = e.synth_ola_slot_weights(comp=comp_slots)
+            if os.environ.get("MAGPHASE_RT_WEIGHTS") and weights is not None:   # experiment: "w0,w1,w2" by age rank of the pair
+                w3 = [float(x) for x in os.environ["MAGPHASE_RT_WEIGHTS"].split(",")]
+                # (6 wave pairs per 12-wave workgroup; pairs 0-1 / 2-3 / 4-5 hold the oldest / middle / youngest waves)
+                weights = np.asarray([w3[((i % 6) * 2) // 4] for i in range(n_slots)], dtype=np.float32)
+        else:
+            n_slots = e.synth_ola_slots() if hasattr(e, "synth_ola_slots") else 1024
+            weights = e.synth_ola_slot_weights() if hasattr(e, "synth_ola_slot_weights") else None
+        _plan_ola_runs(self, pm_rel, starts, lens, self.out_off_host, fft_len, n_slots, frames_per_run, _up, weights=weights)
+        for _k, _t in e.to_device_packed(_up).items():
+            setattr(self, _k, _t)
+
+    def run(self, mag, real, imag, strips=None, out=None):
+        """Fused path: k_synth_ola_pair (per-run LDS overlap-add, output written in place) + k_ola_fixup (run boundaries)."""
+        e = self.engine
+        return _run_ola(e, lambda strips, out: e.synthesis_lossless_ola(self.fft_len, mag, real, imag, self, strips, out),
+                        self.fft_len, self, strips, out, self.total_out)
+
+    def run_unfused(self, mag, real, imag, frames=None, out=None):
+        """Two-kernel form: frames to HBM, then the ascending-order gather (bit-for-bit the reference's sum order)."""
+        e = self.engine
+        frames = e.synthesis_lossless_frames(self.fft_len, mag, real, imag, out=frames)
+        return e.ola_gather(self.fft_len, frames, self.utt_frame_off, self.pm_rel, self.out_start, self.out_off,
+                            self.max_out_len, self.total_out, out=out)
+
+
+class LosslessRoundTripPlan:
+    """
+    Copy synthesis of a batch (analysis_lossless followed by synthesis_from_lossless on the same frames,
+    demos/demo_copy_synthesis_lossless.py:44-50) as ONE launch: the analysis plan's frame tables plus a synthesis plan
+    built from the f0 values the analysis derives on the host (magphase.py:2198-2207 -> :1771-1772), cut into runs for
+    the round-trip kernel's slots.  run() returns ((mag, real, imag), pcm): the feature rows analysis_lossless returns
+    and the waveform synthesis_from_lossless builds from them.
+    """
+
+    def __init__(self, engine, utts, fft_len=None, frames_per_run=None):
+        self.engine = engine
+        if not utts:   # an empty batch: nothing to plan, run() returns empty tensors
+            self.analysis = self.synthesis = None
+            self.fft_len = fft_len or 4096
+            self.total_frames = self.total_out = 0
+            self.out_off_host = np.zeros(1, dtype=np.int64)
+            return
+        self.analysis = LosslessAnalysisPlan(engine, utts, fft_len=fft_len)
+        self.fft_len = self.analysis.fft_len
+        self.synthesis = LosslessSynthesisPlan(engine, self.analysis.v_f0, self.analysis.fs, self.fft_len,
+                                               frames_per_run=frames_per_run, comp_slots="roundtrip")
+        if self.synthesis.total_frames != self.analysis.total_frames:
+            raise ValueError("round trip: the synthesis plan must cover exactly the analysed frames")
+        self.total_frames = self.analysis.total_frames
+        self.total_out = self.synthesis.total_out
+        self.out_off_host = self.synthesis.out_off_host
+
+    def run(self, feats=None, strips=None, out=None):
+        e, a, s = self.engine, self.analysis, self.synthesis
+        if feats is None:
+            feats = tuple(e.empty_feats(self.total_frames, self.fft_len // 2 + 1) for _ in range(3))
+        if out is None:
+            out = e.empty((self.total_out,))
+        if self.total_frames == 0:
+            return feats, out
+        _run_ola(e, lambda strips, out: e.roundtrip_lossless_ola(self.fft_len, a, s, feats, strips, out),
+                 self.fft_len, s, strips, out, self.total_out)
+        return feats, out
+
+
+class LosslessConstRateAnalysisPlan:
+    """
+    analysis_lossless on a constant frame rate (magphase.py:2967-2980 with const_rate_ms as a parameter, without the mel
+    warp that follows there): a LosslessAnalysisPlan (k_analysis writes the variable-rate rows into scratch), the row
+    tables and f0 of hostmath.var_to_const_rate_batch (rows offset per utterance).  run() = k_analysis ->
+    k_rows_lerp; the scratch is released once the interpolation is queued.
+    """
+
+    def __init__(self, engine, utts, fft_len=None, const_rate_ms=5.0, prepared=None):
+        self.engine = e = engine
+        self.const_rate_ms = hm.check_const_rate_ms(const_rate_ms)
+        self.lossless = pl = LosslessAnalysisPlan(engine, utts, fft_len=fft_len, prepared=prepared)
+        self.fft_len, self.fs, self.long_frame_lens = pl.fft_len, pl.fs, pl.long_frame_lens
+        U = len(utts)
+        self.row0_host, self.row1_host, self.rowt_host, self.v_f0, self.out_off = hm.var_to_const_rate_batch(
+            [pl.v_shift[u] for u in range(U)], [pl.v_f0[u] for u in range(U)], pl.frame_off[:U], pl.fs,
+            self.const_rate_ms)
+        self.total_out_frames = int(self.out_off[-1])
+        self.rows, _ = _upload_rows(e, (self.row0_host, self.row1_host, self.rowt_host))
+
+    def run(self, out=None):
+        """Returns (mag, real, imag) [total_out_frames x H] device rows (utterance u: rows out_off[u] .. out_off[u+1])."""
+        e = self.engine
+        H = self.fft_len // 2 + 1
+        if out is None:
+            out = tuple(e.empty_feats(self.total_out_frames, H) for _ in range(3))
+        if self.total_out_frames == 0:
+            return out
+        var = self.lossless.run()
+        e.rows_lerp(var, self.rows, self.total_out_frames, out=out)
+        del var   # (stream-ordered: the allocator reuses the scratch after the interpolation)
+        return out
+
+
+class LosslessConstRateSynthesisPlan:
+    """
+    synthesis_from_lossless from constant-rate rows (the reference's constant -> variable rate steps of
+    synthesis_from_compressed, magphase.py:848, :861-870, followed by :1759-1776): per utterance f0 -> shifts, the
+    uncapped scan (hostplan.const_to_variable_scan_uncapped), the row tables and voicing at the frame locations
+    (hostmath.const_to_variable_rows), f0 at the variable rate (shift_to_f0, b_smooth=False); then a LosslessSynthesisPlan for the
+    PSOLA bookkeeping.  run(): the LERP arm of k_synth_ola_pair (rows interpolated as they are loaded); run_staged():
+    k_rows_lerp into variable-rate scratch rows, then k_synth_ola_pair.  Utterances without rows give empty signals.
+    """
+
+    def __init__(self, engine, f0_list, fs_list, fft_len, const_rate_ms=5.0, frames_per_run=None, host=None):
+        # host: hostplan.plan_const_rate_synthesis(f0_list, fs_list, const_rate_ms) when the caller has it already
+        self.engine = e = engine
+        self.fft_len = int(fft_len)
+        self.const_rate_ms = hm.check_const_rate_ms(const_rate_ms)
+        r = host if host is not None else hostplan.plan_const_rate_synthesis(f0_list, fs_list, self.const_rate_ms)
+        self.live, self.n_rows = r["live"], r["n_rows"]
+        self.v_shift, self.v_locs, self.v_voi, self.v_f0 = r["v_shift"], r["v_locs"], r["v_voi"], r["v_f0"]
+        self.row0_host, self.row1_host, self.rowt_host = r["row0"], r["row1"], r["rowt"]
+        self.total_rows = int(sum(self.n_rows))
+        self.inner = None
+        out_len = [0] * len(self.n_rows)
+        if self.live:
+            self.inner = LosslessSynthesisPlan(e, self.v_f0, [fs_list[u] for u in self.live], self.fft_len,
+                                               frames_per_run=frames_per_run)
+            for k, u in enumerate(self.live):
+                out_len[u] = self.inner.out_len[k]
+            self.rows, _ = _upload_rows(e, (self.row0_host, self.row1_host, self.rowt_host))
+        self.total_frames = self.inner.total_frames if self.inner is not None else 0
+        self.out_len = out_len
+        self.out_off_host = np.concatenate(([0], np.cumsum(out_len))).astype(np.int64)
+        self.total_out = int(self.out_off_host[-1])
+
+    def _check_rows(self, mag):
+        if int(mag.shape[0]) != self.total_rows:
+            raise ValueError("constant-rate rows: %d given, the plan has %d" % (int(mag.shape[0]), self.total_rows))
+
+    def run(self, mag, real, imag, strips=None, out=None):
+        """Fused: k_synth_ola_pair<P, LERP = true> + k_ola_fixup.  Returns the signals [total_out] (u at out_off_host[u])."""
+        e = self.engine
+        self._check_rows(mag)
+        if out is None:
+            out = e.empty((self.total_out,))
+        if self.inner is None:
+            return out
+        s = self.inner
+        return _run_ola(e, lambda strips, out: e.synthesis_lossless_ola_lerp(self.fft_len, mag, real, imag, self.rows, s,
+                                                                              strips, out),
+                        self.fft_len, s, strips, out, self.total_out)
+
+    def run_staged(self, mag, real, imag, rows_out=None, out=None):
+        """Staged: k_rows_lerp into variable-rate rows [total_frames x H], then the unchanged k_synth_ola_pair."""
+        self._check_rows(mag)
+        if out is None:
+            out = self.engine.empty((self.total_out,))
+        if self.inner is None:
+            return out
+        var = self.engine.rows_lerp((mag, real, imag), self.rows, self.total_frames, out=rows_out)
+        return self.inner.run(var[0], var[1], var[2], out=out)
+
+
+class _OlaRuns:
+    """Run / slot tables of one overlap-add kernel over a GriffinLimPlan's frames (pm_rel shared with the plan)."""
+
+
+class GriffinLimPlan:
+    """
+    Device tables of griffin_lim (magphase.py:3320-3372) for a batch of utterances sharing fft_len: shifts -> epochs ->
+    ola bookkeeping and the analysis frame tables of every iteration (hostmath.griffin_lim_plan), the runs of the first
+    synthesis (k_synth_ola_pair's slots, mpx_synthesis_lossless_ola) and of the iterations (k_griffin_lim_pair's: the
+    round-trip kernel's slots and weights), two signal buffers (ping-pong: an iteration never reads the buffer it writes)
+    and the head strips.  run() returns (signal, phase rows or None).
+    """
+
+    def __init__(self, engine, shift_list, fft_len, frames_per_run=None):
+        self.engine = e = engine
+        self.fft_len = N = int(fft_len)
+        r = hm.griffin_lim_plan(shift_list, N)
+        self.v_pm = r["v_pm"]
+        self.out_len = [int(x) for x in r["out_len"]]
+        self.out_off_host = r["out_off"]
+        self.frame_off = r["frame_off"]
+        self.total_out = int(self.out_off_host[-1])
+        self.total_frames = int(self.frame_off[-1])
+        up = [("pm_rel", np.concatenate(r["pm_rel"]), np.int32), ("frame_pos", r["frame_pos"], np.int64),
+              ("frame_left", r["frame_left"], np.int32), ("frame_right", r["frame_right"], np.int32)]
+        for k, t in e.to_device_packed(up).items():
+            setattr(self, k, t)
+        self.synth, self.iter = _OlaRuns(), _OlaRuns()
+        starts = [int(x) for x in r["out_start"]]
+        for runs, n_slots, w in ((self.synth, e.synth_ola_slots(), e.synth_ola_slot_weights()),
+                                 (self.iter, e.synth_comp_slots(), e.synth_ola_slot_weights(comp="roundtrip"))):
+            up = []
+            _plan_ola_runs(runs, r["pm_rel"], starts, self.out_len, self.out_off_host, N, n_slots, frames_per_run, up,
+                           weights=w)
+            for k, t in e.to_device_packed(up).items():
+                setattr(runs, k, t)
+            runs.pm_rel = self.pm_rel
+        self.strips = e.empty((max(self.synth.strip_floats, self.iter.strip_floats, 1),))
+        self.bufs = (e.empty((max(self.total_out, 1),)), e.empty((max(self.total_out, 1),)))
+
+    def run(self, target, init, niters, phase_rows=False):
+        """target: device magnitude rows [F x H] (row pitch target.stride(0)); init: a LIST [mag', phasor real, phasor imag]
+        of rows of the same pitch for the first synthesis (hostmath.griffin_lim_fold), emptied once that synthesis is
+        queued -- nothing else reads them, so their memory goes back to the allocator (stream-ordered) before the
+        iterations; niters >= 1 syntheses.  phase_rows (niters >= 2): rows of the same pitch receive the phase
+        synthesised last (written by the last iteration), allocated after the init rows are released.
+        Returns (signal buffer: total_out samples, utterance u at out_off_host[u]; phase rows or None)."""
+        e, N = self.engine, self.fft_len
+        a, b = self.bufs
+        e.synthesis_lossless_ola(N, init[0], init[1], init[2], self.synth, self.strips, a)
+        e.ola_fixup(N, self.synth, self.strips, a)
+        init.clear()
+        phase = None
+        if phase_rows and niters > 1:
+            phase = e.empty((max(self.total_frames, 1), int(target.stride(0))))[:self.total_frames, :target.shape[1]]
+        for i in range(1, int(niters)):
+            e.griffin_lim_ola(N, self, target, a, b, self.strips, phase_out=phase if i == niters - 1 else None)
+            e.ola_fixup(N, self.iter, self.strips, b)
+            a, b = b, a
+        return a[:self.total_out], phase
+
+
+# ======================================================================================================
+# compressed-feature synthesis (magphase.py:825-997)
+# ======================================================================================================
+class CompressedSynthesisPlan:
+    """
+    Host fp64 bookkeeping + device tables for a batch of utterances synthesised from compressed features.
+    utts: list of (m_mag_mel_log [F x mag_dim], m_real_mel [F x phase_dim], m_imag_mel, v_lf0 [F]) float arrays.
+    Follows magphase.py:836-897 (constants, f0/voicing/shift, constant->variable rate scan, epochs, noise length,
+    noise windows) and :969-976 (anti-ringing lengths, ola) -- all index math in float64/int on the host.
+    """
+
+    # what Type2SynthesisPlan changes: the planner for a grid the native one does not know, the phase unwarp matrix and
+    # the per-bin curves, the noise statistic and the entry of the pair kernel
+    _native_planner = True      # Engine.prepare_synthesis / hostplan.plan_synthesis serve this plan's frame tables
+    _n_per_key = "n_per"
+    _ola_entry = "mpx_synthesis_compressed_ola"
+
+    def __init__(self, engine, utts, fs, fft_len=None, b_voi_ap_win=True, b_const_rate=False, alpha_phase=None,
+                 noise=None, frames_per_run=None, per_phase_type="magphase", post_filter=False, b_fbank_mel=False,
+                 noise_mode="reference", noise_seeds=None, defer_rng=False, noise_spectra=None, prepared=None):
+        # prepared: a PreparedSynthesis of these utterances (Engine.prepare_synthesis, e.g. from the planner thread)
+        # noise_spectra: None = MAGPHASE_NOISE_SPECTRA ("recompute", the default / "store"); True: every noise frame is
+        #            transformed once, its spectrum kept in HBM between the statistics and the synthesis launch (N = 4096)
+        # defer_rng: the reference noise stream's advanced state stays on the device (Engine.numpy_global_uniform(defer=True));
+        #            the caller owes Engine.mt_sync() before numpy's global generator is used again
+        # post_filter: False / True ('magphase': mp.post_filter on the device) / 'merlin' (mp.post_filter_merlin on the device)
+        # (the reference's pf_type vocabulary: 'no' means no filtering, magphase.py:3229-3262 -- anything else is an error,
+        #  not silently "on")
+        if isinstance(post_filter, str):
+            if post_filter not in ("no", "magphase", "merlin"):
+                raise ValueError("post_filter must be False / None / 'no', True / 'magphase' or 'merlin', not %r" % (post_filter,))
+            self.apply_post_filter = {"no": False, "magphase": "magphase", "merlin": "merlin"}[post_filter]
+        elif post_filter is None or isinstance(post_filter, (bool, np.bool_, int, np.integer)):
+            # truthy non-bool callers (b_post_filter=1, a numpy comparison's np.bool_) mean what bool() says
+            if post_filter is not None and not isinstance(post_filter, (bool, np.bool_)) and int(post_filter) not in (0, 1):
+                raise ValueError("post_filter must be False / None / 'no', True / 'magphase' or 'merlin', not %r" % (post_filter,))
+            self.apply_post_filter = bool(post_filter)
+        else:
+            raise ValueError("post_filter must be False / None / 'no', True / 'magphase' or 'merlin', not %r" % (post_filter,))
+        self.b_const_rate = bool(b_const_rate)
+        if noise_mode not in ("reference", "device"):
+            raise ValueError("noise_mode must be 'reference' (numpy global RNG, magphase.py:883) or 'device' (Philox on the GPU)")
+        self.noise_mode = noise_mode
+        if noise_mode == "device" and noise is not None:
+            raise ValueError("noise_mode='device' generates the source itself: do not pass noise")
+
+        if per_phase_type not in ("magphase", "min_phase", "linear"):
+            raise ValueError("per_phase_type must be 'magphase', 'min_phase' or 'linear'")
+        self.per_phase_type = per_phase_type
+
+        self.engine = e = engine
+        self.fs = fs
+        N = self.fft_len = int(fft_len) if fft_len else hm.define_fft_len(fs)
+        alpha = hm.define_alpha(fs)
+        self.alpha_phase = alpha if alpha_phase is None else alpha_phase
+        # Variable-rate features (rows == frames: identity tables, weight 0) take the same unwarp launch as constant-rate ones
+        # (mpx_mel_unwarp_rows): the interpolation is then exact (fmaf(0, 0, m) = m: the same values as mpx_mel_unwarp), and the
+        # phase rows are produced only where the synthesis reads them -- voiced frames, bins below the crossfade's end: a
+        # quarter of the work of the plain form, which unwarped all 2 049 bins of both phase streams for every frame (round 5:
+        # 0.81 -> ... ms per 128-utterance generation launch).  MAGPHASE_UNWARP_ROWS_VAR=0: the plain form.
+        self.unwarp_rows = self.b_const_rate or os.environ.get("MAGPHASE_UNWARP_ROWS_VAR", "1") != "0"
+        # the native whole-launch planner (Engine.prepare_synthesis; `prepared`: built ahead, e.g. on the planner thread) takes
+        # the plain case: ndarray coefficient matrices, the default run planner
+        if (prepared is None and frames_per_run is None and self._native_planner and hasattr(e, "prepare_synthesis")
+                and not os.environ.get("MAGPHASE_OLA_FRAMES_PER_RUN") and os.environ.get("MAGPHASE_NATIVE_PREPARE", "1") != "0"):
+            prepared = e.prepare_synthesis(utts, fs, fft_len=fft_len, b_voi_ap_win=b_voi_ap_win, b_const_rate=b_const_rate,
+                                           wait=False)
+        if prepared is not None:
+            _check_prepared(prepared, e, utts)
+        if prepared is not None and (frames_per_run is not None or prepared.key != (
+                int(fs), N, bool(b_const_rate), bool(b_voi_ap_win), bool(self.unwarp_rows))):
+            prepared.release()
+            prepared = None
+        # either builder sets the batch's shape (mag_dim, phase_dim, n_rows, n_utts, frame_off, ns_len, out_len), the host
+        # tables behind v_shift / v_pm / v_voi (_tabs), the runs (n_runs, n_slots, runs_host) and the device tables, and
+        # returns the staged coefficients on the device; what follows from those is the same for both
+        if prepared is not None:
+            coef, mt_device = self._tables_prepared(prepared, noise, noise_mode, noise_seeds)
+        else:
+            coef, mt_device = self._tables_generic(utts, b_voi_ap_win, noise, noise_mode, noise_seeds, frames_per_run)
+        self.strip_floats = self.n_runs * (N + 64)
+        n_m, n_p = self.n_rows * self.mag_dim, self.n_rows * self.phase_dim
+        self.a_mag = coef[:n_m].view(self.n_rows, self.mag_dim)
+        self.a_real = coef[n_m:n_m + n_p].view(self.n_rows, self.phase_dim)
+        self.a_imag = coef[n_m + n_p:n_m + 2 * n_p].view(self.n_rows, self.phase_dim)
+        H = N // 2 + 1
+        # constants: unwarp matrices and per-bin curves (float64 -> float32)
+        # (resident on the device per configuration: rebuilding them costs 7 ms on the host, as much as the rest of a
+        # single-utterance call -- tools/archive/latency_probe.py)
+        if b_fbank_mel:   # magphase.py:851-852: filter-bank unwarp = a different [mag_dim x H] matrix, same kernel
+            self.u_mag = e.constant(("u_mag_fbank", self.mag_dim, H, float(alpha)),
+                                    lambda: hm.unwarp_fbank_matrix(self.mag_dim, H, alpha))
+        else:
+            self.u_mag = e.constant(("u_mag", self.mag_dim, H, float(alpha)),
+                                    lambda: hm.unwarp_matrix(self.mag_dim, H, alpha))
+        self._phase_and_curve_constants()
+        self._gains_dev = None
+        # "noise spectra once" (opt-in): see run()
+        self.noise_spectra = ((os.environ.get("MAGPHASE_NOISE_SPECTRA", "recompute") == "store")
+                              if noise_spectra is None else bool(noise_spectra))
+        if noise_mode == "device":
+            self.noise = e.empty((max(int(self.noise_off_host[-1]), 1),))
+            e.launch("mpx_noise_uniform", self.n_utts, self.noise_seeds_dev, self.noise_off_dev, int(max(self.ns_len)),
+                     self.noise)
+        elif mt_device:
+            self.noise = e.numpy_global_uniform(int(sum(self.ns_len)), defer=bool(defer_rng))
+
+    def _phase_and_curve_constants(self):
+        e, fs, N = self.engine, self.fs, self.fft_len
+        self.u_phase = e.constant(("u_phase", self.phase_dim, N, int(fs), float(self.alpha_phase)),
+                                  lambda: hm.phase_unwarp_matrix(self.phase_dim, N, fs, self.alpha_phase))
+        self.per_v, self.ap_v, self.ap_u = (
+            e.constant(("bin_curve", k, int(fs), N), lambda k=k: hm.synthesis_bin_curves(fs, N)[k]) for k in range(3))
+
+    def _bin_curves_host(self):
+        return hm.synthesis_bin_curves(self.fs, self.fft_len)
+
+    def _n_per(self):
+        """Bins from n_per on have no periodic component (the curve is exactly zero there)."""
+        return self.engine.host_constant((self._n_per_key, int(self.fs), self.fft_len), lambda: hm._first_all_zero_from(
+            np.asarray(self._bin_curves_host()[0], dtype=np.float32)))
+
+    def _plan_tables(self, lf0s, b_voi_ap_win):
+        """The batch's frame tables (hostplan.plan_synthesis' layout)."""
+        fs, N, b_const_rate = self.fs, self.fft_len, self.b_const_rate
+        try:    # index arithmetic of the whole batch in one native call (hostplan / csrc/magphase_plan.cpp) ...
+            return hostplan.plan_synthesis([np.exp(l) for l in lf0s], fs, N, b_const_rate, b_voi_ap_win)   # :846
+        except hostplan.PlanFallback:   # ... or utterance by utterance in numpy: the same arithmetic, spelled out
+            return hostplan.plan_synthesis_numpy(lf0s, fs, N, b_const_rate, b_voi_ap_win)
+
+    def _mt_device(self, noise, noise_mode, mt_total):
+        """Reference noise (np.random.uniform from numpy's GLOBAL generator, magphase.py:883) for more than a few utterances
+        is continued on the device from numpy's own MT19937 state (mpx_noise_numpy_mt19937: the same samples, the state put
+        back advanced) -- the host draw is 4 ns per sample, 0.13 s per 128 utterances."""
+        return (noise_mode == "reference" and noise is None and mt_total >= (1 << 18)
+                and os.environ.get("MAGPHASE_MT_DEVICE", "1") != "0" and np.random.get_state()[0] == "MT19937")
+
+    def _host_noise(self, noise, ui, ns_len):
+        e = self.engine
+        if noise is not None:
+            v_ns = np.asarray(noise[ui], dtype=np.float64)
+            if v_ns.size != ns_len:
+                raise ValueError("noise length %d != ns_len %d" % (v_ns.size, ns_len))
+            return v_ns
+        if hasattr(e, "mt_sync"):
+            e.mt_sync()                                            # a deferred device state goes back first
+        return np.random.uniform(-1, 1, ns_len)                    # :883 (global numpy RNG, as the reference)
+
+    def _set_layout(self, frame_off, ns_len, out_len, tabs, noise, noise_mode):
+        """What both table builders derive from the planner's per-utterance results: frame_off int64[U + 1], ns_len /
+        out_len per utterance, tabs with v_shift / v_pm / voiced per frame.  Returns _mt_device's decision."""
+        # per-utterance views (v_shift / v_pm / v_voi: properties below) are cut from the batch tables on demand
+        self._tabs = tabs
+        self.frame_off = self._fo = np.asarray(frame_off, dtype=np.int64)
+        self.n_utts, self.total_frames = int(self.frame_off.size - 1), int(self.frame_off[-1])
+        self.ns_len = [int(x) for x in np.asarray(ns_len).tolist()]
+        self.out_len = [int(x) for x in np.asarray(out_len).tolist()]
+        self.out_off_host = np.concatenate(([0], np.cumsum(self.out_len))).astype(np.int64)
+        self.total_out = int(self.out_off_host[-1])
+        self.max_out_len = int(max(self.out_len))
+        self.voiced_host = np.asarray(tabs["voiced"]).astype(bool)
+        # bins from n_per on have no periodic component (the crossfade mask is exactly zero there): their phase rows are
+        # neither unwarped nor read
+        self.n_per = self._n_per()
+        return self._mt_device(noise, noise_mode, int(sum(self.ns_len)))
+
+    def _noise_seed_tables(self, noise_seeds):
+        """noise_mode='device': the seeds and the utterances' offsets into the noise, as items of a packed upload."""
+        seeds = np.arange(self.n_utts, dtype=np.uint64) if noise_seeds is None else np.asarray(noise_seeds).astype(np.uint64)
+        if seeds.size != self.n_utts:
+            raise ValueError("noise_seeds: one per utterance")
+        self.noise_seeds = seeds
+        self.noise_off_host = np.concatenate(([0], np.cumsum(self.ns_len))).astype(np.int64)
+        return [("noise_seeds_dev", seeds.view(np.int64), np.int64), ("noise_off_dev", self.noise_off_host, np.int64)]
+
+    def _host_noise_cat(self, noise):
+        return np.concatenate([self._host_noise(noise, ui, n) for ui, n in enumerate(self.ns_len)])
+
+    def _tables_prepared(self, p, noise, noise_mode, noise_seeds):
+        """Takes over a PreparedSynthesis (Engine.prepare_synthesis): two DMAs (coefficient rows, every table)."""
+        e, torch = self.engine, _torch()
+        self.mag_dim, self.phase_dim, self.n_rows = p.mag_dim, p.phase_dim, p.n_rows
+        F, U = p.total_frames, p.n_utts
+        mt_device = self._set_layout(p.frame_off, p.ns_len, p.out_len,
+                                     {"v_shift": p.v_shift, "v_pm": p.v_pm, "voiced": p.voiced_host}, noise, noise_mode)
+        self.n_runs, self.n_slots, self.runs_host = p.n_runs, p.n_slots, p.runs_host
+        slot, p.slot = p.slot, None
+        sd, dd, self._ready = e._slot_upload(slot, p.stage_bytes, p.desc_bytes)
+        sizes = {"utt_frame_off": U + 1, "tile_first": p.n_tiles1, "out_start": U, "out_off": U + 1,
+                 "runs": 56 * p.n_runs, "slot_off": p.n_slots + 1, "slot_runs": p.n_runs}
+        tmap = {np.int32: torch.int32, np.int64: torch.int64, np.float32: torch.float32, np.uint8: torch.uint8}
+        for (name, dt), off in zip(hostplan.SYNTH_TABLES, p.desc_off.tolist()):
+            n = sizes.get(name, F)
+            if name == "tile_first" and not self.unwarp_rows:
+                continue
+            setattr(self, name, dd[off:off + n * np.dtype(dt).itemsize].view(tmap[dt]))
+        if noise_mode == "device":
+            for k, t in e.to_device_packed(self._noise_seed_tables(noise_seeds)).items():
+                setattr(self, k, t)
+        elif not mt_device:
+            self.noise = e.to_device(self._host_noise_cat(noise), np.float32)
+        return sd.view(torch.float32), mt_device
+
+    def _tables_generic(self, utts, b_voi_ap_win, noise, noise_mode, noise_seeds, frames_per_run):
+        """The generic path: any array-like input, utterance by utterance in Python where the native planner declines.
+        One staged upload (coefficient rows) and one packed upload (every table)."""
+        e = self.engine
+        self.mag_dim = int(np.shape(utts[0][0])[1])
+        self.phase_dim = int(np.shape(utts[0][1])[1])
+        a_mag, a_real, a_imag, lf0s = [], [], [], []
+        nd = np.ndarray
+        for ui, (mml, rm, im, lf0) in enumerate(utts):
+            # the coefficient matrices go to the device as float32 whatever they arrive as: no float64 round trip here
+            # (a plan is built per launch of a corpus job: the usual case -- 2-D ndarrays -- skips the generic conversions)
+            if not (type(mml) is nd and type(rm) is nd and type(im) is nd and mml.ndim == 2 and rm.ndim == 2 and im.ndim == 2):
+                mml, rm, im = np.atleast_2d(np.asarray(mml)), np.atleast_2d(np.asarray(rm)), np.atleast_2d(np.asarray(im))
+            lf0 = np.atleast_1d(np.asarray(lf0, dtype=np.float64))
+            n_rows = mml.shape[0]
+            if rm.shape[0] != n_rows or im.shape[0] != n_rows or lf0.shape[0] != n_rows:
+                raise ValueError("utterance %d: mag / real / imag / lf0 have %d / %d / %d / %d frames"
+                                 % (ui, n_rows, rm.shape[0], im.shape[0], lf0.shape[0]))
+            if rm.shape[1] != im.shape[1]:
+                raise ValueError("utterance %d: real and imag have different dimensions" % ui)
+            if mml.shape[1] != self.mag_dim or rm.shape[1] != self.phase_dim:
+                # (stage_rows checks totals only: rows of another width whose totals happen to match would be copied flat,
+                # silently scrambled -- np.concatenate(axis=0, out=[rows x dim]) used to raise here)
+                raise ValueError("utterance %d: mag / phase dimensions %d / %d differ from the batch's %d / %d"
+                                 % (ui, mml.shape[1], rm.shape[1], self.mag_dim, self.phase_dim))
+            a_mag.append(mml), a_real.append(rm), a_imag.append(im), lf0s.append(lf0)
+        self.n_rows = int(sum(a.shape[0] for a in a_mag))
+
+        r = self._plan_tables(lf0s, b_voi_ap_win)
+        mt_device = self._set_layout(r["frame_off"], r["ns_len"], r["out_len"], r, noise, noise_mode)
+        starts = [int(x) for x in np.asarray(r["out_start"]).tolist()]
+        pm_rel = _FlatRows(np.asarray(r["pm_rel"]), r["frame_off"])
+        up = [("utt_frame_off", self.frame_off, np.int32)]   # (attribute, host array, dtype): ONE upload (to_device_packed)
+        # coefficient matrices: concatenated straight into the page-locked staging buffer, one DMA
+        n_m, n_p = self.n_rows * self.mag_dim, self.n_rows * self.phase_dim
+        stage = e.host_staging(n_m + 2 * n_p)
+        # (inline: on the helper thread -- Engine.background -- the launch loop of a generation job got 5 % SLOWER, the three
+        # calls' Python glue fights the constructor for the GIL; the analysis plan's single native copy gains 7 % there)
+        e.stage_rows(a_mag, stage[:n_m].reshape(self.n_rows, self.mag_dim))
+        e.stage_rows(a_real, stage[n_m:n_m + n_p].reshape(self.n_rows, self.phase_dim))
+        e.stage_rows(a_imag, stage[n_m + n_p:].reshape(self.n_rows, self.phase_dim))
+        if noise_mode == "device":
+            up += self._noise_seed_tables(noise_seeds)
+        elif not mt_device:
+            up.append(("noise", self._host_noise_cat(noise), np.float32))
+        up += [("npos", r["npos"], np.int64), ("nleft", r["nleft"], np.int32), ("nright", r["nright"], np.int32),
+               ("wtype", r["wtype"], np.int32), ("voiced", r["voiced"], np.int32)]
+        if self.unwarp_rows:   # frames of every 31-row tile of the coefficient matrix (mpx_mel_unwarp_rows)
+            self._check_rows_for_tiles(r["row0"], r["row1"])
+            up.append(("tile_first", np.searchsorted(r["row0"], 31 * np.arange((self.n_rows + 30) // 31 + 1), side="left"),
+                       np.int32))
+        up += [("row0", r["row0"], np.int32), ("row1", r["row1"], np.int32), ("rowt", r["rowt"], np.float32),
+               ("win_l", r["win_l"], np.int32), ("win_r", r["win_r"], np.int32), ("pm_rel", pm_rel.flat, np.int32),
+               ("out_start", np.asarray(starts), np.int32), ("out_off", self.out_off_host, np.int64)]
+        # OLA runs
+        n_slots = e.synth_comp_slots() if hasattr(e, "synth_comp_slots") else 1024
+        _plan_ola_runs(self, pm_rel, starts, self.out_len, self.out_off_host, self.fft_len, n_slots, frames_per_run, up,
+                       weights=e.synth_ola_slot_weights(comp=True) if hasattr(e, "synth_ola_slot_weights") else None)
+        coef = e.upload_staged(n_m + 2 * n_p)
+        for k, t in e.to_device_packed(up).items():
+            setattr(self, k, t)
+        return coef, mt_device
+
+    def _per_utt(self, key, cast=None):
+        r, fo = self._tabs, self._fo
+        out = [r[key][int(fo[u]):int(fo[u + 1])] for u in range(len(self.ns_len))]
+        return [cast(x) for x in out] if cast else out
+
+    @property
+    def v_shift(self):
+        """Per utterance: the frames' shifts in samples (magphase.py:862-868 / :2210-2215)."""
+        return self._per_utt("v_shift")
+
+    @property
+    def v_pm(self):
+        """Per utterance: the frames' epochs in samples (la.shift_to_pm, magphase.py:880)."""
+        return self._per_utt("v_pm")
+
+    @property
+    def v_voi(self):
+        """Per utterance: the frames' voicing decisions (magphase.py:847, :866)."""
+        return self._per_utt("voiced", lambda x: x.astype(bool))
+
+    @staticmethod
+    def _check_rows_for_tiles(r0, r1):
+        """What the tiled unwarp relies on: row0 ascending over the batch, row1 - row0 in {0, 1}."""
+        if r0.size and (np.any(np.diff(r0) < 0) or np.any((r1 - r0) < 0) or np.any((r1 - r0) > 1)):
+            raise ValueError("constant -> variable rate tables out of order")
+
+    @property
+    def gains(self):
+        """[(g_voiced, g_unvoiced)] per utterance (float64), fetched from the device on demand."""
+        if self._gains_dev is None:
+            return None
+        g = self._gains_dev.cpu().numpy()
+        return [(float(a), float(b)) for a, b in g]
+
+    def noise_gains(self, sums_host):
+        """magphase.py:902-906 (Q10) from the per-frame sums of (ln|Ns|)^2: two gains per utterance, float64."""
+        H = self.fft_len // 2 + 1
+        inv = np.ones(self.total_frames)
+        gains = []
+        for u in range(len(self.out_len)):
+            a, b = int(self.frame_off[u]), int(self.frame_off[u + 1])
+            s = np.asarray(sums_host[a:b], dtype=np.float64)
+            v = self.voiced_host[a:b]
+            g = []
+            for cls in (v, ~v):
+                ncls = int(np.sum(cls))
+                g.append(np.sqrt(np.exp(np.sum(s[cls]) / (ncls * (H - 2)))) if ncls else np.nan)
+                if ncls:
+                    inv[a:b][cls] = 1.0 / g[-1]
+            gains.append(tuple(g))
+        return inv
+
+    def _buffers(self):
+        """Work buffers of run(), allocated once per plan (the caching allocator makes a re-allocation per call cheap
+        but not free: ~1.6 GB of spectra + strips + per-frame scalars)."""
+        b = getattr(self, "_buf", None)
+        if b is None:
+            e, torch = self.engine, _torch()
+            H = self.fft_len // 2 + 1
+            ld = int(e.lib.mpx_spec_ld(H))
+            b = self._buf = dict(
+                ld=ld,
+                # unwarped spectra at the VARIABLE rate: one row per synthesis frame (mpx_mel_unwarp_rows interpolates)
+                spec=tuple(e.empty((self.total_frames, ld))[:, :H] for _ in range(3)),
+                sums=e.empty((self.total_frames,)),
+                inv_gain=e.empty((self.total_frames,)),
+                gains=torch.empty((self.n_utts, 2), dtype=torch.float64, device=e.device),
+                strips=e.empty((max(self.strip_floats, 1),)),
+            )
+            if self.per_phase_type != "magphase":
+                F = self.total_frames
+                b["ident"] = torch.arange(F, dtype=torch.int32, device=e.device)
+                b["zeros_t"] = torch.zeros(F, dtype=torch.float32, device=e.device)
+                b["spec_v"] = tuple(e.empty((F, ld))[:, :H] for _ in range(3))
+        return b
+
+    def _launch_noise_statistic(self, tab, buf, mark):
+        """The noise statistic of the utterances and buf["inv_gain"] from it; returns the stored noise spectra, or None."""
+        e, N = self.engine, self.fft_len
+        H = N // 2 + 1
+        sums, inv_gain = buf["sums"], buf["inv_gain"]
+        nspec = None
+        if N == 4096 and self.total_frames > 0 and self.noise_spectra:
+            nspec = buf.get("nspec")
+            if nspec is None:
+                nspec = buf["nspec"] = e.empty((int(e.lib.mpx_noise_spectra_floats(N, self.total_frames)),))
+        stats = (N, tab, self.noise, self.npos, self.nleft, self.nright, self.wtype, self.total_frames, sums)
+        if nspec is not None:
+            e.launch("mpx_noise_stats_spectra", *stats, nspec)
+        else:
+            e.launch("mpx_noise_stats", *stats)
+        mark("k_noise_stats")
+        # two gains per utterance (Q10): float64 reduction on the device, no host round trip
+        self._gains_dev = buf["gains"]
+        e.launch("mpx_noise_gains", sums, self.voiced, self.utt_frame_off, self.n_utts, H - 2, inv_gain, self._gains_dev)
+        mark("k_noise_gains")
+        return nspec
+
+    def run(self, out=None, keep=False, mark=None):
+        """mark: optional callable(name), called after every kernel launch has been enqueued (bench.py: HIP events)."""
+        e, N = self.engine, self.fft_len
+        H = N // 2 + 1
+        tab = e.tables(N)
+        mark = mark or (lambda name: None)
+        _wait_ready(self)
+        buf = self._buffers()
+        # unwarped spectra: internal matrices, rows 128-byte aligned (mpx_spec_ld: full-line stores of the MFMA unwarp)
+        ld = buf["ld"]
+        mag, real, imag = buf["spec"]
+        sums, strips, inv_gain = buf["sums"], buf["strips"], buf["inv_gain"]
+        pcm = out if out is not None else e.empty((self.total_out,))
+        magphase = self.per_phase_type == "magphase"
+        mark("start")
+        a_mag = self.a_mag
+        if self.apply_post_filter == "merlin":   # magphase.py:3262-3264
+            a_mag = e.post_filter_merlin(self.a_mag, self.fs)
+            mark("k_post_filter_merlin")
+        elif self.apply_post_filter:   # magphase.py:3259-3261
+            a_mag = e.post_filter(self.a_mag, self.fs)
+            mark("k_post_filter")
+        if self.unwarp_rows:   # constant -> variable rate inside the unwarp: one spectrum row per synthesis frame
+            e.launch("mpx_mel_unwarp_rows", self.total_frames, H, a_mag, self.mag_dim, self.u_mag, mag, self.a_real,
+                     self.a_imag, self.phase_dim, self.u_phase, real, imag, ld, self.row0, self.row1, self.rowt,
+                     self.n_rows, self.tile_first, self.voiced if magphase else None, self.n_per if magphase else 0)
+        else:                   # variable-rate features: rows == frames
+            e.launch("mpx_mel_unwarp", self.n_rows, H, a_mag, self.mag_dim, self.u_mag, mag, self.a_real, self.a_imag,
+                     self.phase_dim, self.u_phase, real, imag, ld)
+        mark("k_mel_unwarp_mfma")
+        # (the noise chain is independent of the unwarp, but a second HIP stream does not help: measured 3.13 vs
+        # 3.18 ms per step with 12-wave and 3.15 vs 3.16 with 8-wave noise workgroups -- the two grids do not co-run)
+        # "noise spectra once" (opt-in, MAGPHASE_NOISE_SPECTRA=store; N = 4096): the statistics launch
+        # stores every frame's noise spectrum and the synthesis launch loads it instead of a second transform --
+        # 17.4 KB per frame each way for the arithmetic of one forward FFT (measured: docs/LAB_NOTES.md, round 5)
+        nspec = self._launch_noise_statistic(tab, buf, mark)
+        if not magphase:
+            # periodic component's phase is not the transmitted one (magphase.py:933-938):
+            #   'min_phase': complex-cepstrum minimum phase of the magnitude, per frame
+            #   'linear'   : zero phase
+            if self.per_phase_type == "min_phase":
+                ident, spec_v = buf["ident"], buf["spec_v"]
+                e.launch("mpx_min_phase", N, tab, mag, ident, ident, buf["zeros_t"], self.total_frames, *spec_v, ld)
+                mark("k_min_phase")
+                mag, real, imag = spec_v
+            else:
+                real.fill_(1.0)
+                imag.fill_(0.0)
+        ola_args = (N, tab, mag, real, imag, self.noise, self.npos, self.nleft, self.nright, self.wtype, self.voiced,
+                    inv_gain, None, None, None, self.win_l, self.win_r, self.pm_rel, self.per_v, self.ap_v, self.ap_u,
+                    self.runs, self.n_runs, self.slot_off, self.slot_runs, self.n_slots, strips, pcm, ld,
+                    self.n_per if magphase else 0)
+        if nspec is not None:
+            e.launch("mpx_synthesis_compressed_ola_spectra", *ola_args, nspec)
+        else:
+            e.launch(self._ola_entry, *ola_args)
+        mark("k_synth_comp_pair")
+        e.ola_fixup(N, self, strips, pcm)
+        mark("k_ola_fixup")
+        if keep:
+            self.debug = dict(mag=mag, real=real, imag=imag, sums=sums)
+        return pcm
+
+
+class Type2SynthesisPlan(CompressedSynthesisPlan):
+    """
+    synthesis_from_compressed_type2 (magphase.py:1452-1597, the output filter excluded) for a batch of utterances: the
+    type-1 plan's tables, buffers and launch sequence with
+      * the grid's period as a parameter (const_rate_ms > 0; <= 0: the variable rate) and type 2's voicing rules on it
+        (hostplan.plan_synthesis_numpy(type2=True); the variable rate keeps the native planner, its arithmetic is type 1's),
+      * the phase coefficients extended to mag_dim columns and unwarped at alpha (hm.type2_phase_unwarp_matrix),
+      * the plain crossfade curves and the hf_slope line (hm.type2_synthesis_bin_curves),
+      * one noise gain per utterance, rms of the noise spectra over all frames and bins, from mpx_noise_power +
+        mpx_noise_rms (no transform) instead of mpx_noise_stats + mpx_noise_gains,
+      * the type-2 arm of the pair kernel (mpx_synthesis_compressed_type2_ola: signed real DC / Nyquist bins).
+    Constants are cached under keys of their own and the gain buffers belong to the plan: running a type-2 plan leaves
+    nothing behind that a type-1 plan on the same engine reads.
+    """
+    _n_per_key = "n_per_t2"
+    _ola_entry = "mpx_synthesis_compressed_type2_ola"
+
+    def __init__(self, engine, utts, fs, fft_len=None, hf_slope_coeff=1.0, b_voi_ap_win=True, const_rate_ms=-1.0,
+                 noise=None, frames_per_run=None, noise_mode="reference", noise_seeds=None, defer_rng=False):
+        self.const_rate_ms = float(const_rate_ms)
+        self.hf_slope_coeff = float(hf_slope_coeff)
+        const = self.const_rate_ms > 0.0
+        self._native_planner = not const
+        super().__init__(engine, utts, fs, fft_len=fft_len, b_voi_ap_win=b_voi_ap_win, b_const_rate=const, noise=noise,
+                         frames_per_run=frames_per_run, noise_mode=noise_mode, noise_seeds=noise_seeds,
+                         defer_rng=defer_rng, noise_spectra=False)
+        self._rms_dev = None
+
+    def _plan_tables(self, lf0s, b_voi_ap_win):
+        if not self.b_const_rate:
+            return super()._plan_tables(lf0s, b_voi_ap_win)
+        return hostplan.plan_synthesis_numpy(lf0s, self.fs, self.fft_len, True, b_voi_ap_win,
+                                             const_rate_ms=self.const_rate_ms, type2=True)
+
+    def _bin_curves_host(self):
+        return hm.type2_synthesis_bin_curves(self.fs, self.fft_len, self.hf_slope_coeff)
+
+    def _phase_and_curve_constants(self):
+        e, fs, N = self.engine, self.fs, self.fft_len
+        H, alpha = N // 2 + 1, hm.define_alpha(fs)
+        self.u_phase = e.constant(("u_phase_t2", self.phase_dim, self.mag_dim, H, float(alpha)),
+                                  lambda: hm.type2_phase_unwarp_matrix(self.phase_dim, self.mag_dim, H, alpha))
+        self.per_v, self.ap_v, self.ap_u = (
+            e.constant(("bin_curve_t2", k, int(fs), N, self.hf_slope_coeff), lambda k=k: self._bin_curves_host()[k])
+            for k in range(3))
+
+    @property
+    def gains(self):
+        """Type 2 has one gain per utterance: see rms."""
+        return None
+
+    @property
+    def rms(self):
+        """[rms_noise] per utterance (float64, magphase.py:1539), fetched from the device on demand."""
+        return None if self._rms_dev is None else [float(x) for x in self._rms_dev.cpu().numpy()]
+
+    def _buffers(self):
+        b = getattr(self, "_buf", None)
+        if b is None:
+            b = super()._buffers()
+            torch = _torch()
+            b["power"] = torch.empty((max(self.total_frames, 1),), dtype=torch.float64, device=self.engine.device)
+            b["rms"] = torch.empty((self.n_utts,), dtype=torch.float64, device=self.engine.device)
+        return b
+
+    def _launch_noise_statistic(self, tab, buf, mark):
+        e, N, power = self.engine, self.fft_len, buf["power"]
+        e.launch("mpx_noise_power", N, self.noise, self.npos, self.nleft, self.nright, self.wtype, self.total_frames, power)
+        mark("k_noise_power")
+        self._rms_dev = buf["rms"]
+        e.launch("mpx_noise_rms", N, power, self.utt_frame_off, self.n_utts, buf["inv_gain"], self._rms_dev)
+        mark("k_noise_rms")
+        return None
+
+
+# ======================================================================================================
+# compressed-feature analysis (magphase.py:2947-2988, 2490-2544)
+# ======================================================================================================
+class CompressedAnalysisPlan:
+    """
+    Lossless analysis plan + host tables for the mel warp of a batch (one sample rate).  run() = k_analysis ->
+    k_mel_warp, everything resident on the device; host fp64 does f0 / lf0 / constant-rate tables only.
+    """
+
+    def __init__(self, engine, utts, fft_len=None, mag_dim=60, phase_dim=10, b_const_rate=False, alpha_phase=None,
+                 b_mag_fbank_mel=False, prepared=None):
+        # prepared: see LosslessAnalysisPlan (Engine.prepare_analysis, e.g. from the planner thread)
+        self.engine = e = engine
+        self.lossless = plan = LosslessAnalysisPlan(engine, utts, fft_len=fft_len, prepared=prepared)
+        fs = self.fs = plan.fs[0]
+        if plan.fs.count(fs) != len(plan.fs):
+            raise ValueError("one sample rate per batch")
+        N = self.fft_len = plan.fft_len
+        H = N // 2 + 1
+        self.mag_dim, self.phase_dim, self.b_const_rate = int(mag_dim), int(phase_dim), bool(b_const_rate)
+        alpha = hm.define_alpha(fs)
+        a_ph = alpha if alpha_phase is None else alpha_phase
+        cf, _ = hm.define_crossfade_params(fs)
+        k_full = hm.get_num_full_mel_coeffs_from_num_phase_coeffs(cf, phase_dim, a_ph, fs)
+        self.w_mag, self._warp_name = e.warp_mag_matrix(mag_dim, H, alpha, b_mag_fbank_mel)
+        self.w_ph = e.constant(("w_ph", int(k_full), H, float(a_ph), int(phase_dim)),
+                               lambda: hm.warp_matrix(k_full, H, a_ph, nrows=phase_dim))
+        rows = None
+        if b_const_rate:
+            U = len(utts)
+            row0, row1, rowt, self.f0_out, self.out_off = hm.var_to_const_rate_batch(
+                [plan.v_shift[u] for u in range(U)], [plan.v_f0[u] for u in range(U)], plan.frame_off[:U], fs, 5.0)
+            rows = (row0, row1, rowt)
+        else:   # variable rate: output rows == frames (no row tables go to the device)
+            self.f0_out = plan.v_f0 if isinstance(plan.v_f0, _FlatRows) else list(plan.v_f0)
+            self.out_off = np.asarray(plan.frame_off, dtype=np.int64)
+        self.total_out_frames = int(self.out_off[-1])
+        if isinstance(self.f0_out, _FlatRows):
+            f0_cat = self.f0_out.flat
+        else:
+            f0_cat = np.concatenate(self.f0_out) if self.f0_out else np.zeros(0)
+        voi_dev = None if b_const_rate else getattr(plan, "voi_dev", None)   # already in the prepared tables' upload
+        items, tail = ([] if voi_dev is not None else [("voi", (f0_cat > 0).astype(np.float32), np.float32)]), []
+        # phase streams warped on the variable-rate rows, their 45 outputs interpolated afterwards (mpx_mel_warp_rows):
+        # the rows a voiced constant-rate frame interpolates from
+        self.phase_on_rows = bool(b_const_rate) and os.environ.get("MAGPHASE_WARP_PHASE_ROWS", "1") != "0"
+        if self.phase_on_rows:
+            voiced = f0_cat > 0
+            need = np.zeros(plan.total_frames, dtype=np.float32)
+            need[row0[voiced]] = 1.0
+            need[row1[voiced]] = 1.0
+            tail.append(("rows_in_use", need, np.float32))
+        # one H2D copy
+        if rows is not None:
+            (self.row0, self.row1, self.rowt), desc = _upload_rows(e, rows, head=items, tail=tail)
+        else:
+            self.row0 = self.row1 = self.rowt = None
+            desc = e.to_device_packed(items) if items else {}
+        self.voi = desc["voi"] if voi_dev is None else voi_dev
+        self.rows_in_use = desc.get("rows_in_use")
+        self._phase_tmp = None
+        # Variable frame rate: ONE fused kernel, the lossless features never reach HBM (mpx_analysis_compressed_fused;
+        # MAGPHASE_COMP_FUSED=0 keeps the staged pair k_analysis_f64 -> k_mel_warp_mfma).  The constant-rate path
+        # interpolates staged lossless rows, as the reference does (SURVEY.md 8d allows that staging).
+        fusable = (N in (2048, 4096) and self.mag_dim <= 64 and self.phase_dim <= 48
+                   and os.environ.get("MAGPHASE_COMP_FUSED", "1") != "0"
+                   and os.environ.get("MAGPHASE_COMP_ANALYSIS", "f64") != "f32")
+        self.fused = fusable and not b_const_rate
+        # Constant rate: the staged pair k_analysis_f64 -> k_mel_warp_mfma, which interpolates staged lossless rows as the
+        # reference does (SURVEY.md 8d allows that staging), or -- MAGPHASE_COMP_FUSED_CR=1 -- the same ONE kernel with the
+        # row interpolation inside (mpx_analysis_compressed_fused_cr: the magnitudes' operand rows are built per
+        # constant-rate frame, the phase streams are warped at the variable rate and finished by mpx_warp_phase_rows).
+        # Measured on configs[2] (round 6, bench.py configs2.analysis_one_kernel): HBM traffic of the analysis side 2.87 ->
+        # 0.37 GB, no 1.4 GB of staged rows -- and 1.38 ms instead of 0.98: opt-in.  (The filter-bank magnitudes take the
+        # logarithm AFTER the product: staged only.)
+        self.fused_cr = (fusable and b_const_rate and self.phase_on_rows and self._warp_name != "mpx_mel_warp_fbank"
+                         and self.total_out_frames > 0 and int(e.lib.mpx_analysis_compressed_fused_waves()) == 8
+                         and int(e.lib.mpx_analysis_compressed_fused_layout()) == 1
+                         and os.environ.get("MAGPHASE_COMP_FUSED_CR", "0") == "1")
+        self._cr_work = None
+        if self.fused or self.fused_cr:
+            nw = int(e.lib.mpx_analysis_compressed_fused_waves())
+            layout = int(e.lib.mpx_analysis_compressed_fused_layout())   # fragment order this build of the kernel reads
+            key = ("wpack", self._warp_name, int(mag_dim), int(k_full), int(phase_dim), H, float(alpha), float(a_ph), nw,
+                   layout)
+            if key not in e._tables:
+                wm = (hm.warp_fbank_matrix(mag_dim, H, alpha) if self._warp_name == "mpx_mel_warp_fbank"
+                      else hm.warp_matrix(mag_dim, H, alpha))
+                wph = hm.warp_matrix(k_full, H, a_ph, nrows=phase_dim)
+                wpack, whalf = hm.pack_warp_fused(wm, wph, N, n_waves=nw, layout=layout)
+                e._tables[key] = (e.to_device(wpack, np.float32), e.to_device(whalf, np.float32))
+            self.wpack, self.whalf = e._tables[key]
+
+    def _phase_rows_tmp(self):
+        """The two phase streams warped at the variable rate, allocated at the first run and kept."""
+        if self._phase_tmp is None:
+            e, shape = self.engine, (int(self.lossless.total_frames), self.phase_dim)
+            self._phase_tmp = (e.empty(shape), e.empty(shape))
+        return self._phase_tmp
+
+    def run(self, feats=None, out=None, mark=None):
+        e, pl, N = self.engine, self.lossless, int(self.fft_len)
+        H = N // 2 + 1
+        Fo, fbank = self.total_out_frames, 1 if self._warp_name == "mpx_mel_warp_fbank" else 0
+        mark = mark or (lambda name: None)
+        mark("start")
+        # float64 transform: the warp's log / division amplify an fp32 FFT's noise on weak bins (magphase_f64.hip)
+        precise = os.environ.get("MAGPHASE_COMP_ANALYSIS", "f64") != "f32"
+        _wait_ready(pl)
+
+        def outputs():   # called once per run, by the path taken: the staged path allocates its lossless rows first
+            return out if out is not None else (e.empty((Fo, self.mag_dim)), e.empty((Fo, self.phase_dim)),
+                                                e.empty((Fo, self.phase_dim)))
+
+        if self.fused:   # (feats, the staged path's lossless feature buffers, are not used)
+            out = outputs()
+            e.launch("mpx_analysis_compressed_fused", N, e.tables_f64(N), pl.sig, pl.pos, pl.left, pl.right,
+                     int(pl.total_frames), *e.hann_window_args(), self.wpack, self.whalf, self.mag_dim, self.phase_dim,
+                     self.voi, fbank, out[0], out[1], out[2])
+            mark("k_analysis_warp_fused")
+            return out
+        n_var = int(pl.total_frames)
+        if self.fused_cr:
+            out = outputs()
+            self._phase_rows_tmp()
+            if self._cr_work is None:
+                nbytes = int(e.lib.mpx_analysis_compressed_fused_cr_work_bytes(N, n_var))
+                self._cr_work = e.empty(((nbytes + 3) // 4,))
+            e.launch("mpx_analysis_compressed_fused_cr", N, e.tables_f64(N), pl.sig, pl.pos, pl.left, pl.right, n_var,
+                     *e.hann_window_args(), self.wpack, self.whalf, self.mag_dim, self.phase_dim, self.rows_in_use,
+                     self.row0, self.row1, self.rowt, int(Fo), out[0], *self._phase_tmp, self._cr_work)
+            mark("k_analysis_warp_fused_cr")
+            e.launch("mpx_warp_phase_rows", int(Fo), self.phase_dim, *self._phase_tmp, self.row0, self.row1, self.rowt,
+                     self.voi, out[1], out[2])
+            mark("k_warp_phase_rows")
+            return out
+        # (the phase rows nobody reads -- rows_in_use == 0 -- are not written either)
+        mag, real, imag = pl.run(out=feats, precise=precise, rows_in_use=self.rows_in_use if self.phase_on_rows else None)
+        mark("k_analysis_f64" if precise else "k_analysis")
+        out = outputs()
+        warp = (Fo, H, mag, real, imag, self.row0, self.row1, self.rowt, self.w_mag, self.mag_dim, self.w_ph, self.phase_dim,
+                self.voi, out[0], out[1], out[2], e.feat_ld(mag, real, imag))
+        if self.phase_on_rows:
+            e.launch("mpx_mel_warp_rows", *warp, fbank, n_var, self.rows_in_use, *self._phase_rows_tmp())
+        else:
+            e.launch(self._warp_name, *warp)
+        mark("k_mel_warp_mfma")
+        return out
+
+
+class Type2AnalysisPlan:
+    """
+    analysis_lossless_type2 (magphase.py:2793-2866) for a batch of utterances with epochs, (v_sig, fs, v_pm_sec, v_voi),
+    one fft_len.  A LosslessAnalysisPlan holds the signal and the one-period frame table (phase, f0, gain); this plan adds
+    the two-period half lengths of the same epochs (hostmath.two_period_frame_bounds: the magnitude frames), the voicing
+    of the gain and the float shifts of the unrounded epochs (hostmath.type2_shift).  Rows are those of the lossless plan:
+    utterance u's output is rows frame_off[u] + 1 .. frame_off[u + 1] (the reference drops row 0).
+    run(): k_analysis_f64 over the one-period frames (float64 transform: the mel warp of the compressed form reads the
+    phase, as in analysis_compressed), k_analysis_f64 over the two-period frames into the same magnitude rows (magnitudes
+    only: the phase rows keep the one-period values), k_frame_gain, k_true_envelope at 600 coefficients on those rows.
+    """
+
+    def __init__(self, engine, utts, fft_len=None):
+        self.engine = e = engine
+        utts = list(utts)
+        self.lossless = pl = LosslessAnalysisPlan(engine, utts, fft_len=fft_len)
+        N = self.fft_len = pl.fft_len
+        self.fs = list(pl.fs)
+        l2, r2, voi = [], [], []
+        self.v_f0, self.v_shift, self.long_frame_lens = [], [], []
+        for u, (_sig, fs, v_pm_sec, v_voi) in enumerate(utts):
+            n = int(pl.n_smpls[u])
+            pm_sec, vv = hm.clean_epochs(v_pm_sec, v_voi, check_len_smpls=n, fs=fs)
+            pm = np.asarray(pl.v_pm[u], dtype=np.int64)
+            if pm.size != vv.size:
+                raise RuntimeError("Type2AnalysisPlan: %d epochs planned, %d cleaned" % (pm.size, vv.size))
+            lft2, rgt2 = hm.two_period_frame_bounds(pm, n)
+            # the reference's warnings: the even-epoch frames, the odd ones (both incl. row 0), then the one-period ones
+            tot2 = lft2 + rgt2 + 1
+            self.long_frame_lens.append([int(x) for x in np.concatenate((tot2[0::2], tot2[1::2])) if x > N]
+                                        + list(pl.long_frame_lens[u]))
+            l2.append(lft2), r2.append(rgt2), voi.append((vv == 1).astype(np.float32))
+            self.v_f0.append(np.asarray(pl.v_f0[u], dtype=np.float64)[1:])
+            self.v_shift.append(hm.type2_shift(pm_sec * fs))
+        self.frame_off = np.asarray(pl.frame_off, dtype=np.int64)
+        F = self.total_frames = int(pl.total_frames)
+        cat = (lambda v, dt: np.concatenate(v).astype(dt) if v else np.zeros(0, dt))   # noqa: E731
+        t = e.to_device_packed([("left2", cat(l2, np.int64), np.int32), ("right2", cat(r2, np.int64), np.int32),
+                                ("voi", cat(voi, np.float32), np.float32),
+                                ("mag_only", np.zeros(F, dtype=np.float32), np.float32)])
+        self.left2, self.right2, self.voi, self.mag_only = t["left2"], t["right2"], t["voi"], t["mag_only"]
+        self.ld = int(e.lib.mpx_spec_ld(N // 2 + 1))   # one row pitch for the analysis rows and the envelope
+
+    def out_rows(self, u):
+        """Rows of utterance u in run()'s outputs: (first, end)."""
+        a, b = int(self.frame_off[u]), int(self.frame_off[u + 1])
+        return min(a + 1, b), b
+
+    def run(self, want_iters=False, forced_iters=None, gain_blocks_per_cu=0):
+        """-> (env, real, imag, gain, iters): float32 device rows [F x H] (one row pitch, self.ld; see out_rows), float64
+        device gain [F], int32 device passes per envelope row (want_iters / forced_iters) or None."""
+        e, torch = self.engine, _torch()
+        pl, N, F = self.lossless, self.fft_len, self.total_frames
+        H = N // 2 + 1
+        mag, real, imag, env = (e.empty((max(F, 1), self.ld)) for _ in range(4))
+        gain = torch.empty(max(F, 1), dtype=torch.float64, device=e.device)
+        iters = None
+        if want_iters or forced_iters is not None:
+            iters = torch.empty(max(F, 1), dtype=torch.int32, device=e.device)
+        feats = (mag[:F, :H], real[:F, :H], imag[:F, :H])
+        if F == 0:
+            return env[:0, :H], feats[1], feats[2], gain[:0], (iters[:0] if iters is not None else None)
+        pl.run(out=feats, precise=True)
+        # the two-period magnitudes overwrite the one-period ones (stream order); rows_in_use = 0: no phase row written
+        e.analysis_frames(N, pl.sig, pl.pos, self.left2, self.right2, out=feats, precise=True, rows_in_use=self.mag_only)
+        w = e.constant(("true_env_w", N, TYPE2_ENV_NCOEFFS, 0.7),
+                       lambda: hm.true_envelope_lifter(N, TYPE2_ENV_NCOEFFS, 0.7))
+        forced = None
+        if forced_iters is not None:
+            forced = e.to_device(np.asarray(forced_iters, dtype=np.int32).reshape(F), np.int32)
+        tk = torch.empty(1, dtype=torch.int32, device=e.device)
+        e.launch("mpx_frame_gain", N, pl.sig, pl.pos, pl.left, pl.right, self.voi, F, gain, int(gain_blocks_per_cu))
+        e.launch("mpx_true_envelope", N, e.tables(N), w, mag, self.ld, F, hm.TRUE_ENV_IN_TYPES.index("abs"),
+                 TYPE2_ENV_THRES_DB, hm.TRUE_ENV_MAX_ITERS, env, self.ld, iters, forced, tk)
+        del mag   # (stream-ordered: the allocator reuses the magnitude rows after the envelope)
+        return env[:F, :H], feats[1], feats[2], gain[:F], iters
+
+
+class Type2CompressedAnalysisPlan:
+    """
+    analysis_compressed_type2 (magphase.py:3123-3196): a Type2AnalysisPlan, then format_for_modelling's two warps on its
+    device rows (mpx_mel_warp, alpha_phase = alpha), which read their input rows through row tables: at the variable
+    rate every row but row 0 of each utterance, at const_rate_ms > 0 the rows and weights of the grid
+    arange(step, pm[-1], step) over the float epochs cumsum(v_shift), f0 / voicing by hostmath._const_rate_f0_voi
+    (hostmath.var_to_const_rate_batch).  The gain is interpolated on the host (float64, as the reference).
+    """
+
+    def __init__(self, engine, utts, fft_len=None, mag_dim=60, phase_dim=45, const_rate_ms=-1.0):
+        self.engine = e = engine
+        self.t2 = t2 = Type2AnalysisPlan(engine, utts, fft_len=fft_len)
+        fs = self.fs = t2.fs[0] if t2.fs else None
+        if t2.fs.count(fs) != len(t2.fs):
+            raise ValueError("one sample rate per batch")
+        N = self.fft_len = t2.fft_len
+        H = N // 2 + 1
+        self.mag_dim, self.phase_dim = int(mag_dim), int(phase_dim)
+        self.const_rate_ms = float(const_rate_ms)
+        alpha = hm.define_alpha(fs)
+        cf, _ = hm.define_crossfade_params(fs)
+        k_full = hm.get_num_full_mel_coeffs_from_num_phase_coeffs(cf, phase_dim, alpha, fs)
+        self.w_mag = e.constant(("w_mag", self.mag_dim, H, float(alpha)), lambda: hm.warp_matrix(mag_dim, H, alpha))
+        self.w_ph = e.constant(("w_ph", int(k_full), H, float(alpha), self.phase_dim),
+                               lambda: hm.warp_matrix(k_full, H, alpha, nrows=phase_dim))
+        self.const = self.const_rate_ms > 0.0
+        spans = [t2.out_rows(u) for u in range(len(t2.v_f0))]
+        self.grid = []
+        if self.const:
+            self.grid = [np.cumsum(s) for s in t2.v_shift]   # la.shift_to_pm (magphase.py:3130)
+            row0, row1, rowt, self.f0_out, self.out_off = hm.var_to_const_rate_batch(
+                t2.v_shift, t2.v_f0, [a for a, _b in spans], fs, self.const_rate_ms)
+        else:   # every row but row 0 of each utterance, weight 0
+            row0 = np.concatenate([np.arange(a, b, dtype=np.int64) for a, b in spans] or [np.zeros(0, np.int64)])
+            row1, rowt, self.f0_out = row0, np.zeros(row0.size), list(t2.v_f0)
+            self.out_off = np.concatenate(([0], np.cumsum([f.size for f in self.f0_out]))).astype(np.int64)
+        self.total_out_frames = int(self.out_off[-1])
+        f0_cat = np.concatenate(self.f0_out) if self.f0_out else np.zeros(0)
+        (self.row0, self.row1, self.rowt), d = _upload_rows(
+            e, (row0, row1, rowt), head=[("voi", (f0_cat > 0).astype(np.float32), np.float32)])
+        self.voi = d["voi"]
+
+    def run(self):
+        """-> ((mag [Fo x mag_dim], real, imag [Fo x phase_dim]) float32 device, gain float64 device [F]: the type-2
+        plan's rows, see Type2AnalysisPlan.out_rows)."""
+        e = self.engine
+        H = self.fft_len // 2 + 1
+        env, real, imag, gain, _ = self.t2.run()
+        Fo = self.total_out_frames
+        out = (e.empty((max(Fo, 1), self.mag_dim)), e.empty((max(Fo, 1), self.phase_dim)),
+               e.empty((max(Fo, 1), self.phase_dim)))
+        if Fo:
+            e.launch("mpx_mel_warp", Fo, H, env, real, imag, self.row0, self.row1, self.rowt, self.w_mag, self.mag_dim,
+                     self.w_ph, self.phase_dim, self.voi, out[0], out[1], out[2], e.feat_ld(env, real, imag))
+        return tuple(o[:Fo] for o in out), gain

@@ -153,6 +153,35 @@ def test_model_matches_the_reference_golden():
             assert np.max(np.abs(v_syn - g[key])) <= 1e-9 * np.max(np.abs(g[key]))
 
 
+def test_batch_tables_against_the_reference_golden():
+    """hostmath.var_to_const_rate_batch (the three constant-rate analysis plans' tables) on golden G14's utterances as
+    one batch: f0 is the reference's, exactly; the rows, offset by each utterance's base, interpolate the oracle's
+    variable-rate rows to the reference's stored columns (the bound of model.golden_rows)."""
+    g = np.load(GOLDEN)
+    tags, cr, step = [str(t) for t in g["tags"]], float(g["const_rate_ms"]), int(g["col_step"])
+    fs_list = [int(g[t + "_fs"]) for t in tags]
+    o = [orc.analysis_lossless_from_epochs(syn.pcm_to_float(g[t + "_pcm"]), fs, g[t + "_pm_sec"], g[t + "_voi"])
+         for t, fs in zip(tags, fs_list)]
+    bases = np.concatenate(([0], np.cumsum([x[0].shape[0] for x in o])))
+    row0, row1, rowt, f0, out_off = hm.var_to_const_rate_batch([x[5] for x in o], [x[3] for x in o], bases[:-1], fs_list, cr)
+    assert row0.dtype == row1.dtype == out_off.dtype == np.int64 and rowt.dtype == np.float64
+    assert np.array_equal(out_off, np.concatenate(([0], np.cumsum([g[t + "_f0"].size for t in tags]))))
+    for u, t in enumerate(tags):
+        a, b = int(out_off[u]), int(out_off[u + 1])
+        assert np.array_equal(f0[u], g[t + "_f0"])
+        lo, hi, w = hm.var_to_const_rate_table(np.cumsum(o[u][5]), cr, fs_list[u])
+        assert np.array_equal(row0[a:b], lo + bases[u]) and np.array_equal(row1[a:b], hi + bases[u])
+        assert np.array_equal(rowt[a:b], w)
+        mag = o[u][0][:, ::step]
+        lerp = (1 - w[:, None]) * mag[row0[a:b] - bases[u]] + w[:, None] * mag[row1[a:b] - bases[u]]
+        pk = np.max((1 - w[:, None]) * o[u][0][lo] + w[:, None] * o[u][0][hi], axis=1, keepdims=True)
+        assert np.max(np.abs(lerp - g[t + "_mag"]) / pk) <= 1e-6
+    one = hm.var_to_const_rate_batch([o[0][5]], [o[0][3]], [0], fs_list[0], cr)   # one rate for the batch: a scalar fs
+    assert np.array_equal(one[0], row0[:int(out_off[1])]) and np.array_equal(one[3][0], f0[0])
+    empty = hm.var_to_const_rate_batch([], [], [], 16000, cr)
+    assert empty[0].size == 0 and empty[3] == [] and np.array_equal(empty[4], [0])
+
+
 def test_argument_errors_before_any_device_call():
     pcm, pm_sec, voi = syn.make_utterance(1, dur_s=0.2, fs=16000)
     utt = (syn.pcm_to_float(pcm), 16000, pm_sec, voi)

@@ -39,7 +39,6 @@ def main():
     import torch
     from scipy import signal
 
-    from magphase_amd import _lib
     from magphase_amd import engine as em
     from magphase_amd import synthetic as syn
 
@@ -75,15 +74,13 @@ def main():
     mark = lambda name: None   # noqa: E731
 
     def t1_stat():
-        p1._launch_noise_statistic(e.stream_ptr(), tab, b1, mark)
+        p1._launch_noise_statistic(tab, b1, mark)
 
     def t2_stat():
-        p2._launch_noise_statistic(e.stream_ptr(), tab, b2, mark)
+        p2._launch_noise_statistic(tab, b2, mark)
 
     def power():
-        _lib.check(e.lib.mpx_noise_power(e.stream_ptr(), N, p2.noise.data_ptr(), p2.npos.data_ptr(), p2.nleft.data_ptr(),
-                                         p2.nright.data_ptr(), p2.wtype.data_ptr(), p2.total_frames,
-                                         b2["power"].data_ptr()), "mpx_noise_power")
+        e.launch("mpx_noise_power", N, p2.noise, p2.npos, p2.nleft, p2.nright, p2.wtype, p2.total_frames, b2["power"])
 
     def t1_chain():
         e.output_hpf(p1.run(), p1.out_off_host, fs)
