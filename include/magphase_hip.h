@@ -679,6 +679,45 @@ int mpx_post_filter_merlin(void* stream, const float* mag_mel_log, int64_t n_fra
 int mpx_bw_probe_shapes(void);
 int mpx_bw_probe(void* stream, int32_t mode, float* a, float* b, int64_t n_floats);
 
+/*
+ * Feature rows that already live in device memory, gathered into a plan's dense float32 buffers (csrc/magphase_pack.hip,
+ * k_rows_pack): what Engine.stage_rows + upload_staged do for host arrays, for rows an acoustic model left on the GPU.
+ * One launch serves n_utts utterances and n_streams <= 3 streams (mag | real | imag) of different widths.
+ *
+ * Descriptor table: n_streams * n_utts entries of mpx_pack_desc, 32 bytes each, entry [s * n_utts + u] = utterance u of
+ * stream s:
+ *   base        DEVICE pointer to element [0, 0] of the utterance's rows (any element alignment)
+ *   row_stride  elements between the starts of two rows (>= 0; the column stride is 1)
+ *   dtype       element type code: MPX_PACK_F32 0, MPX_PACK_F16 1, MPX_PACK_BF16 2, MPX_PACK_F64 3
+ *   n_rows      rows of this utterance (0: nothing is read, base may be NULL)
+ *   out_row0    its first row in the stream's output; within a stream the entries follow one another:
+ *               out_row0[0] = 0, out_row0[u + 1] = out_row0[u] + n_rows[u], and the last one ends at rows_s
+ * table: the DEVICE copy the kernel reads; table_host: the same bytes in HOST memory, checked in full before the launch
+ * (type codes, sizes, the tiling above), so that every store lands inside [0, rows_s) x [0, width_s) of its stream.
+ *
+ * Stream s: out_s DEVICE float32, row r at out_s + r * ld_s (ld_s >= width_s: width_s for the dense `coef` layout of the
+ * compressed synthesis plan, Engine.empty_feats' pitch for lossless features), rows_s rows of width_s columns.  Arguments
+ * of streams >= n_streams are ignored.
+ * Conversion: f16 and bf16 widen exactly; f64 narrows round-to-nearest-even (numpy's astype(float32)); f32 is copied bit
+ * for bit (NaN payloads, -0).  n_utts == 0 and utterances without rows launch nothing.
+ * Returns MPX_ERR_ARG for a null table with n_utts > 0, an unknown type code, negative sizes or a table that does not
+ * tile the outputs -- all detected on the host, without a device.
+ */
+#define MPX_PACK_F32 0
+#define MPX_PACK_F16 1
+#define MPX_PACK_BF16 2
+#define MPX_PACK_F64 3
+typedef struct {
+    const void* base;
+    int64_t row_stride;
+    int32_t dtype;
+    int32_t n_rows;
+    int64_t out_row0;
+} mpx_pack_desc;
+int mpx_rows_pack(void* stream, const mpx_pack_desc* table, const mpx_pack_desc* table_host, int32_t n_utts,
+                  int32_t n_streams, float* out0, int32_t width0, int64_t ld0, int64_t rows0, float* out1, int32_t width1,
+                  int64_t ld1, int64_t rows1, float* out2, int32_t width2, int64_t ld2, int64_t rows2);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Host-side file helpers of the batch scripts (csrc/magphase_host.cpp; no device work, no stream).  Called from the
  * reader / writer threads of iobatch.py: the FFI call drops the interpreter lock, so reading, computing and writing overlap.

@@ -98,6 +98,7 @@ PROTOTYPES = {
     "mpx_output_hpf": (i32, [vp] * 4 + [i32, i64] + [vp] * 7),
     "mpx_bw_probe": (i32, [vp, i32, vp, vp, i64]),
     "mpx_bw_probe_shapes": (i32, []),
+    "mpx_rows_pack": (i32, [vp, vp, vp, i32, i32] + [vp, i32, i64, i64] * 3),
     "mpx_post_filter_merlin": (i32, [vp, vp, i64, i32] + [vp] * 4 + [i32, f64, vp, f64] + [vp] * 5),
 }
 SYMBOLS = tuple(PROTOTYPES)

@@ -353,12 +353,13 @@ class Engine:
             raise
         return views, HostTicket(self.out_ring(), slot, ev, list(tensors))
 
-    def output_pcm16(self, y, out_off_host, norm=0.98, async_out=False):
+    def output_pcm16(self, y, out_off_host, norm=0.98, async_out=False, return_device=False):
         """
         libaudio.py:352-365 on the device (mpx_pcm16): y float64 or float32 [total] (utterances at out_off_host) ->
         int16 numpy [total], each utterance peak-normalised to `norm` (None: no normalisation) and rounded like
         libsndfile's PCM_16 conversion -- bit-identical to la.write_audio_file's samples.
         async_out: returns (view of a page-locked ring slot, HostTicket) without waiting for the copy.
+        return_device: stops before the download -- the int16 device tensor [total].
         """
         torch = _torch()
         out_off_host = np.asarray(out_off_host, dtype=np.int64)
@@ -369,6 +370,8 @@ class Engine:
         out = torch.empty(max(total, 1), dtype=torch.int16, device=self.device)
         self.launch("mpx_pcm16", y, 1 if y.dtype == torch.float64 else 0, d_off, int(lens.size),
                     int(lens.max()) if lens.size else 0, float(norm) if norm is not None else 0.0, peaks, out)
+        if return_device:
+            return out[:total]
         with torch.cuda.device(self.device):
             if async_out:   # non-blocking copy into a page-locked ring slot; the consumer waits on the ticket
                 slot, buf = self.out_ring().acquire(2 * max(total, 1))
@@ -620,6 +623,93 @@ class Engine:
                 t.record_stream(cur)
             st["events"][st["cur"]] = ev
         return t
+
+    # ------------------------------------------------------------------ feature rows that are already on the device
+    def is_device_rows(self, x):
+        """True for a torch tensor that lives on this engine's device."""
+        torch = _torch()
+        return torch.is_tensor(x) and x.device == self.device
+
+    def pack_rows(self, streams, outs):
+        """
+        The rows of a batch gathered into dense device matrices by ONE mpx_rows_pack launch (k_rows_pack): streams is a
+        list (at most three) of per-utterance lists of [rows x width] tensors on this device -- float32 / float16 /
+        bfloat16 / float64, any row stride (column slices of one wide tensor are read where they lie; a non-unit column
+        stride is made contiguous first); outs the streams' float32 device matrices [sum of rows x width] (unit column
+        stride, any row pitch: the `coef` slices of a compressed synthesis plan, empty_feats matrices).  Returns outs.
+        Host arrays (or CPU tensors) among the utterances are uploaded one by one and packed with the rest: the slow
+        mixed case -- a batch of host arrays belongs in stage_rows / upload_staged, one copy and one DMA.
+        The launch goes to torch's current stream of the device, like every other: rows produced on that stream need no
+        synchronisation.
+        """
+        torch = _torch()
+        if len(streams) != len(outs):
+            raise ValueError("pack_rows: one output per stream")
+        dev = []
+        for st in streams:
+            row = []
+            for t in st:
+                if not self.is_device_rows(t):
+                    if torch.is_tensor(t):
+                        if t.device.type != "cpu":
+                            raise ValueError("pack_rows: tensor on %s, the engine runs on %s" % (t.device, self.device))
+                        t = t.detach()
+                        t = (t.float() if t.dtype in (torch.float16, torch.bfloat16) else t).numpy()
+                    a = np.atleast_2d(np.asarray(t))
+                    t = self.to_device(a, np.float32) if a.size else self.empty(a.shape)
+                elif t.dim() == 2 and t.shape[1] > 1 and t.stride(1) != 1:
+                    t = t.contiguous()
+                row.append(t.detach())
+            dev.append(row)
+        table, widths, rows = hm.rows_pack_table(dev)
+        args = []
+        for s, o in enumerate(outs):
+            if (not self.is_device_rows(o) or o.dtype != torch.float32 or o.dim() != 2
+                    or (o.shape[1] > 1 and o.stride(1) != 1)):
+                raise ValueError("pack_rows: output %d must be a 2-D float32 matrix on %s with unit column stride"
+                                 % (s, self.device))
+            if int(o.shape[0]) != rows[s] or (rows[s] and int(o.shape[1]) != widths[s]):
+                raise ValueError("pack_rows: output %d is %d x %d, its stream has %d rows of %d"
+                                 % (s, o.shape[0], o.shape[1], rows[s], widths[s]))
+            ld = max(int(o.stride(0)), int(o.shape[1])) if o.shape[0] > 1 else int(o.shape[1])
+            args += [o, int(o.shape[1]), ld, rows[s]]
+        args += [None, 0, 0, 0] * (3 - len(outs))
+        if table.size and sum(rows):
+            d_table = self.to_device(table.view(np.uint8), np.uint8)
+            self.launch("mpx_rows_pack", d_table, table.ctypes.data, len(dev[0]), len(dev), *args)
+        return outs
+
+    def lf0_to_host(self, lf0s, what="v_lf0"):
+        """The lf0 vectors of a batch as float64 numpy arrays.  Host arrays are converted as always; device tensors
+        (float32 / bfloat16 / float64 -- float16 cannot hold the unvoiced marker -1e10) are widened to float64 on the
+        device (exact) and come down in ONE copy: the values of tensor.double().cpu().numpy()."""
+        torch = _torch()
+        out = [None] * len(lf0s)
+        idx = [k for k, v in enumerate(lf0s) if torch.is_tensor(v)]
+        for k, v in enumerate(lf0s):
+            if not torch.is_tensor(v):
+                out[k] = np.atleast_1d(np.asarray(v, dtype=np.float64))
+        if idx:
+            for k in idx:
+                hm.check_feature_tensor(lf0s[k], "%s of utterance %d" % (what, k), lf0=True)
+                if lf0s[k].device != self.device and lf0s[k].device.type != "cpu":
+                    raise ValueError("%s of utterance %d is on %s, the engine runs on %s"
+                                     % (what, k, lf0s[k].device, self.device))
+            ts = [lf0s[k].detach().reshape(-1) for k in idx]
+            on_dev = [t for t in ts if t.device == self.device]
+            if on_dev:
+                with torch.cuda.device(self.device):
+                    same = len(set(t.dtype for t in on_dev)) == 1
+                    cat = torch.cat(on_dev).double() if same else torch.cat([t.double() for t in on_dev])
+                    flat = cat.cpu().numpy()
+            o = 0
+            for k, t in zip(idx, ts):
+                if t.device == self.device:
+                    out[k] = flat[o:o + t.numel()]
+                    o += t.numel()
+                else:
+                    out[k] = t.double().numpy()
+        return out
 
     # ------------------------------------------------------------------ prepared launches (native planners, planner thread)
     def host_threads(self, nbytes=0, big=32):

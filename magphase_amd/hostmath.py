@@ -164,6 +164,69 @@ OLA_RUN_DTYPE = np.dtype([("frame_begin", "<i4"), ("frame_end", "<i4"), ("x0", "
                           ("fix_hi", "<i4"), ("pad", "<i4"), ("out_base", "<i8"), ("strip_off", "<i8")])
 
 
+# numpy record layout of the C struct mpx_pack_desc (include/magphase_hip.h), 32 bytes, and its element type codes
+ROWS_PACK_DTYPE = np.dtype([("base", "<u8"), ("row_stride", "<i8"), ("dtype", "<i4"), ("n_rows", "<i4"),
+                            ("out_row0", "<i8")])
+ROWS_PACK_CODES = {"torch.float32": 0, "torch.float16": 1, "torch.bfloat16": 2, "torch.float64": 3}
+
+
+def check_feature_tensor(t, name, lf0=False):
+    """Argument check of a torch tensor given where the batch API takes a feature matrix (lf0: the lf0 vector): float32,
+    float16, bfloat16 or float64 -- integer, bool and complex tensors are refused, and so is a float16 lf0 (the unvoiced
+    marker -1e10 is not representable in float16).  Needs no device."""
+    if str(t.dtype) not in ROWS_PACK_CODES:
+        raise ValueError("%s: dtype %s is not supported (float32, float16, bfloat16 or float64)" % (name, t.dtype))
+    if lf0 and str(t.dtype) == "torch.float16":
+        raise ValueError("%s: a float16 lf0 cannot hold the unvoiced marker -1e10 (float32, bfloat16 or float64)" % name)
+    if lf0 and t.dim() != 1:
+        raise ValueError("%s: must be 1-D, got %d-D" % (name, t.dim()))
+    if not lf0 and t.dim() != 2:
+        raise ValueError("%s: must be 2-D [rows x width], got %d-D" % (name, t.dim()))
+
+
+def rows_pack_table(streams):
+    """
+    The descriptor table of mpx_rows_pack: streams is a list (at most three) of lists of 2-D tensors, streams[s][u] =
+    the rows of utterance u in stream s, unit column stride, float32 / float16 / bfloat16 / float64.  A pure function of
+    the tensors' shapes, strides, dtypes and data_ptr()s (CPU tensors serve as well as device ones).
+    Returns (table, widths, rows): a ROWS_PACK_DTYPE array of len(streams) * U entries, entry [s * U + u], the utterances
+    of a stream one after the other in its output; per stream the row width and the total number of rows.
+    """
+    if not 0 < len(streams) <= 3:
+        raise ValueError("rows_pack_table: one to three streams")
+    U = len(streams[0])
+    if any(len(st) != U for st in streams):
+        raise ValueError("rows_pack_table: every stream needs one tensor per utterance")
+    table = np.zeros(len(streams) * U, dtype=ROWS_PACK_DTYPE)
+    widths, rows = [], []
+    for s, st in enumerate(streams):
+        width, row0 = None, 0
+        for u, t in enumerate(st):
+            code = ROWS_PACK_CODES.get(str(t.dtype))
+            if code is None:
+                raise ValueError("rows_pack_table: stream %d, utterance %d: dtype %s (float32, float16, bfloat16 or float64)"
+                                 % (s, u, t.dtype))
+            if t.dim() != 2:
+                raise ValueError("rows_pack_table: stream %d, utterance %d: %d-D, expected [rows x width]" % (s, u, t.dim()))
+            n, w = int(t.shape[0]), int(t.shape[1])
+            if width is not None and w != width:
+                raise ValueError("rows_pack_table: stream %d, utterance %d: %d columns, the stream has %d" % (s, u, w, width))
+            width = w
+            if w > 1 and n > 0 and int(t.stride(1)) != 1:
+                raise ValueError("rows_pack_table: stream %d, utterance %d: column stride %d (must be 1)"
+                                 % (s, u, int(t.stride(1))))
+            if n >= 1 << 31:
+                raise ValueError("rows_pack_table: stream %d, utterance %d: too many rows" % (s, u))
+            e = table[s * U + u]
+            e["base"] = int(t.data_ptr()) if n and w else 0
+            e["row_stride"] = int(t.stride(0)) if n > 1 else w   # (the stride of a single row is never used)
+            e["dtype"], e["n_rows"], e["out_row0"] = code, n, row0
+            row0 += n
+        widths.append(int(width or 0))
+        rows.append(int(row0))
+    return table, widths, rows
+
+
 def _run_cuts(rel, N, target):
     """
     Frame indices at which one utterance's frames are cut into runs of about ``target`` frames, such that only ADJACENT

@@ -32,6 +32,39 @@ _WARN_LONG = ("fft_len (%d) is shorter than the current detected frame length (%
               "This issue is not very critical, but if it occurs often "
               "(e.g., more than 3 times per utterance), please increase de FFT length.")
 
+_SYN_NAMES = ("m_mag_mel_log", "m_real_mel", "m_imag_mel", "v_lf0")
+_LOSSLESS_NAMES = ("m_mag", "m_real", "m_imag")
+
+
+def _tensor_inputs(utts, names, lf0_at=None):
+    """
+    torch tensors among the feature arguments of a batch (names: the tuple positions that may hold one).  Checked without
+    a device: float32 / float16 / bfloat16 / float64 only, 2-D (the lf0 vector at position lf0_at: 1-D, not float16) --
+    ValueError naming the argument otherwise.  CPU tensors become host arrays (float16 / bfloat16 widened to float32:
+    exact) and take the host path.  Returns (utts, True when a tensor of another device remains): a batch without
+    tensors comes back as it is.
+    """
+    import sys
+
+    torch = sys.modules.get("torch")
+    if torch is None or not any(issubclass(t, torch.Tensor) for t in {type(x) for u in utts for x in u}):
+        return utts, False
+    out, on_dev = [], False
+    for i, u in enumerate(utts):
+        u = list(u)
+        for k, name in enumerate(names[:len(u)]):
+            x = u[k]
+            if not torch.is_tensor(x):
+                continue
+            hm.check_feature_tensor(x, "utts[%d]: %s" % (i, name), lf0=(k == lf0_at))
+            if x.device.type == "cpu":
+                x = x.detach()
+                u[k] = (x.float() if x.element_size() == 2 else x).numpy()
+            else:
+                on_dev = True
+        out.append(tuple(u))
+    return out, on_dev
+
 
 def set_epoch_provider(fn):
     """fn(wav_file) -> (v_pm_sec, v_voi) or None.  Replaces the REAPER call of magphase.py:2875-2876."""
@@ -274,7 +307,11 @@ def synthesis_from_lossless_batch(feats, engine=None):
     """
     Batched magphase.py:1759-1776.  feats: list of (m_mag, m_real, m_imag, v_f0, fs), all with the same
     number of bins.  Returns a list of float64 numpy signals.
+    m_mag / m_real / m_imag may be torch tensors on the engine's device (float32 / float16 / bfloat16 / float64, any
+    row stride): they are gathered on the device (Engine.pack_rows); one float32 utterance is taken without a copy.  CPU
+    tensors are treated as host arrays.  Launches go to torch's current stream of the engine's device.
     """
+    feats, _on_dev = _tensor_inputs(feats, _LOSSLESS_NAMES)
     engine = engine or get_engine()
     H = int(np.shape(feats[0][0])[1])
     fft_len = 2 * (H - 1)
@@ -286,24 +323,29 @@ def synthesis_from_lossless_batch(feats, engine=None):
 
 def _feats_cat_device(engine, feats, H):
     """The mag / real / imag matrices of a batch, each stream as ONE device float32 matrix (engine.empty_feats pitch):
-    a one-utterance float32 device tensor is taken as it is, host arrays go through pinned staging in one DMA."""
+    a one-utterance float32 device tensor is taken as it is, host arrays go through pinned staging in one DMA, device
+    tensors (float32 / float16 / bfloat16 / float64, any row stride) are gathered by ONE mpx_rows_pack launch for all
+    the streams that hold any (Engine.pack_rows; host arrays among them are uploaded one by one: the slow mixed case)."""
     torch = __import__("torch")
     rows = np.concatenate(([0], np.cumsum([int(np.shape(f[0])[0]) for f in feats])))
-    cat = []
+    for u, f in enumerate(feats):
+        for k in range(3):
+            if torch.is_tensor(f[k]) and f[k].device != engine.device:
+                raise ValueError("feats[%d]: %s is on %s, the engine runs on %s"
+                                 % (u, _LOSSLESS_NAMES[k], f[k].device, engine.device))
+    cat, packed = [None] * 3, []
     for k in range(3):   # one device matrix per stream (engine.empty_feats)
         if len(feats) == 1 and torch.is_tensor(feats[0][k]) and feats[0][k].dtype == torch.float32:
-            cat.append(feats[0][k])
+            cat[k] = feats[0][k]
             continue
         if not any(torch.is_tensor(f[k]) for f in feats):   # host arrays: narrowed into pinned staging, one DMA
-            buf = engine.feats_cat_to_device([f[k] for f in feats], H)
-            if buf is not None:
-                cat.append(buf)
+            cat[k] = engine.feats_cat_to_device([f[k] for f in feats], H)
+            if cat[k] is not None:
                 continue
-        buf = engine.empty_feats(int(rows[-1]), H)
-        for u, f in enumerate(feats):
-            part = f[k] if torch.is_tensor(f[k]) else torch.from_numpy(np.ascontiguousarray(f[k], dtype=np.float32))
-            buf[int(rows[u]):int(rows[u + 1])].copy_(part)
-        cat.append(buf)
+        cat[k] = engine.empty_feats(int(rows[-1]), H)
+        packed.append(k)
+    if packed:
+        engine.pack_rows([[f[k] for f in feats] for k in packed], [cat[k] for k in packed])
     return cat
 
 
@@ -404,6 +446,7 @@ def synthesis_from_lossless_const_rate_batch(feats, const_rate_ms=5.0, engine=No
     feats = list(feats)
     if not feats:
         return []
+    feats, _on_dev = _tensor_inputs(feats, _LOSSLESS_NAMES)
     H = _const_rate_synthesis_check(feats)
     f0_list = [np.asarray(f[3].cpu() if hasattr(f[3], "cpu") else f[3], dtype=np.float64) for f in feats]
     fs_list = [f[4] for f in feats]
@@ -689,8 +732,20 @@ def _output_hpf(v_syn_sig, fs):
 def synthesis_from_compressed_batch(utts, fs, fft_len=None, b_voi_ap_win=True, b_const_rate=False, alpha_phase=None,
                                     b_out_hpf=True, noise=None, engine=None, per_phase_type='magphase',
                                     b_post_filter=False, b_fbank_mel=False, noise_mode='reference', noise_seeds=None,
-                                    pcm16_norm=False, async_out=False, defer_rng=False, prepared=None):
+                                    pcm16_norm=False, async_out=False, defer_rng=False, prepared=None,
+                                    return_device=False):
     """Batched synthesis_from_compressed; utts: list of (m_mag_mel_log, m_real_mel, m_imag_mel, v_lf0).
+    Device features: the three matrices may be torch tensors on the engine's device (an acoustic model's output) --
+    float32 / float16 / bfloat16 / float64, any row stride (column slices of one [F x 151] tensor are read where they
+    lie, a non-unit column stride is made contiguous first); they are gathered on the device (Engine.pack_rows,
+    mpx_rows_pack), not staged through the host.  v_lf0 may be a device tensor too (not float16): the lf0 vectors of the
+    batch come down in one copy, the frame tables are host arithmetic.  CPU tensors are treated as host arrays; tensors
+    of another device, integer / bool / complex tensors and `prepared` together with tensors raise ValueError.  Host
+    arrays mixed into a device batch are uploaded one by one (slow).
+    return_device: the signals stay on the device -- a list of per-utterance views of the PCM buffer: float64 after the
+    output high-pass, float32 without it, int16 with pcm16_norm.  Not with async_out.
+    Streams: every launch goes to torch's CURRENT stream of the engine's device; inputs produced on that stream and
+    outputs consumed on it need no further synchronisation.
     defer_rng: reference noise only -- numpy's advanced generator state stays on the device between calls; the caller owes
     engine.mt_sync() before numpy's global generator is used again (iobatch does this for a corpus run).
     async_out (with pcm16_norm): returns (signals, ticket) -- the int16 signals are views of a page-locked buffer the
@@ -705,6 +760,12 @@ def synthesis_from_compressed_batch(utts, fs, fft_len=None, b_voi_ap_win=True, b
     prepared: the host side of THIS batch built ahead of time (engine.prepare_async("synthesis", utts, fs, fft_len=...,
     b_voi_ap_win=..., b_const_rate=...).result(): the planner thread prepares launch i + 1 while this thread enqueues
     launch i; None: prepared here)."""
+    if return_device and async_out:
+        raise ValueError("return_device and async_out exclude each other (async_out is a download)")
+    checked, _on_dev = _tensor_inputs(utts, _SYN_NAMES, lf0_at=3)
+    if checked is not utts and prepared is not None:
+        raise ValueError("prepared= was built from host arrays: it cannot be combined with tensor inputs")
+    utts = checked
     engine = engine or get_engine()
     plan = CompressedSynthesisPlan(engine, utts, fs, fft_len=fft_len, b_voi_ap_win=b_voi_ap_win,
                                    b_const_rate=b_const_rate, alpha_phase=alpha_phase, noise=noise,
@@ -713,6 +774,10 @@ def synthesis_from_compressed_batch(utts, fs, fft_len=None, b_voi_ap_win=True, b
     pcm_dev = plan.run()
     if b_out_hpf:   # magphase.py:981-995, float64 on the device (engine.output_hpf); _output_hpf is the host form
         pcm_dev = engine.output_hpf(pcm_dev, plan.out_off_host, fs)
+    if return_device:
+        if pcm16_norm is not False:
+            pcm_dev = engine.output_pcm16(pcm_dev, plan.out_off_host, norm=pcm16_norm, return_device=True)
+        return [pcm_dev[int(plan.out_off_host[u]):int(plan.out_off_host[u + 1])] for u in range(len(utts))]
     if pcm16_norm is not False and async_out:
         pcm, ticket = engine.output_pcm16(pcm_dev, plan.out_off_host, norm=pcm16_norm, async_out=True)
         return [pcm[plan.out_off_host[u]:plan.out_off_host[u + 1]] for u in range(len(utts))], ticket
@@ -766,7 +831,7 @@ def synthesis_from_acoustic_modelling(in_feats_dir, filename_token, out_syn_dir,
 # compressed-feature analysis
 # ======================================================================================================
 def analysis_compressed_batch(utts, fft_len=None, mag_dim=60, phase_dim=10, b_const_rate=False, alpha_phase=None,
-                              engine=None, as_float32=False, async_out=False, prepared=None):
+                              engine=None, as_float32=False, async_out=False, prepared=None, return_device=False):
     """
     Batched magphase.py:2947-2988 for utterances with epochs: utts = list of (v_sig, fs, v_pm_sec, v_voi), one
     sample rate per call.  Lossless analysis (k_analysis) stays on the device; the mel warp runs on it directly.
@@ -775,7 +840,13 @@ def analysis_compressed_batch(utts, fft_len=None, mag_dim=60, phase_dim=10, b_co
     is still copying into; ticket.wait() before reading them, ticket.release() when done (engine.HostTicket).
     prepared: the host side of THIS batch built ahead of time (engine.prepare_async("analysis", utts, fft_len).result():
     the planner thread prepares launch i + 1 while this thread enqueues launch i; None: prepared here).
+    return_device: the three matrices stay on the device -- float32 row views of the plan's output (the values
+    as_float32 downloads), for a training loop that extracts features on the fly; v_lf0_smth, v_shift, fs and fft_len are
+    host values as always.  Not with async_out.  The launches go to torch's CURRENT stream of the engine's device: work
+    that consumes the matrices on that stream needs no further synchronisation.
     """
+    if return_device and async_out:
+        raise ValueError("return_device and async_out exclude each other (async_out is a download)")
     engine = engine or get_engine()
     if len(utts) == 0:   # nothing to do (the per-utterance loop of the reference would run zero times)
         from .engine import HostTicket
@@ -792,6 +863,8 @@ def analysis_compressed_batch(utts, fft_len=None, mag_dim=60, phase_dim=10, b_co
         if not as_float32:
             raise ValueError("async_out needs as_float32")
         (h_mag, h_real, h_imag), ticket = engine.to_host_f32_async(list(plan.run()))
+    elif return_device:
+        h_mag, h_real, h_imag = plan.run()
     else:
         h_mag, h_real, h_imag = ((engine.to_host_f32 if as_float32 else engine.to_host_f64)(t_) for t_ in plan.run())
     res = []
@@ -1072,7 +1145,7 @@ def _type2_synthesis_check(utts, fs, fft_len, hf_slope_coeff):
 
 def synthesis_from_compressed_type2_batch(utts, fs, fft_len=None, hf_slope_coeff=1.0, b_voi_ap_win=True,
                                           const_rate_ms=-1.0, noise=None, noise_mode='reference', noise_seeds=None,
-                                          engine=None, pcm16_norm=False, defer_rng=False):
+                                          engine=None, pcm16_norm=False, defer_rng=False, return_device=False):
     """
     Batched synthesis_from_compressed_type2 (magphase.py:1452-1606); utts: list of (m_mag_mel_log, m_real_mel,
     m_imag_mel, v_lf0) as analysis_compressed_type2 returns them, one sample rate per call.  const_rate_ms > 0: the rows
@@ -1081,17 +1154,30 @@ def synthesis_from_compressed_type2_batch(utts, fs, fft_len=None, hf_slope_coeff
     reference's elliptic high-pass (order 4, 60 Hz).  noise, noise_mode, noise_seeds, pcm16_norm and defer_rng as in
     synthesis_from_compressed_batch.  Returns a list of float64 signals (int16 with pcm16_norm).  Engine:
     Type2SynthesisPlan.
+    Device features and return_device as in synthesis_from_compressed_batch: the matrices (and v_lf0) may be tensors on
+    the engine's device; with return_device the signals are float64 (int16 with pcm16_norm) views of the device PCM
+    buffer.  Device lf0 vectors come to the host first (one copy), so every argument check, the finite-lf0 check
+    included, still runs before the first kernel.  Launches go to torch's current stream of the engine's device.
     """
     const_rate_ms = _type2_rate(const_rate_ms)
     utts = list(utts)
     if not utts:
         return []
+    utts, on_dev = _tensor_inputs(utts, _SYN_NAMES, lf0_at=3)
+    if on_dev:
+        engine = engine or get_engine()
+        if all(len(u) == 4 for u in utts):   # (device lf0 comes down for the checks below; a malformed tuple raises there)
+            utts = [tuple(u[:3]) + (l,) for u, l in zip(utts, engine.lf0_to_host([u[3] for u in utts]))]
     _type2_synthesis_check(utts, fs, fft_len, hf_slope_coeff)
     engine = engine or get_engine()
     plan = Type2SynthesisPlan(engine, utts, fs, fft_len=fft_len, hf_slope_coeff=hf_slope_coeff,
                               b_voi_ap_win=b_voi_ap_win, const_rate_ms=const_rate_ms, noise=noise,
                               noise_mode=noise_mode, noise_seeds=noise_seeds, defer_rng=defer_rng)
     pcm_dev = engine.output_hpf(plan.run(), plan.out_off_host, fs, design="ellip60")   # magphase.py:1599-1604
+    if return_device:
+        if pcm16_norm is not False:
+            pcm_dev = engine.output_pcm16(pcm_dev, plan.out_off_host, norm=pcm16_norm, return_device=True)
+        return [pcm_dev[int(plan.out_off_host[u]):int(plan.out_off_host[u + 1])] for u in range(len(utts))]
     if pcm16_norm is not False:
         pcm = engine.output_pcm16(pcm_dev, plan.out_off_host, norm=pcm16_norm)
     else:

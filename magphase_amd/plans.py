@@ -18,6 +18,27 @@ def _torch():
     return torch
 
 
+def _is_tensor(x):
+    """torch.is_tensor without importing torch for what cannot be one (a tensor's class lives in the torch package)."""
+    return type(x).__module__.startswith("torch") and _torch().is_tensor(x)
+
+
+def _rows_or_array(engine, x, name):
+    """One coefficient matrix of a synthesis batch that is not a plain 2-D ndarray: a tensor on the engine's device stays
+    what it is (checked: a float type, 2-D; a non-unit column stride made contiguous), a CPU tensor becomes a host array
+    (float16 / bfloat16 widened to float32: exact), a tensor elsewhere is an error; anything else goes through numpy."""
+    if not _is_tensor(x):
+        return np.atleast_2d(np.asarray(x))
+    hm.check_feature_tensor(x, name)
+    if x.device.type == "cpu":
+        x = x.detach()
+        return (x.float() if x.element_size() == 2 else x).numpy()
+    if not (hasattr(engine, "is_device_rows") and engine.is_device_rows(x)):
+        raise ValueError("%s is on %s, the engine runs on %s" % (name, x.device, getattr(engine, "device", None)))
+    x = x.detach()
+    return x if x.shape[1] <= 1 or x.stride(1) == 1 else x.contiguous()
+
+
 TYPE2_ENV_NCOEFFS = 600   # la.true_envelope(..., ncoeffs=600, thres_db=0.1) of analysis_lossless_type2 (magphase.py:2829)
 TYPE2_ENV_THRES_DB = 0.1
 
@@ -612,6 +633,9 @@ class CompressedSynthesisPlan:
         self.unwarp_rows = self.b_const_rate or os.environ.get("MAGPHASE_UNWARP_ROWS_VAR", "1") != "0"
         # the native whole-launch planner (Engine.prepare_synthesis; `prepared`: built ahead, e.g. on the planner thread) takes
         # the plain case: ndarray coefficient matrices, the default run planner
+        if prepared is not None and any(_is_tensor(x) for utt in utts for x in utt):
+            prepared.release()
+            raise ValueError("prepared= was built from host arrays: it cannot be combined with tensor inputs")
         if (prepared is None and frames_per_run is None and self._native_planner and hasattr(e, "prepare_synthesis")
                 and not os.environ.get("MAGPHASE_OLA_FRAMES_PER_RUN") and os.environ.get("MAGPHASE_NATIVE_PREPARE", "1") != "0"):
             prepared = e.prepare_synthesis(utts, fs, fft_len=fft_len, b_voi_ap_win=b_voi_ap_win, b_const_rate=b_const_rate,
@@ -760,12 +784,23 @@ class CompressedSynthesisPlan:
         self.phase_dim = int(np.shape(utts[0][1])[1])
         a_mag, a_real, a_imag, lf0s = [], [], [], []
         nd = np.ndarray
+        # Coefficient matrices that are tensors on the engine's device (an acoustic model's output) stay there: the three
+        # streams are gathered into a fresh device `coef` by one mpx_rows_pack launch (Engine.pack_rows) -- no host staging,
+        # no upload.  Host arrays in such a batch are uploaded one by one and packed with the rest (the slow mixed case).
+        # lf0 always comes to the host (the frame tables are float64 host arithmetic): device vectors in ONE copy.
+        on_dev = lf0_tensors = False
         for ui, (mml, rm, im, lf0) in enumerate(utts):
             # the coefficient matrices go to the device as float32 whatever they arrive as: no float64 round trip here
             # (a plan is built per launch of a corpus job: the usual case -- 2-D ndarrays -- skips the generic conversions)
             if not (type(mml) is nd and type(rm) is nd and type(im) is nd and mml.ndim == 2 and rm.ndim == 2 and im.ndim == 2):
-                mml, rm, im = np.atleast_2d(np.asarray(mml)), np.atleast_2d(np.asarray(rm)), np.atleast_2d(np.asarray(im))
-            lf0 = np.atleast_1d(np.asarray(lf0, dtype=np.float64))
+                mml, rm, im = (_rows_or_array(e, x, "utterance %d: %s" % (ui, n_))
+                               for x, n_ in ((mml, "m_mag_mel_log"), (rm, "m_real_mel"), (im, "m_imag_mel")))
+                on_dev = on_dev or any(type(x) is not nd for x in (mml, rm, im))
+            if type(lf0) is not nd and _is_tensor(lf0):
+                hm.check_feature_tensor(lf0, "utterance %d: v_lf0" % ui, lf0=True)
+                lf0_tensors = True     # (brought down after the loop, all of them in one copy)
+            else:
+                lf0 = np.atleast_1d(np.asarray(lf0, dtype=np.float64))
             n_rows = mml.shape[0]
             if rm.shape[0] != n_rows or im.shape[0] != n_rows or lf0.shape[0] != n_rows:
                 raise ValueError("utterance %d: mag / real / imag / lf0 have %d / %d / %d / %d frames"
@@ -779,6 +814,8 @@ class CompressedSynthesisPlan:
                                  % (ui, mml.shape[1], rm.shape[1], self.mag_dim, self.phase_dim))
             a_mag.append(mml), a_real.append(rm), a_imag.append(im), lf0s.append(lf0)
         self.n_rows = int(sum(a.shape[0] for a in a_mag))
+        if lf0_tensors:
+            lf0s = e.lf0_to_host(lf0s)
 
         r = self._plan_tables(lf0s, b_voi_ap_win)
         mt_device = self._set_layout(r["frame_off"], r["ns_len"], r["out_len"], r, noise, noise_mode)
@@ -787,12 +824,13 @@ class CompressedSynthesisPlan:
         up = [("utt_frame_off", self.frame_off, np.int32)]   # (attribute, host array, dtype): ONE upload (to_device_packed)
         # coefficient matrices: concatenated straight into the page-locked staging buffer, one DMA
         n_m, n_p = self.n_rows * self.mag_dim, self.n_rows * self.phase_dim
-        stage = e.host_staging(n_m + 2 * n_p)
-        # (inline: on the helper thread -- Engine.background -- the launch loop of a generation job got 5 % SLOWER, the three
-        # calls' Python glue fights the constructor for the GIL; the analysis plan's single native copy gains 7 % there)
-        e.stage_rows(a_mag, stage[:n_m].reshape(self.n_rows, self.mag_dim))
-        e.stage_rows(a_real, stage[n_m:n_m + n_p].reshape(self.n_rows, self.phase_dim))
-        e.stage_rows(a_imag, stage[n_m + n_p:].reshape(self.n_rows, self.phase_dim))
+        if not on_dev:
+            stage = e.host_staging(n_m + 2 * n_p)
+            # (inline: on the helper thread -- Engine.background -- the launch loop of a generation job got 5 % SLOWER, the
+            # three calls' Python glue fights the constructor for the GIL; the analysis plan's single native copy gains 7 %)
+            e.stage_rows(a_mag, stage[:n_m].reshape(self.n_rows, self.mag_dim))
+            e.stage_rows(a_real, stage[n_m:n_m + n_p].reshape(self.n_rows, self.phase_dim))
+            e.stage_rows(a_imag, stage[n_m + n_p:].reshape(self.n_rows, self.phase_dim))
         if noise_mode == "device":
             up += self._noise_seed_tables(noise_seeds)
         elif not mt_device:
@@ -810,7 +848,13 @@ class CompressedSynthesisPlan:
         n_slots = e.synth_comp_slots() if hasattr(e, "synth_comp_slots") else 1024
         _plan_ola_runs(self, pm_rel, starts, self.out_len, self.out_off_host, self.fft_len, n_slots, frames_per_run, up,
                        weights=e.synth_ola_slot_weights(comp=True) if hasattr(e, "synth_ola_slot_weights") else None)
-        coef = e.upload_staged(n_m + 2 * n_p)
+        if on_dev:
+            coef = e.empty((max(n_m + 2 * n_p, 1),))
+            e.pack_rows([a_mag, a_real, a_imag], [coef[:n_m].view(self.n_rows, self.mag_dim),
+                                                  coef[n_m:n_m + n_p].view(self.n_rows, self.phase_dim),
+                                                  coef[n_m + n_p:n_m + 2 * n_p].view(self.n_rows, self.phase_dim)])
+        else:
+            coef = e.upload_staged(n_m + 2 * n_p)
         for k, t in e.to_device_packed(up).items():
             setattr(self, k, t)
         return coef, mt_device
