@@ -241,6 +241,42 @@ int mpx_rows_lerp(void* stream, int32_t n_bins, const float* src_mag, const floa
                   float* dst_mag, float* dst_real, float* dst_imag, int64_t ld_dst);
 
 /*
+ * Backward pass of mpx_synthesis_lossless_ola / mpx_synthesis_lossless_ola_lerp (magphase.py:1759-1776, ola :34-62): from
+ * grad_out = dL/d pcm_out (float32 [total_out], the utterances where the forward wrote them) the gradients with respect to
+ * the rows of mag / real / imag.  irfft and the overlap-add are linear, so frame f needs only the fft_len gradient samples
+ * that lie under it: sample n of its window is grad_out[grad_pos[f] + n], read for grad_lo[f] <= n < grad_hi[f] and zero
+ * elsewhere (the part of the frame inside its own utterance's kept output; hostmath.lossless_backward_table builds the
+ * three tables from the plan: grad_pos = out_off[u] + pm_rel[f] - out_start[u]).  Reads are also clamped to
+ * [0, total_out) on the device, whatever the tables say.  Per frame: one forward FFT of the window rotated by fft_len/2,
+ * gX_k = (c_k / fft_len) G_k (c_k = 2, 1 at bins 0 and fft_len/2, whose imaginary parts are dropped), and with
+ * u = (real + j imag) / den, den = |real + j imag| (1 where that is 0), d = Re(conj(u) gX):
+ *     grad_mag = d,   grad_real = (mag / den) (Re gX - Re u d),   grad_imag = (mag / den) (Im gX - Im u d).
+ * mag / real / imag (row pitch ld) are the forward's inputs.  row0 / row1 / row_t: all null (frame f reads row f) or the
+ * forward's row tables (frame f reads fma(x[row1[f]] - x[row0[f]], row_t[f], x[row0[f]]), the forward's own arithmetic);
+ * either way the gradient rows are per FRAME: grad_X + f * ld_grad, [n_frames x fft_len/2 + 1] -- with row tables
+ * mpx_rows_lerp_adjoint folds them back onto the constant-rate rows.  A null grad_X is not computed; all three null
+ * launches nothing.  Every element of a non-null grad_X is written exactly once: no atomics, deterministic.
+ */
+int mpx_synthesis_lossless_backward(void* stream, int fft_len, const void* tables, const float* grad_out,
+                                    int64_t total_out, const int64_t* grad_pos, const int32_t* grad_lo,
+                                    const int32_t* grad_hi, int64_t n_frames, const float* mag, const float* real,
+                                    const float* imag, int64_t ld, const int32_t* row0, const int32_t* row1,
+                                    const float* row_t, float* grad_mag, float* grad_real, float* grad_imag,
+                                    int64_t ld_grad);
+
+/*
+ * Adjoint of the row interpolation out[f] = fma(x[row1[f]] - x[row0[f]], row_t[f], x[row0[f]]):
+ *     dst_X[r] = sum over f with row0[f] == r of (1 - row_t[f]) src_X[f] + sum over f with row1[f] == r of row_t[f] src_X[f]
+ * for r < n_rows (a frame with row0 == row1 == r weighs exactly 1).  ranges: int32 [n_rows x 4] = (a0, a1, b0, b1) per
+ * row, the frames with row0 == r are [a0, a1), those with row1 == r are [b0, b1) (hostmath.lerp_adjoint_table; the row
+ * tables are non-decreasing, so both sets are contiguous); row_t [frames].  One wavefront per row sums in ascending frame
+ * order: deterministic, no atomics; a row no frame reads gets zeros.  A null dst_X (with any src_X) is skipped.
+ */
+int mpx_rows_lerp_adjoint(void* stream, int32_t n_bins, const float* src_mag, const float* src_real,
+                          const float* src_imag, int64_t ld_src, const int32_t* ranges, const float* row_t,
+                          int64_t n_rows, float* dst_mag, float* dst_real, float* dst_imag, int64_t ld_dst);
+
+/*
  * Copy synthesis in one launch: analysis_lossless (magphase.py:2869-2906: windowing :74-119, analysis_with_del_comp_from_pm
  * :266-334, compute_lossless_feats :457-476) followed by synthesis_from_lossless (:1759-1776, ola :34-62) on the same
  * frames, as demos/demo_copy_synthesis_lossless.py:44-50 calls them back to back.  Frame f is cut out of `sig` exactly as

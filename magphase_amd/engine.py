@@ -1418,6 +1418,42 @@ class Engine:
                     out[2], self.feat_ld(*out))
         return out
 
+    def synthesis_lossless_backward(self, fft_len, grad_out, plan, mag, real, imag, need=(True, True, True), rows=None):
+        """mpx_synthesis_lossless_backward: grad_out float32 [plan.total_out] (contiguous) = dL/d(the plan's waveform),
+        plan: LosslessSynthesisPlan, mag / real / imag: the forward's rows -> (g_mag, g_real, g_imag), per-FRAME gradient
+        rows [plan.total_frames x H] (None where need[k] is false: not computed).  rows = (row0, row1, rowt): the forward ran
+        with row tables (synthesis_lossless_ola_lerp); rows_lerp_adjoint folds the result back onto the table's rows."""
+        H = int(fft_len) // 2 + 1
+        nfr = int(plan.total_frames)
+        if int(grad_out.numel()) != int(plan.total_out) or grad_out.dtype != _torch().float32 or not grad_out.is_contiguous():
+            raise ValueError("synthesis_lossless_backward: grad_out must be a contiguous float32 [%d]" % plan.total_out)
+        out = tuple(self.empty_feats(nfr, H) if n else None for n in need)
+        if nfr == 0 or not any(need):
+            return out
+        pos, lo, hi = plan.backward_tables()
+        r0, r1, rt = rows if rows is not None else (None, None, None)
+        first = next(o for o in out if o is not None)   # (empty_feats: one pitch for all)
+        ld_g = self.feat_ld(first, first, first)
+        self.launch("mpx_synthesis_lossless_backward", int(fft_len), self.tables(fft_len), grad_out, int(plan.total_out), pos,
+                    lo, hi, nfr, mag, real, imag, self.feat_ld(mag, real, imag), r0, r1, rt, out[0], out[1], out[2], ld_g)
+        return out
+
+    def rows_lerp_adjoint(self, src, ranges, rowt, n_rows):
+        """mpx_rows_lerp_adjoint: src = (g_mag, g_real, g_imag) per-frame rows (None: stream not wanted), ranges int32
+        [n_rows x 4] (hostmath.lerp_adjoint_table) and rowt on the device -> the gradients of the n_rows table rows, a
+        tuple with None where src has None.  Rows no frame reads are zero."""
+        have = [s for s in src if s is not None]
+        if not have:
+            return (None, None, None)
+        H = int(have[0].shape[1])
+        out = tuple(self.empty_feats(int(n_rows), H) if s is not None else None for s in src)
+        if int(n_rows) == 0:
+            return out
+        first = next(o for o in out if o is not None)
+        self.launch("mpx_rows_lerp_adjoint", H, src[0], src[1], src[2], self.feat_ld(have[0], have[0], have[0]),
+                    ranges, rowt, int(n_rows), out[0], out[1], out[2], self.feat_ld(first, first, first))
+        return out
+
     def roundtrip_lossless_ola(self, fft_len, plan_a, plan_s, feats, strips, pcm_out):
         """Copy synthesis in one launch (mpx_roundtrip_lossless_ola): plan_a's frames are analysed, their feature rows
         written to feats = (mag, real, imag) and overlap-added by plan_s' runs (a LosslessSynthesisPlan built for this

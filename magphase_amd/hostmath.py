@@ -793,6 +793,56 @@ def const_to_variable_rows(v_voi_c, v_locs, const_rate_ms, fs):
     return lo.astype(np.int64), hi.astype(np.int64), t, v_voi
 
 
+def lerp_adjoint_table(row0, row1, rowt, n_rows):
+    """
+    Frame ranges of the adjoint of out[f] = (1 - rowt[f]) rows[row0[f]] + rowt[f] rows[row1[f]] (mpx_rows_lerp_adjoint):
+    int32 [n_rows x 4] = (a0, a1, b0, b1) per row r -- the frames with row0 == r are [a0, a1), those with row1 == r are
+    [b0, b1).  Both tables must be non-decreasing (they are, within an utterance and across the utterances of a batch,
+    whose rows follow one another), so each set is contiguous; a row no frame reads gets two empty ranges.  Pure index
+    arithmetic: no torch, no GPU.
+    """
+    row0 = np.asarray(row0, dtype=np.int64).reshape(-1)
+    row1 = np.asarray(row1, dtype=np.int64).reshape(-1)
+    n_rows = int(n_rows)
+    if row0.size != row1.size or np.size(rowt) != row0.size:
+        raise ValueError("lerp_adjoint_table: row0, row1 and rowt must have one length")
+    if n_rows < 0 or row0.size >= 2 ** 31:
+        raise ValueError("lerp_adjoint_table: n_rows < 0 or too many frames")
+    for name, r in (("row0", row0), ("row1", row1)):
+        if r.size and (r.min() < 0 or r.max() >= n_rows):
+            raise ValueError("lerp_adjoint_table: %s outside [0, %d)" % (name, n_rows))
+        if np.any(np.diff(r) < 0):
+            raise ValueError("lerp_adjoint_table: %s must be non-decreasing" % name)
+    rows = np.arange(n_rows, dtype=np.int64)
+    out = np.empty((n_rows, 4), dtype=np.int32)
+    out[:, 0] = np.searchsorted(row0, rows, side="left")
+    out[:, 1] = np.searchsorted(row0, rows, side="right")
+    out[:, 2] = np.searchsorted(row1, rows, side="left")
+    out[:, 3] = np.searchsorted(row1, rows, side="right")
+    return out
+
+
+def lossless_backward_table(pm_rel, frame_off, out_start, out_len, out_off, fft_len):
+    """
+    Where every frame of a lossless synthesis batch finds its gradient samples (mpx_synthesis_lossless_backward).  The
+    forward is out_u[t] = sum_i frame_i[t + out_start[u] - pm_rel[i]] for 0 <= t < out_len[u] (ola_plan), so sample n of
+    frame i receives the gradient of t = pm_rel[i] - out_start[u] + n when that lies in [0, out_len[u]) and nothing
+    otherwise.  pm_rel: the frames' positions, concatenated (utterance u: frame_off[u] .. frame_off[u + 1]); out_off[u]:
+    the utterance's offset in the gradient buffer.  Returns (pos int64[F] = index of sample 0 in the buffer -- may lie
+    outside it --, lo, hi int32[F]: the samples lo <= n < hi are read).
+    """
+    pm_rel = np.asarray(pm_rel, dtype=np.int64).reshape(-1)
+    frame_off = np.asarray(frame_off, dtype=np.int64)
+    n_fr = np.diff(frame_off)
+    if frame_off.size < 1 or int(frame_off[-1]) != pm_rel.size:
+        raise ValueError("lossless_backward_table: frame_off does not cover pm_rel")
+    rep = lambda v: np.repeat(np.asarray(v, dtype=np.int64)[:n_fr.size], n_fr)   # noqa: E731
+    t0 = pm_rel - rep(out_start)
+    lo = np.clip(-t0, 0, int(fft_len))
+    hi = np.maximum(np.clip(rep(out_len) - t0, 0, int(fft_len)), lo)
+    return rep(out_off) + t0, lo.astype(np.int32), hi.astype(np.int32)
+
+
 def _const_to_variable_scan_scipy(v_shift_c_rate, frm_rate_ms, fs):
     """The constant -> variable rate scan (magphase.py:1426-1449) written like the reference: one scipy interp1d call per
     step (8 us each).  hostplan._const_to_variable_scan is the native form the tests compare with this one."""

@@ -303,22 +303,43 @@ def analysis_lossless(wav_file, fft_len=None, out_dir=None):
 # ======================================================================================================
 # lossless synthesis
 # ======================================================================================================
-def synthesis_from_lossless_batch(feats, engine=None):
+def synthesis_from_lossless_batch(feats, engine=None, return_device=False):
     """
     Batched magphase.py:1759-1776.  feats: list of (m_mag, m_real, m_imag, v_f0, fs), all with the same
-    number of bins.  Returns a list of float64 numpy signals.
+    number of bins.  Returns a list of float64 numpy signals (device float32 with return_device: views of one buffer).
     m_mag / m_real / m_imag may be torch tensors on the engine's device (float32 / float16 / bfloat16 / float64, any
     row stride): they are gathered on the device (Engine.pack_rows); one float32 utterance is taken without a copy.  CPU
     tensors are treated as host arrays.  Launches go to torch's current stream of the engine's device.
+    Autograd: with return_device, grad mode on and a device matrix that requires grad, the returned signals carry a
+    grad_fn and tensor.backward() reaches m_mag / m_real / m_imag (magphase_amd/autograd.py; the forward launch and its
+    samples are the same).  Not differentiable: v_f0 and fs; no double backward.
     """
     feats, _on_dev = _tensor_inputs(feats, _LOSSLESS_NAMES)
     engine = engine or get_engine()
     H = int(np.shape(feats[0][0])[1])
     fft_len = 2 * (H - 1)
     plan = LosslessSynthesisPlan(engine, [f[3] for f in feats], [f[4] for f in feats], fft_len)
-    cat = _feats_cat_device(engine, feats, H)
-    pcm = engine.to_host_f64(plan.run(cat[0], cat[1], cat[2]))
+    pcm = _run_lossless_synthesis(engine, plan, feats, H, return_device)
+    if return_device:
+        return [pcm[int(plan.out_off_host[u]):int(plan.out_off_host[u + 1])] for u in range(len(feats))]
+    pcm = engine.to_host_f64(pcm)
     return [pcm[plan.out_off_host[u]:plan.out_off_host[u + 1]] for u in range(len(feats))]
+
+
+def _run_lossless_synthesis(engine, plan, feats, H, return_device):
+    """plan.run on the packed matrices of feats (_feats_cat_device) -> the float32 [total_out] device buffer.  Through
+    autograd.synthesize -- the same two calls inside a torch.autograd.Function -- when the result stays on the device,
+    grad mode is on and one of the matrices is a tensor that requires grad (CPU tensors are host arrays by now)."""
+    import sys
+
+    torch = sys.modules.get("torch")
+    if (return_device and torch is not None and torch.is_grad_enabled()
+            and any(torch.is_tensor(x) and x.requires_grad for f in feats for x in f[:3])):
+        from .autograd import synthesize
+
+        return synthesize(plan, lambda fs_: _feats_cat_device(engine, fs_, H), feats)
+    cat = _feats_cat_device(engine, feats, H)
+    return plan.run(cat[0], cat[1], cat[2])
 
 
 def _feats_cat_device(engine, feats, H):
@@ -441,6 +462,8 @@ def synthesis_from_lossless_const_rate_batch(feats, const_rate_ms=5.0, engine=No
     the start of the grid (the reference's stops after 2n slots).  Time-stretch: synthesise with
     another const_rate_ms than the analysis used; pitch-shift: scale v_f0.  The rows are interpolated as the synthesis
     kernel loads them.  Returns a list of float64 signals (device float32 with return_device).
+    Autograd as synthesis_from_lossless_batch: with return_device, grad mode on and a device matrix that requires grad, the
+    signals carry a grad_fn and backward() reaches the constant-rate rows of m_mag / m_real / m_imag (not v_f0, not fs).
     """
     const_rate_ms = check_const_rate_ms(const_rate_ms)
     feats = list(feats)
@@ -454,8 +477,7 @@ def synthesis_from_lossless_const_rate_batch(feats, const_rate_ms=5.0, engine=No
     engine = engine or get_engine()
     plan = LosslessConstRateSynthesisPlan(engine, f0_list, fs_list, 2 * (H - 1), const_rate_ms=const_rate_ms,
                                           host=host)
-    cat = _feats_cat_device(engine, feats, H)
-    pcm = plan.run(cat[0], cat[1], cat[2])
+    pcm = _run_lossless_synthesis(engine, plan, feats, H, return_device)
     o = plan.out_off_host
     if return_device:
         return [pcm[int(o[u]):int(o[u + 1])] for u in range(len(feats))]

@@ -339,6 +339,8 @@ class LosslessSynthesisPlan:
         self.total_out = int(self.out_off_host[-1])
         self.max_out_len = int(max(lens)) if lens else 0
         self.total_frames = int(sum(nfr))
+        self._ola_host = (pm_rel, starts, lens, nfr)   # what backward_tables() is built from, should it ever be asked for
+        self._bwd = None
         e = engine
         _up = []   # (attribute, host array, dtype): uploaded together (Engine.to_device_packed)
         _up.append(("utt_frame_off", np.concatenate(([0], np.cumsum(nfr))), np.int32))
@@ -364,6 +366,23 @@ class LosslessSynthesisPlan:
         e = self.engine
         return _run_ola(e, lambda strips, out: e.synthesis_lossless_ola(self.fft_len, mag, real, imag, self, strips, out),
                         self.fft_len, self, strips, out, self.total_out)
+
+    def backward_tables(self):
+        """(pos, lo, hi) device tables of mpx_synthesis_lossless_backward: where every frame finds its gradient samples in
+        the [total_out] buffer (hostmath.lossless_backward_table).  Built and uploaded by the first backward pass."""
+        if self._bwd is None:
+            pm_rel, starts, lens, nfr = self._ola_host
+            rel = np.concatenate([np.asarray(r, dtype=np.int64) for r in pm_rel]) if pm_rel else np.zeros(0, np.int64)
+            pos, lo, hi = hm.lossless_backward_table(rel, np.concatenate(([0], np.cumsum(nfr))), starts, lens,
+                                                     self.out_off_host, self.fft_len)
+            d = self.engine.to_device_packed([("pos", pos, np.int64), ("lo", lo, np.int32), ("hi", hi, np.int32)])
+            self._bwd = (d["pos"], d["lo"], d["hi"])
+        return self._bwd
+
+    def run_backward(self, grad_out, mag, real, imag, need=(True, True, True)):
+        """The gradients of run()'s waveform with respect to the rows of mag / real / imag, given grad_out = dL/d(waveform)
+        (contiguous float32 [total_out]): k_synth_lossless_bwd.  None where need[k] is false."""
+        return self.engine.synthesis_lossless_backward(self.fft_len, grad_out, self, mag, real, imag, need=need)
 
     def run_unfused(self, mag, real, imag, frames=None, out=None):
         """Two-kernel form: frames to HBM, then the ascending-order gather (bit-for-bit the reference's sum order)."""
@@ -496,6 +515,24 @@ class LosslessConstRateSynthesisPlan:
         return _run_ola(e, lambda strips, out: e.synthesis_lossless_ola_lerp(self.fft_len, mag, real, imag, self.rows, s,
                                                                               strips, out),
                         self.fft_len, s, strips, out, self.total_out)
+
+    def run_backward(self, grad_out, mag, real, imag, need=(True, True, True)):
+        """The gradients of run()'s waveform with respect to the constant-rate rows of mag / real / imag, given grad_out
+        (contiguous float32 [total_out]): k_synth_lossless_bwd<P, LERP = true> into per-frame scratch rows, then
+        k_rows_lerp_adjoint (frame ranges: hostmath.lerp_adjoint_table, uploaded by the first backward pass).  None where
+        need[k] is false; rows that no frame reads get zeros."""
+        e = self.engine
+        self._check_rows(mag)
+        H = self.fft_len // 2 + 1
+        if self.inner is None:
+            return tuple(e.empty_feats(self.total_rows, H).zero_() if n else None for n in need)
+        if getattr(self, "_adj", None) is None:
+            self._adj = e.to_device(hm.lerp_adjoint_table(self.row0_host, self.row1_host, self.rowt_host,
+                                                          self.total_rows).reshape(-1), np.int32)
+        var = e.synthesis_lossless_backward(self.fft_len, grad_out, self.inner, mag, real, imag, need=need, rows=self.rows)
+        out = e.rows_lerp_adjoint(var, self._adj, self.rows[2], self.total_rows)
+        del var   # (stream-ordered: the allocator reuses the scratch after the adjoint)
+        return out
 
     def run_staged(self, mag, real, imag, rows_out=None, out=None):
         """Staged: k_rows_lerp into variable-rate rows [total_frames x H], then the unchanged k_synth_ola_pair."""
