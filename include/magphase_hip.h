@@ -277,6 +277,31 @@ int mpx_rows_lerp_adjoint(void* stream, int32_t n_bins, const float* src_mag, co
                           int64_t n_rows, float* dst_mag, float* dst_real, float* dst_imag, int64_t ld_dst);
 
 /*
+ * Backward pass of mpx_analysis_frames (magphase.py:74-119, :266-334, :457-476): from grad_mag / grad_real / grad_imag =
+ * dL/d(out_mag, out_real, out_imag) (rows f * ld_grad, [n_frames x fft_len/2 + 1]) and the forward's own output rows
+ * mag / real / imag (row pitch ld) the gradient with respect to the samples, grad_sig float32 [total_smpls].  Per frame,
+ * with N = fft_len, L / R = frame_left / frame_right, len = min(L + R + 1, N), rot = L if L < N else 0:
+ *     d = real grad_real + imag grad_imag,
+ *     gX = grad_mag (real + j imag) + ((grad_real + j grad_imag) - (real + j imag) d) / mag,
+ *          and gX = 0 where mag^2 < 1e-37 (the forward's clamp region, which holds X == 0: silent frames give zeros),
+ *     b = N irfft_N(Y), Y_k = gX_k / 2 for 0 < k < N/2, Y_0 = Re gX_0, Y_{N/2} = Re gX_{N/2},
+ *     gfrm[k] = b[(k - rot) mod N] w(k) for 0 <= k < len (w: the forward's window),
+ *     grad_sig[frame_pos - L + k] += gfrm[k].
+ * Two launches: the frames' len samples go to `scratch` at scratch_off[f] (int64 [n_frames + 1], scratch_off[f + 1] -
+ * scratch_off[f] = len: hostmath.analysis_backward_table; scratch_floats >= scratch_off[n_frames]), then one thread per
+ * sample adds the frames that cover it in ascending frame order -- frame starts and ends must be non-decreasing, as they
+ * are for the batches the plans build.  Every element of grad_sig is written exactly once (0 where no frame covers it):
+ * no atomics, deterministic.  Whatever the tables say, nothing is written outside scratch and grad_sig.  A null grad_X
+ * is not read and contributes zero; all three null, or n_frames == 0, launches nothing and leaves grad_sig untouched.
+ */
+int mpx_analysis_lossless_backward(void* stream, int fft_len, const void* tables, const float* mag, const float* real,
+                                   const float* imag, int64_t ld, const float* grad_mag, const float* grad_real,
+                                   const float* grad_imag, int64_t ld_grad, const int64_t* frame_pos,
+                                   const int32_t* frame_left, const int32_t* frame_right, const int64_t* scratch_off,
+                                   int64_t n_frames, float* scratch, int64_t scratch_floats, float* grad_sig,
+                                   int64_t total_smpls);
+
+/*
  * Copy synthesis in one launch: analysis_lossless (magphase.py:2869-2906: windowing :74-119, analysis_with_del_comp_from_pm
  * :266-334, compute_lossless_feats :457-476) followed by synthesis_from_lossless (:1759-1776, ola :34-62) on the same
  * frames, as demos/demo_copy_synthesis_lossless.py:44-50 calls them back to back.  Frame f is cut out of `sig` exactly as

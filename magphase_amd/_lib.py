@@ -44,6 +44,8 @@ PROTOTYPES = {
     "mpx_rows_lerp": (i32, [vp, i32, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64]),
     "mpx_synthesis_lossless_backward": (i32, [vp, i32, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64] + [vp] * 6 + [i64]),
     "mpx_rows_lerp_adjoint": (i32, [vp, i32, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, i64]),
+    "mpx_analysis_lossless_backward": (i32, [vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, i64,
+                                             vp, i64]),
     "mpx_ola_fixup": (i32, [vp, i32, vp, i32, vp, vp]),
     "mpx_roundtrip_lossless_ola": (i32, [vp, i32] + [vp] * 5 + [i64, vp, i32, vp, vp, i32] + [vp] * 6 + [i64]),
     "mpx_roundtrip_slot_weights": (i32, [vp, i32]),

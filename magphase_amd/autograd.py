@@ -1,11 +1,21 @@
 """
-Autograd for the lossless synthesis: a torch.autograd.Function around the unchanged forward
-launch of synthesis_from_lossless_batch / synthesis_from_lossless_const_rate_batch, with the gradients with respect to
-m_mag / m_real / m_imag computed by k_synth_lossless_bwd (and k_rows_lerp_adjoint for constant-rate rows).  Imported
-lazily by magphase.py, and only when a device tensor that requires grad goes in with return_device=True and grad mode on.
+Autograd for the lossless features, both directions.  Imported lazily by magphase.py, and only when a device tensor that
+requires grad goes in with return_device=True and grad mode on.
 
-Not differentiable: v_f0 (the pitch marks are integers) and fs.  No double backward.  The compressed and type-2
-synthesis and the analysis direction have no backward pass.
+Synthesis: a torch.autograd.Function around the unchanged forward launch of
+synthesis_from_lossless_batch / synthesis_from_lossless_const_rate_batch, with the gradients with respect to
+m_mag / m_real / m_imag computed by k_synth_lossless_bwd (and k_rows_lerp_adjoint for constant-rate rows).
+Not differentiable: v_f0 (the pitch marks are integers) and fs.
+
+Analysis (section 3.3i): a second Function around the unchanged forward launch of analysis_lossless_batch, with the
+gradient with respect to the samples v_sig computed by k_analysis_lossless_bwd and k_analysis_bwd_gather from the
+forward's own output rows (X = mag (real + j imag): nothing else is kept).  Not differentiable: v_pm_sec, v_voi and fs
+(the epochs are rounded to samples); v_f0 and v_shift come from the host and carry no grad_fn.  Where mag^2 < 1e-37 --
+the clamp region of the forward's 1 / |X|, which holds X == 0 -- the gradient with respect to X is defined as zero: a
+silent frame gives zeros, never Inf or NaN.
+
+No double backward.  The compressed and type-2 synthesis, and the constant-rate, type-2 and compressed analysis, have
+no backward pass.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -56,3 +66,40 @@ def synthesize(plan, cat_fn, feats):
     matrices that are tensors requiring grad.  Returns the float32 [total_out] waveform buffer (with grad_fn)."""
     mats = [x for f in feats for x in f[:3]]
     return _LosslessSynthesis.apply(plan, cat_fn, len(feats), *mats)
+
+
+class _LosslessAnalysis(torch.autograd.Function):
+    """forward(plan, *sigs): plan = a LosslessAnalysisPlan built from the utterances whose v_sig are sigs (tensors or
+    host arrays; the plan holds the samples as one float32 device buffer already); plan.run() is the forward launch,
+    plan.run_backward(...) the backward ones.  Outputs: the three float32 [total_frames x H] matrices of the batch; the
+    per-utterance results are row views of them."""
+
+    @staticmethod
+    def forward(ctx, plan, *sigs):
+        mag, real, imag = plan.run()
+        ctx.plan = plan
+        ctx.like = [(s.dtype, tuple(s.shape)) if torch.is_tensor(s) else None for s in sigs]
+        ctx.set_materialize_grads(False)     # an output nobody differentiated arrives as None: not read by the kernel
+        ctx.save_for_backward(mag, real, imag)
+        return mag, real, imag
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        mag, real, imag = ctx.saved_tensors
+        need_in = ctx.needs_input_grad[1:]
+        grads = tuple(g if g is None or (g.dtype == torch.float32 and g.is_contiguous())
+                      else g.to(torch.float32).contiguous() for g in grads)
+        with torch.cuda.device(mag.device):
+            gsig = ctx.plan.run_backward(mag, real, imag, grads)
+        out, a = [], 0
+        for like, need, n in zip(ctx.like, need_in, ctx.plan.n_smpls):
+            out.append(gsig[a:a + n].to(like[0]).reshape(like[1]) if like is not None and need else None)
+            a += n
+        return (None,) + tuple(out)
+
+
+def analyze(plan, sigs):
+    """plan.run(), differentiable with respect to the v_sig in sigs that are tensors requiring grad.  Returns the three
+    float32 [total_frames x H] matrices (with grad_fn)."""
+    return _LosslessAnalysis.apply(plan, *sigs)

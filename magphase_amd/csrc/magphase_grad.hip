@@ -1,4 +1,5 @@
-// magphase_grad.hip -- backward pass of the lossless synthesis.
+// magphase_grad.hip -- backward passes of the lossless synthesis (first part of this file) and of
+// the lossless analysis (section 3.3i: k_analysis_lossless_bwd, k_analysis_bwd_gather, further down).
 //
 //   k_synth_lossless_bwd<P, L>  one wavefront per frame, persistent waves (grid-stride over frames), the shape of
 //                               k_analysis: the N samples of the incoming waveform gradient around the frame's pitch mark
@@ -317,6 +318,179 @@ __global__ __launch_bounds__(kAdjWaves * 64) void k_rows_lerp_adjoint(int H, con
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Backward pass of the lossless analysis.
+//
+// The forward (k_analysis) is X = rfft_N(buf), buf = the windowed frame rotated by rot, and (mag, real, imag) =
+// (|X|, X / |X|) (all 0 where X == 0).  Given (gm, gr, gi) = dL/d(mag, real, imag) and the forward's own outputs:
+//   d = real gr + imag gi,   gX = gm (real + j imag) + ((gr + j gi) - (real + j imag) d) / mag     (0 where mag^2 < 1e-37)
+//   b = N irfft_N(Y), Y_k = gX_k / 2 for 0 < k < N/2, Y_0 = Re gX_0, Y_{N/2} = Re gX_{N/2}   (the transpose of rfft_N)
+//   gfrm[k] = b[(k - rot) mod N] w(k) for 0 <= k < len,   gsig[pos - L + k] += gfrm[k]
+//
+//   k_analysis_lossless_bwd<P>  one wavefront per frame, persistent waves (grid-stride), the shape of k_synth_lossless:
+//                               the six rows of a frame in the paired layout of feat_load_paired (ascending bins
+//                               lane + 64 j and their mirrors M - k: every load one contiguous 256-byte block) -> gX ->
+//                               merge_pair_step / merge_handover -> wave_fft<P, +1> -> rotation, hann_half -> the frame's
+//                               len samples into a COMPACT scratch (scratch_off[f]: prefix sums built on the host).
+//   k_analysis_bwd_gather       one thread per signal sample: the sum over the frames that cover it, in ascending frame
+//                               order (a contiguous frame range: hostmath.analysis_backward_table).  One writer per
+//                               element, no atomics; a sample no frame covers gets 0.
+// ---------------------------------------------------------------------------------------------
+// One bin of the pointwise step: (m, a, b) the forward's mag / real / imag, (gm, gr, gi) their gradients -> sc gX.
+// mag^2 < 1e-37 is the forward's clamp region (rsq(max(|X|^2, 1e-37)): X == 0 lies in it, and the outputs there are not
+// (|X|, X / |X|)): the gradient is defined as 0 there -- silent frames give zeros, never Inf or NaN.
+__device__ __forceinline__ void ana_bwd_bin(float m, float a, float b, float gm, float gr, float gi, float sc, float& x_r,
+                                            float& x_i) {
+    const bool live = m * m >= 1.0e-37f;
+    const float inv = live ? sc * __builtin_amdgcn_rcpf(m) : 0.0f;
+    const float gs = live ? sc * gm : 0.0f;
+    const float d = a * gr + b * gi;
+    x_r = gs * a + (gr - a * d) * inv;
+    x_i = gs * b + (gi - b * d) * inv;
+}
+
+// Waves per workgroup: k_analysis' 12 (three per SIMD, <= 168 VGPRs) for P = 8 / 16; P = 32 holds 64 spectrum registers
+// beside the row loads and needs more than 168 (it spilled 51 at any load group size): 8 waves, two per SIMD, as
+// k_synth_lossless.
+template <int P>
+constexpr int ana_bwd_waves() { return P == 32 ? kWavesPerBlock : kAnaWaves; }
+template <int P>
+constexpr size_t lds_bytes_ana_bwd() { return sizeof(float) * (size_t)(tw_floats<P>() + ana_bwd_waves<P>() * P * kXStride); }
+
+template <int P>
+__global__ __launch_bounds__(64 * ana_bwd_waves<P>()) void k_analysis_lossless_bwd(
+    const float* __restrict__ mag, const float* __restrict__ real, const float* __restrict__ imag, long long ld,
+    const float* __restrict__ gmag, const float* __restrict__ greal, const float* __restrict__ gimag, long long ldg,
+    const int* __restrict__ fleft, const int* __restrict__ fright, const long long* __restrict__ soff, long long nframes,
+    const float* __restrict__ tw_g, float* __restrict__ scratch, long long scratch_floats) {
+    constexpr int M = 64 * P, N = 2 * M, LB = ilog2(P), HP = P / 2;
+    constexpr int CH = 4;   // bin pairs per load group: 12 CH row values in flight beside the 2 P of the growing spectrum
+    constexpr int kWaves = ana_bwd_waves<P>(), kThr = 64 * kWaves;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* tw = smem;
+    const int lane_id = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    float* xbuf = smem + tw_floats<P>() + wave * (P * kXStride);
+    for (int i = threadIdx.x; i < tw_floats<P>(); i += kThr) tw[i] = tw_g[i];
+    __syncthreads();
+
+    // input layout is natural (k = lane + 64 j): lane twiddle conj(W_N^lane) = e^{+2 pi i lane/N}, as k_synth_lossless
+    float wl_s0, wl_c0;
+    sincospif(2.0f * (float)lane_id / (float)N, &wl_s0, &wl_c0);
+
+    const long long fstep = (long long)gridDim.x * kWaves;
+    for (long long f = (long long)blockIdx.x * kWaves + rfl(wave); f < nframes; f += fstep) {
+        int lane = lane_id;  // laundered per frame (see k_analysis)
+        float wl_s = wl_s0, wl_c = wl_c0;
+        asm volatile("" : "+v"(lane), "+v"(wl_s), "+v"(wl_c));
+        const int kap = kappa<P>(lane);
+        const bool lane0 = (lane == 0);
+
+        // ---- the six rows in the paired layout, CH bin pairs at a time; a null gradient stream is never loaded
+        const float* row[3] = {mag + f * ld, real + f * ld, imag + f * ld};
+        const float* grow[3] = {gmag ? gmag + f * ldg : nullptr, greal ? greal + f * ldg : nullptr,
+                                gimag ? gimag + f * ldg : nullptr};
+        float xr[P], xi[P], zr[HP], zi[HP];
+#pragma unroll
+        for (int c = 0; c < HP; c += CH) {
+            float v[3][CH], vq[3][CH], g[3][CH], gq[3][CH];
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+                const float* lo = row[s] + lane;
+                const float* hi = row[s] + (M - lane);
+#pragma unroll
+                for (int e = 0; e < CH; ++e) {
+                    v[s][e] = lo[64 * (c + e)];
+                    vq[s][e] = hi[-64 * (c + e)];
+                    g[s][e] = gq[s][e] = 0.0f;
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+                if (!grow[s]) continue;   // wave-uniform
+                const float* lo = grow[s] + lane;
+                const float* hi = grow[s] + (M - lane);
+#pragma unroll
+                for (int e = 0; e < CH; ++e) {
+                    g[s][e] = lo[64 * (c + e)];
+                    gq[s][e] = hi[-64 * (c + e)];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < CH; ++e) {
+                const int j = c + e;
+                // bins 0 and M (lane 0 of step 0): Y = Re gX; every other bin: Y = gX / 2
+                const bool edge = (j == 0) && lane0;
+                const float sc = edge ? 1.0f : 0.5f;
+                float x_r, x_i, p_r, p_i;
+                ana_bwd_bin(v[0][e], v[1][e], v[2][e], g[0][e], g[1][e], g[2][e], sc, x_r, x_i);
+                ana_bwd_bin(vq[0][e], vq[1][e], vq[2][e], gq[0][e], gq[1][e], gq[2][e], sc, p_r, p_i);
+                x_i = edge ? 0.0f : x_i;
+                p_i = edge ? 0.0f : p_i;
+                merge_pair_step<P>(j, x_r, x_i, p_r, p_i, wl_c, wl_s, xr[j], xi[j], zr[j], zi[j]);
+            }
+        }
+        {   // bin M/2 is its own mirror (lane 0): Z = 2 conj(Y).  Every lane loads "its" bin M/2 + lane (feat_load_paired)
+            float v[3], g[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int s = 0; s < 3; ++s) v[s] = row[s][M / 2 + lane];
+#pragma unroll
+            for (int s = 0; s < 3; ++s)
+                if (grow[s]) g[s] = grow[s][M / 2 + lane];
+            float h_r, h_i;
+            ana_bwd_bin(v[0], v[1], v[2], g[0], g[1], g[2], 0.5f, h_r, h_i);
+            merge_handover<P>(zr, zi, 2.0f * h_r, -2.0f * h_i, xr, xi, lane);
+        }
+
+        wave_fft<P, +1>(xr, xi, tw, xbuf, lane);
+
+        // ---- register i holds b[2 n], b[2 n + 1], n = kappa + 64 brev(i): buffer index m is sample k = (m + rot) mod N of
+        // the frame, kept for k < len.  Whatever the tables say, nothing is written outside the frame's own part of the
+        // scratch, [soff[f], soff[f + 1]) within [0, scratch_floats).
+        const FrameGeom fg = frame_geom(scratch, 0, fleft[f], fright[f], N);   // (base is not used: the samples go to dst)
+        const long long so = soff[f], cap = soff[f + 1] - so;
+        const bool fits = so >= 0 && cap >= 0 && so + cap <= scratch_floats;
+        const int nvalid = fits ? max((int)min((long long)fg.len, cap), 0) : 0;
+        float* dst = scratch + so;
+#pragma unroll
+        for (int i = 0; i < P; ++i) {
+            const int m0 = 2 * (kap + 64 * brev(i, LB));
+            int k0 = m0 + fg.rot;
+            k0 = (k0 >= N) ? k0 - N : k0;
+            int k1 = m0 + 1 + fg.rot;
+            k1 = (k1 >= N) ? k1 - N : k1;
+            if ((unsigned)k0 < (unsigned)nvalid) dst[k0] = xr[i] * hann_half(k0, fg.L, fg.LR, fg.kadd, fg.invL, fg.invR);
+            if ((unsigned)k1 < (unsigned)nvalid) dst[k1] = xi[i] * hann_half(k1, fg.L, fg.LR, fg.kadd, fg.invL, fg.invR);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_analysis_bwd_gather(const float* __restrict__ scratch, long long scratch_floats,
+                                                             const long long* __restrict__ fpos,
+                                                             const int* __restrict__ fleft,
+                                                             const long long* __restrict__ soff, long long nframes,
+                                                             float* __restrict__ gsig, long long total) {
+    // the first frame that ends after the workgroup's first sample: one binary search per workgroup (wave-uniform: scalar
+    // loads) over the frames' ends, which are non-decreasing; every thread then walks on from there
+    const long long t0 = (long long)blockIdx.x * 256;
+    long long lo = 0, hi = nframes;
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        const long long end = fpos[mid] - fleft[mid] + (soff[mid + 1] - soff[mid]);   // one past the frame's last sample
+        if (end > t0) hi = mid; else lo = mid + 1;
+    }
+    const long long t = t0 + threadIdx.x;
+    if (t >= total) return;
+    float acc = 0.0f;
+    for (long long f = lo; f < nframes; ++f) {
+        const long long start = fpos[f] - fleft[f];
+        if (start > t) break;   // starts are non-decreasing: no later frame covers t
+        const long long o = soff[f], n = soff[f + 1] - o, k = t - start;
+        if (k < n && o >= 0 && o + n <= scratch_floats) acc += scratch[o + k];
+    }
+    gsig[t] = acc;
+}
+
 }  // namespace mpx
 
 using namespace mpx;
@@ -362,6 +536,49 @@ int mpx_synthesis_lossless_backward(void* stream, int fft_len, const void* table
     }
 #undef MPX_LAUNCH_BWD
     MPX_HIP_CHECK(hipGetLastError());
+    return MPX_OK;
+}
+
+int mpx_analysis_lossless_backward(void* stream, int fft_len, const void* tables, const float* mag, const float* real,
+                                   const float* imag, int64_t ld, const float* grad_mag, const float* grad_real,
+                                   const float* grad_imag, int64_t ld_grad, const int64_t* frame_pos,
+                                   const int32_t* frame_left, const int32_t* frame_right, const int64_t* scratch_off,
+                                   int64_t n_frames, float* scratch, int64_t scratch_floats, float* grad_sig,
+                                   int64_t total_smpls) {
+    const int P = p_of(fft_len);
+    if (!P) return fail(MPX_ERR_ARG, "mpx_analysis_lossless_backward: fft_len must be 1024, 2048 or 4096%s");
+    if (n_frames < 0 || total_smpls < 0 || scratch_floats < 0)
+        return fail(MPX_ERR_ARG, "mpx_analysis_lossless_backward: negative count%s");
+    if (ld < fft_len / 2 + 1 || ld_grad < fft_len / 2 + 1)
+        return fail(MPX_ERR_ARG, "mpx_analysis_lossless_backward: ld < fft_len/2 + 1%s");
+    if (n_frames == 0) return MPX_OK;
+    if (!grad_mag && !grad_real && !grad_imag) return MPX_OK;   // nothing to propagate: grad_sig is not written
+    if (!tables || !mag || !real || !imag || !frame_pos || !frame_left || !frame_right || !scratch_off ||
+        (scratch_floats > 0 && !scratch) || (total_smpls > 0 && !grad_sig))
+        return fail(MPX_ERR_ARG, "mpx_analysis_lossless_backward: null pointer%s");
+    if ((total_smpls + 255) / 256 > 2147483647LL)
+        return fail(MPX_ERR_ARG, "mpx_analysis_lossless_backward: too many samples%s");
+    hipStream_t s = (hipStream_t)stream;
+#define MPX_LAUNCH_ABWD(PP)                                                                                           \
+    do {                                                                                                              \
+        const dim3 grid(grid_for(n_frames, ana_bwd_waves<PP>())), block(64 * ana_bwd_waves<PP>());                    \
+        if (int rc = set_lds((k_analysis_lossless_bwd<PP>), lds_bytes_ana_bwd<PP>())) return rc;                      \
+        hipLaunchKernelGGL((k_analysis_lossless_bwd<PP>), grid, block, lds_bytes_ana_bwd<PP>(), s, mag, real, imag,   \
+                           (long long)ld, grad_mag, grad_real, grad_imag, (long long)ld_grad, frame_left, frame_right, \
+                           (const long long*)scratch_off, (long long)n_frames, (const float*)tables, scratch,         \
+                           (long long)scratch_floats);                                                               \
+    } while (0)
+    if (P == 32) MPX_LAUNCH_ABWD(32);
+    else if (P == 16) MPX_LAUNCH_ABWD(16);
+    else MPX_LAUNCH_ABWD(8);
+#undef MPX_LAUNCH_ABWD
+    MPX_HIP_CHECK(hipGetLastError());
+    if (total_smpls > 0) {
+        hipLaunchKernelGGL(k_analysis_bwd_gather, dim3((unsigned)((total_smpls + 255) / 256)), dim3(256), 0, s, scratch,
+                           (long long)scratch_floats, (const long long*)frame_pos, frame_left,
+                           (const long long*)scratch_off, (long long)n_frames, grad_sig, (long long)total_smpls);
+        MPX_HIP_CHECK(hipGetLastError());
+    }
     return MPX_OK;
 }
 

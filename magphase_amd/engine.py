@@ -1438,6 +1438,28 @@ class Engine:
                     lo, hi, nfr, mag, real, imag, self.feat_ld(mag, real, imag), r0, r1, rt, out[0], out[1], out[2], ld_g)
         return out
 
+    def analysis_lossless_backward(self, fft_len, plan, mag, real, imag, grads):
+        """mpx_analysis_lossless_backward: plan: LosslessAnalysisPlan, mag / real / imag: the rows its run() returned,
+        grads = (g_mag, g_real, g_imag): float32 [plan.total_frames x H] rows with unit column stride and one row pitch, or
+        None for an output nobody differentiated (not read, contributes zero) -> dL/d(samples), float32
+        [plan.total_smpls] (zeros where no frame covers a sample, or when nothing is given)."""
+        torch = _torch()
+        H = int(fft_len) // 2 + 1
+        nfr, total = int(plan.total_frames), int(plan.total_smpls)
+        have = [g for g in grads if g is not None]
+        for g in have:
+            if g.dtype != torch.float32 or tuple(g.shape) != (nfr, H):
+                raise ValueError("analysis_lossless_backward: gradients must be float32 [%d x %d]" % (nfr, H))
+        if nfr == 0 or total == 0 or not have:
+            return torch.zeros((total,), dtype=torch.float32, device=self.device)
+        soff, scratch_floats = plan.backward_tables()
+        scratch = self.empty((max(scratch_floats, 1),))
+        out = self.empty((total,))
+        self.launch("mpx_analysis_lossless_backward", int(fft_len), self.tables(fft_len), mag, real, imag,
+                    self.feat_ld(mag, real, imag), grads[0], grads[1], grads[2], self.feat_ld(*(have * 3)[:3]),
+                    plan.pos, plan.left, plan.right, soff, nfr, scratch, scratch_floats, out, total)
+        return out
+
     def rows_lerp_adjoint(self, src, ranges, rowt, n_rows):
         """mpx_rows_lerp_adjoint: src = (g_mag, g_real, g_imag) per-frame rows (None: stream not wanted), ranges int32
         [n_rows x 4] (hostmath.lerp_adjoint_table) and rowt on the device -> the gradients of the n_rows table rows, a

@@ -843,6 +843,46 @@ def lossless_backward_table(pm_rel, frame_off, out_start, out_len, out_off, fft_
     return rep(out_off) + t0, lo.astype(np.int32), hi.astype(np.int32)
 
 
+def check_signal_tensor(t, name):
+    """Argument check of a torch tensor given where the batch API takes a waveform: float32, float16, bfloat16 or
+    float64, 1-D (any element stride).  Needs no device."""
+    if str(t.dtype) not in ROWS_PACK_CODES:
+        raise ValueError("%s: dtype %s is not supported (float32, float16, bfloat16 or float64)" % (name, t.dtype))
+    if t.dim() != 1:
+        raise ValueError("%s: must be 1-D, got %d-D" % (name, t.dim()))
+
+
+def analysis_backward_table(pos, left, right, fft_len, total_smpls):
+    """
+    Where every frame of a lossless analysis batch puts its windowed gradient samples, and where the gather finds them
+    (mpx_analysis_lossless_backward).  Frame f covers the samples start[f] = pos[f] - left[f] .. start[f] + n[f] - 1 of the
+    batch's signal buffer, n[f] = min(left[f] + right[f] + 1, fft_len) (a longer frame is truncated by the forward); its
+    n[f] gradient samples lie at scratch_off[f] in a compact scratch buffer of scratch_off[-1] floats.  The gather adds,
+    per signal sample, the frames that cover it in ascending frame order: those are a contiguous index range when start
+    and start + n are non-decreasing over the batch -- they are (within an utterance both ends of a frame are epochs or
+    the utterance's ends, and the utterances follow one another in the buffer), and a table for which they are not is
+    refused, as is a frame that leaves [0, total_smpls).  Returns (start int64[F], scratch_off int64[F + 1]).  Pure index
+    arithmetic: no torch, no GPU.
+    """
+    pos = np.asarray(pos, dtype=np.int64).reshape(-1)
+    left = np.asarray(left, dtype=np.int64).reshape(-1)
+    right = np.asarray(right, dtype=np.int64).reshape(-1)
+    N, total = int(fft_len), int(total_smpls)
+    if not (pos.size == left.size == right.size):
+        raise ValueError("analysis_backward_table: pos, left and right must have one length")
+    if N < 1 or total < 0 or pos.size >= 2 ** 31:
+        raise ValueError("analysis_backward_table: fft_len < 1, total_smpls < 0 or too many frames")
+    if pos.size and (left.min() < 0 or right.min() < 0):
+        raise ValueError("analysis_backward_table: negative left or right")
+    n = np.minimum(left + right + 1, N)
+    start = pos - left
+    if pos.size and (start.min() < 0 or (start + n).max() > total):
+        raise ValueError("analysis_backward_table: a frame leaves the signal buffer [0, %d)" % total)
+    if np.any(np.diff(start) < 0) or np.any(np.diff(start + n) < 0):
+        raise ValueError("analysis_backward_table: frame starts and ends must be non-decreasing")
+    return start, np.concatenate(([0], np.cumsum(n))).astype(np.int64)
+
+
 def _const_to_variable_scan_scipy(v_shift_c_rate, frm_rate_ms, fs):
     """The constant -> variable rate scan (magphase.py:1426-1449) written like the reference: one scipy interp1d call per
     step (8 us each).  hostplan._const_to_variable_scan is the native form the tests compare with this one."""

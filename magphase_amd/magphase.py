@@ -257,13 +257,22 @@ def analysis_lossless_batch(utts, fft_len=None, engine=None, return_device=False
     memory).  copy=False: the utterances' matrices are ROW VIEWS of three arrays that hold the whole batch -- no second
     pass over the data (0.7 GB for 16 utterances), but keeping one utterance alive keeps the batch alive and in-place
     edits are made in the shared arrays; bench.py and iobatch use it.
+    v_sig may be a 1-D torch tensor on the engine's device (float32 / float16 / bfloat16 / float64, any element stride):
+    the samples stay on the device -- one float32 contiguous utterance is read where it lies, otherwise the batch is
+    converted and concatenated there; host arrays in the same batch are uploaded one by one (the slow mixed case) -- and
+    the rows equal those of the host-array call on the same float32 samples bit for bit.  v_pm_sec and v_voi stay host
+    arrays.  A CPU tensor is treated as a host array; a tensor on another device raises ValueError.  Launches go to
+    torch's current stream of the engine's device.
+    Autograd: with return_device, grad mode on and a device v_sig that requires grad, m_mag / m_real / m_imag carry a
+    grad_fn and tensor.backward() reaches v_sig (magphase_amd/autograd.py; the forward launch and its rows are the
+    same).  Not differentiable: v_pm_sec, v_voi and fs; v_f0 and v_shift carry no grad_fn; no double backward.
     """
     engine = engine or get_engine()
     plan = LosslessAnalysisPlan(engine, utts, fft_len=fft_len)
     for lens in plan.long_frame_lens:
         for n in lens:  # Q19: truncation warns, it does not raise (magphase.py:311-315)
             warnings.warn(_WARN_LONG % (plan.fft_len, n))
-    mag, real, imag = plan.run()
+    mag, real, imag = _run_lossless_analysis(plan, utts, return_device)
     if not return_device:   # one pinned, chunked D2H per stream for the whole batch (engine.to_host_f64)
         h_feats = tuple(engine.to_host_f64_many([mag, real, imag]))
     out = []
@@ -277,6 +286,21 @@ def analysis_lossless_batch(utts, fft_len=None, engine=None, return_device=False
             feats = h_feats if len(utts) == 1 else tuple((h[a:b].copy() if copy else h[a:b]) for h in h_feats)
         out.append(feats + (plan.v_f0[u], plan.fs[u], plan.v_shift[u].astype(int)))
     return out
+
+
+def _run_lossless_analysis(plan, utts, return_device):
+    """plan.run() -> the batch's three float32 device matrices.  Through autograd.analyze -- the same launch inside a
+    torch.autograd.Function -- when the result stays on the device, grad mode is on and some v_sig is a device tensor that
+    requires grad (a CPU tensor is a host array to the plan)."""
+    import sys
+
+    torch = sys.modules.get("torch")
+    if (return_device and torch is not None and torch.is_grad_enabled()
+            and any(torch.is_tensor(u[0]) and u[0].requires_grad and u[0].device.type != "cpu" for u in utts)):
+        from .autograd import analyze
+
+        return analyze(plan, [u[0] for u in utts])
+    return plan.run()
 
 
 def analysis_lossless_from_epochs(v_sig, fs, v_pm_sec, v_voi, fft_len=None):

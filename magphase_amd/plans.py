@@ -39,6 +39,30 @@ def _rows_or_array(engine, x, name):
     return x if x.shape[1] <= 1 or x.stride(1) == 1 else x.contiguous()
 
 
+def _signal_inputs(engine, utts):
+    """torch tensors among the v_sig of an analysis batch utts = [(v_sig, fs, v_pm_sec, v_voi), ...]: checked (float32 /
+    float16 / bfloat16 / float64, 1-D: ValueError naming the utterance otherwise); a CPU tensor becomes a host array
+    (float16 / bfloat16 widened to float32: exact), a tensor on the engine's device stays, a tensor elsewhere is an error.
+    Returns (utts, True when a device tensor remains); a batch without tensors comes back as it is."""
+    if not any(_is_tensor(u[0]) for u in utts):
+        return utts, False
+    out, on_dev = [], False
+    for i, u in enumerate(utts):
+        x = u[0]
+        if _is_tensor(x):
+            name = "utts[%d]: v_sig" % i
+            hm.check_signal_tensor(x, name)
+            if x.device.type == "cpu":
+                x = x.detach()
+                x = (x.float() if x.element_size() == 2 else x).numpy()
+            elif x.device != getattr(engine, "device", None):
+                raise ValueError("%s is on %s, the engine runs on %s" % (name, x.device, getattr(engine, "device", None)))
+            else:
+                on_dev = True
+        out.append((x,) + tuple(u[1:]))
+    return out, on_dev
+
+
 TYPE2_ENV_NCOEFFS = 600   # la.true_envelope(..., ncoeffs=600, thres_db=0.1) of analysis_lossless_type2 (magphase.py:2829)
 TYPE2_ENV_THRES_DB = 0.1
 
@@ -148,6 +172,13 @@ class LosslessAnalysisPlan:
         # prepared: a PreparedAnalysis of these utterances (Engine.prepare_analysis, e.g. from the planner thread); None:
         # prepared here when the batch is in the plain shape the native path takes, else the generic path below
         self.engine = engine
+        utts, on_dev = _signal_inputs(engine, utts)
+        if on_dev:      # some v_sig is a tensor on the engine's device: the samples never visit the host
+            if prepared is not None:
+                prepared.release()
+                raise ValueError("prepared= was built from host arrays: it cannot be combined with tensor inputs")
+            self._from_device(engine, utts, fft_len)
+            return
         if prepared is None and hasattr(engine, "prepare_analysis") and os.environ.get("MAGPHASE_NATIVE_PREPARE", "1") != "0":
             prepared = engine.prepare_analysis(utts, fft_len, wait=False)
         if prepared is not None:
@@ -204,8 +235,9 @@ class LosslessAnalysisPlan:
 
     def _build_generic(self, engine, utts, fft_len, buf, off, copied, all_i16, staged, total, pos, left, right):
         for (v_sig, fs, v_pm_sec, v_voi) in utts:
-            v_sig = np.asarray(v_sig)
-            n = v_sig.shape[0]
+            if not _is_tensor(v_sig):   # (a device tensor: _from_device, which copies no samples here)
+                v_sig = np.asarray(v_sig)
+            n = int(v_sig.shape[0])
             if copied:
                 pass
             elif all_i16:
@@ -268,6 +300,57 @@ class LosslessAnalysisPlan:
                                    ("left", np.concatenate(left) if left else np.zeros(0), np.int32),
                                    ("right", np.concatenate(right) if right else np.zeros(0), np.int32)])
         self.pos, self.left, self.right = desc["pos"], desc["left"], desc["right"]
+
+    def _from_device(self, engine, utts, fft_len):
+        """A batch with device-tensor signals (_signal_inputs has checked them): the tables as for host signals
+        (hostplan.plan_analysis or its numpy fallback: they need the lengths only), self.sig = ONE contiguous float32
+        device buffer -- a single float32 contiguous utterance where it lies, else torch converts and concatenates on the
+        device (copy_: float64 -> float32 rounds to nearest even, as numpy's cast on the host path; float16 / bfloat16
+        widen exactly; any element stride).  Host arrays in the same batch are uploaded one by one (the slow mixed case).
+        No host staging, no D2H copy of samples; everything is queued on torch's current stream."""
+        torch = _torch()
+        pos, left, right = [], [], []
+        self.v_shift, self.v_f0, self.fs, self.n_frames, self.n_smpls, self.v_pm = [], [], [], [], [], []
+        self._build_generic(engine, utts, fft_len, None, 0, True, False, False, 0, pos, left, right)
+        sigs = [u[0] for u in utts]
+        with torch.cuda.device(engine.device):
+            if len(sigs) == 1 and sigs[0].dtype == torch.float32 and sigs[0].is_contiguous():
+                self.sig = sigs[0].detach()
+            else:
+                self.sig = engine.empty((max(self.total_smpls, 1),))[:self.total_smpls]
+                a = 0
+                for v, n in zip(sigs, self.n_smpls):
+                    if _is_tensor(v):
+                        self.sig[a:a + n].copy_(v.detach())
+                    else:
+                        v = np.asarray(v)
+                        v = v.astype(np.float32) * np.float32(1.0 / 32768.0) if v.dtype == np.int16 else v.astype(np.float32)
+                        self.sig[a:a + n].copy_(torch.from_numpy(np.ascontiguousarray(v)))
+                    a += n
+        cat = [np.concatenate(x) if x else np.zeros(0, dtype=np.int64) for x in (pos, left, right)]
+        self._host_tabs = tuple(cat)
+        desc = engine.to_device_packed([("pos", cat[0], np.int64), ("left", cat[1], np.int32), ("right", cat[2], np.int32)])
+        self.pos, self.left, self.right = desc["pos"], desc["left"], desc["right"]
+
+    def backward_tables(self):
+        """(scratch_off device int64 [F + 1], scratch floats) of mpx_analysis_lossless_backward
+        (hostmath.analysis_backward_table).  Built and uploaded by the first backward pass; a plan that kept no host
+        copy of its frame tables reads them back from the device for that."""
+        if getattr(self, "_bwd", None) is None:
+            tabs = getattr(self, "_host_tabs", None)
+            if tabs is None:
+                _wait_ready(self)
+                tabs = tuple(t.cpu().numpy() for t in (self.pos, self.left, self.right))
+            _start, soff = hm.analysis_backward_table(tabs[0], tabs[1], tabs[2], self.fft_len, self.total_smpls)
+            self._bwd = (self.engine.to_device(soff, np.int64), int(soff[-1]))
+        return self._bwd
+
+    def run_backward(self, mag, real, imag, grads):
+        """The gradient of a loss with respect to the batch's samples, float32 [total_smpls] (utterance u at the offset
+        of its samples in self.sig), given mag / real / imag = run()'s rows and grads = (dL/d mag, dL/d real, dL/d imag)
+        as contiguous float32 [total_frames x H] matrices or None: k_analysis_lossless_bwd + k_analysis_bwd_gather."""
+        _wait_ready(self)
+        return self.engine.analysis_lossless_backward(self.fft_len, self, mag, real, imag, grads)
 
     def _from_prepared(self, p, utts):
         """Takes over a PreparedAnalysis: two DMAs (samples, tables) and, for 16-bit input, the widening kernel."""
