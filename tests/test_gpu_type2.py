@@ -147,3 +147,83 @@ def test_file_products(g, tmp_path):
     assert sorted(os.listdir(str(d_var))) == ["t2.imag", "t2.lf0", "t2.mag", "t2.real", "t2.shift"]
     assert sorted(os.listdir(str(d_cr))) == ["t2.imag", "t2.lf0", "t2.mag", "t2.real"]
     np.testing.assert_array_equal(lu.read_binfile(str(d_cr / "t2.mag"), dim=60), c[0].astype(np.float32))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# synthetic utterances against the float64 model: fft_len 1024, mixed sample rates, over-long frames, silence
+# ---------------------------------------------------------------------------------------------------------------------
+def _synthetic(u, fs, dur_s=0.4):
+    pcm, pm, voi = syn.make_utterance(u, dur_s=dur_s, fs=fs)
+    return (syn.pcm_to_float(pcm), fs, pm, voi)
+
+
+def _sparse_epochs(u, fs, N, dur_s):
+    """A synthetic signal with epochs N/2 + 40 samples apart, voiced and unvoiced in turn: every one-period frame is
+    longer than N (the gain kernel's truncation branch, and past the first N/2 frames' left its wrap of the index)."""
+    x = _synthetic(u, fs, dur_s)[0]
+    pm = np.arange(1, int(x.size // (N // 2 + 40))) * (N // 2 + 40) / float(fs)
+    return (x, fs, np.round(pm, 6), (np.arange(pm.size) % 2).astype(np.float64))
+
+
+def _silent(fs, dur_s=0.2):
+    x, _, pm, voi = _synthetic(7, fs, dur_s)
+    return (np.zeros_like(x), fs, pm, voi)
+
+
+def _check_against_model(r, u, N):
+    env, real, imag, f0, fs, shift, gain = r[:7]
+    m = t2m.analysis(*u, N)
+    assert fs == u[1] and env.shape == m["mag2"].shape and real.shape == m["real"].shape
+    np.testing.assert_array_equal(f0, m["f0"])
+    np.testing.assert_array_equal(shift, m["shift"])
+    zero = m["gain"] == 0.0
+    np.testing.assert_array_equal(gain[zero], 0.0)
+    if not zero.all():
+        within(np.max(np.abs(gain[~zero] / m["gain"][~zero] - 1.0)), T2_GAIN_TOL, "T2_GAIN_TOL")
+    nan_ref = (m["mag2"] == 0.0).any(axis=1)   # a magnitude row with a zero bin: an all-NaN envelope row
+    np.testing.assert_array_equal(np.isnan(env).all(axis=1), nan_ref)
+    np.testing.assert_array_equal(np.isnan(env).any(axis=1), nan_ref)
+    if np.max(m["mag1"]) > 0.0:
+        _phase_check(real, imag, m["real"], m["imag"], m["mag1"])
+    else:   # silence: the phasor of a zero bin is 0 (the reference divides by 1 there)
+        within(np.max(np.abs(real - m["real"])), T2_PHASE_TOL, "T2_PHASE_TOL")
+        within(np.max(np.abs(imag - m["imag"])), T2_PHASE_TOL, "T2_PHASE_TOL")
+    return m
+
+
+def _batch_with_warnings(utts, **kw):
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        r = mp.analysis_lossless_type2_batch(utts, **kw)
+    return r, len(w)
+
+
+def test_lossless_type2_8k_fft_1024_against_model():
+    utts = [_synthetic(21, 8000), _synthetic(22, 8000), _sparse_epochs(23, 8000, 1024, 1.0), _silent(8000)]
+    assert hm.define_fft_len(8000) == 1024
+    n_model = 0
+    for u in utts:
+        (r,), n_warn = _batch_with_warnings([u])
+        m = _check_against_model(r, u, 1024)
+        assert n_warn == m["n_warn"]
+        n_model += m["n_warn"]
+    batch, n_warn = _batch_with_warnings(utts)
+    assert n_warn == n_model and n_model >= 10
+    for r, u in zip(batch, utts):
+        m = _check_against_model(r, u, 1024)
+    assert np.all(batch[3][6] == 0.0) and np.isnan(batch[3][0]).all()
+    one = _batch_with_warnings([utts[2]])[0][0]
+    for x, y in zip(one, batch[2]):
+        np.testing.assert_array_equal(x, y)
+
+
+def test_lossless_type2_batch_of_mixed_sample_rates_against_model():
+    N = 2048
+    utts = [_synthetic(31, 48000), _synthetic(32, 16000), _synthetic(33, 8000), _sparse_epochs(34, 16000, N, 1.2),
+            _silent(48000), _synthetic(35, 8000, 0.25)]
+    batch, n_warn = _batch_with_warnings(utts, fft_len=N)
+    n_model = 0
+    for r, u in zip(batch, utts):
+        n_model += _check_against_model(r, u, N)["n_warn"]
+    assert n_warn == n_model
+    assert np.all(batch[4][6] == 0.0) and np.isnan(batch[4][0]).all()

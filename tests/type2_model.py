@@ -39,7 +39,8 @@ def gain(v_sig, p, left, right, voiced, N):
 
 
 def analysis(v_sig, fs, v_pm_sec, v_voi, N):
-    """-> dict: mag2 / mag1 (|X| of the two- / one-period frames), real, imag, f0, shift, gain; row 0 dropped as the reference does."""
+    """-> dict: mag2 / mag1 (|X| of the two- / one-period frames), real, imag, f0, shift, gain; row 0 dropped as the reference
+    does.  n_warn: the frames longer than N, row 0 included -- one warning each in the reference (two- and one-period)."""
     v_sig = np.asarray(v_sig, dtype=np.float64)
     n = v_sig.size
     pm_sec, voi = hm.clean_epochs(v_pm_sec, v_voi, check_len_smpls=n, fs=fs)
@@ -56,4 +57,5 @@ def analysis(v_sig, fs, v_pm_sec, v_voi, N):
     with np.errstate(divide="ignore", invalid="ignore"):
         f0 = voi * fs / left.astype(np.float64)
     return {"mag2": np.abs(X2)[1:], "mag1": mag1[1:], "real": real[1:], "imag": imag[1:], "f0": f0[1:],
-            "shift": np.diff(np.hstack((0, pm_smpls[1:]))), "gain": g[1:], "pm": pm, "left2": l2, "right2": r2}
+            "shift": np.diff(np.hstack((0, pm_smpls[1:]))), "gain": g[1:], "pm": pm, "left2": l2, "right2": r2,
+            "n_warn": int(np.sum(l2 + r2 + 1 > N) + np.sum(left + right + 1 > N))}
