@@ -213,10 +213,14 @@ __global__ __launch_bounds__(256) void k_epoch_crossings(const double* __restric
     const int k = atomicAdd(&cnt[2 * u + p], 1);
     if (k >= cap) return;
     const double* c = c2 + off[u];
+    // The centre q of the two windows is moved inwards so that both fit; an utterance shorter than 2 w + 1 samples has no
+    // such centre: q stays at i and the windows are cut at the utterance's ends (every index into c within [-1, n - 1],
+    // c[-1] = 0).  From 2 w + 1 samples on no index is clamped.
     long long q = i;
-    q = q < w_score ? w_score : (q > n - w_score - 1 ? n - w_score - 1 : q);
+    if (n >= 2 * (long long)w_score + 1) q = q < w_score ? w_score : (q > n - w_score - 1 ? n - w_score - 1 : q);
+    const long long iq = min(q - 1, n - 1), ip = min(q + w_score - 1, n - 1), im = min(q - w_score - 1, n - 1);
     // torch form: c = [0, cumsum(dx^2)]; (c[q + w] - c[q]) - (c[q] - c[q - w])  ->  inclusive sums shifted by one
-    const double cq = c[q - 1], cp = c[q + w_score - 1], cm = (q - w_score - 1 >= 0) ? c[q - w_score - 1] : 0.0;
+    const double cq = iq >= 0 ? c[iq] : 0.0, cp = ip >= 0 ? c[ip] : 0.0, cm = im >= 0 ? c[im] : 0.0;
     const long long slot = (long long)(2 * u + p) * cap + k;
     idx[slot] = (int)i;
     // where between samples i - 1 and i the line through the two values crosses zero, as a fraction of the step back from i

@@ -8,7 +8,8 @@ reference's bundled natural recordings, tests/test_epochs.py).  It is never subs
 only after magphase.use_builtin_epoch_tracker() or with MAGPHASE_EPOCHS=builtin.  It produces what
 read_reaper_est_file returns -- epoch times in seconds and a 0/1 voicing flag per epoch, with marks every 5 ms in
 unvoiced regions (REAPER's `-u 0.005`) -- in two stages, both batched HIP kernels behind the C ABI
-(csrc/magphase_epochs.hip; there is no CPU path):
+(csrc/magphase_epochs.hip; there is no CPU path -- tests/epochs_model.py is a numpy model of each kernel, for the tests
+only):
 
   1. F0 / voicing track (mpx_epoch_f0_track): normalised cross-correlation on the signal box-decimated to ~4 kHz, 40 ms
      frames every 5 ms, lags for 60-400 Hz (REAPER's -m 50 -x 400 range); the host median-smooths the per-frame
@@ -39,6 +40,96 @@ def _geometry(fs, hop_s=0.005, win_s=0.040, f_lo=60.0, f_hi=400.0):
     win = int(round(win_s * fs_d))
     l_min, l_max = max(2, int(fs_d / f_hi)), int(np.ceil(fs_d / f_lo))
     return dec, fs_d, hop, win, l_min, l_max
+
+
+def _voicing_from_candidates(f0, peak, e_ref, fs, nccf_min=0.5, energy_db=-45.0):
+    """Host half of stage 1 for one utterance: the per-frame candidates of mpx_epoch_f0_track (float64 arrays [T]) ->
+    (f0 track [T], 0 in unvoiced frames; half_win of the zero-frequency filter's moving mean: ~1.5 median pitch periods,
+    1 without a voiced frame)."""
+    e_db = 10.0 * np.log10(e_ref / (e_ref.max() + 1e-30) + 1e-30)
+    voiced = (peak > nccf_min) & (e_db > energy_db)
+    voiced = _median5(voiced.astype(np.float64)) > 0.5           # isolated flips / octave slips
+    f0 = np.where(voiced, _median5(f0), 0.0)
+    half_win = 1
+    if voiced.any():
+        t0 = float(np.median(1.0 / f0[voiced]))
+        half_win = (int(round(1.5 * t0 * fs)) | 1) // 2
+    return f0, half_win
+
+
+def _epochs_from_crossings(n, fs, f0_h, cnt, idx_h, slope_h, score_h, frac_h, cap, hop_s, win_s, unvoiced_step_s=0.005):
+    """Host half of stage 2 for one utterance of n samples: the F0 track of _voicing_from_candidates and the two crossing
+    lists of mpx_epoch_zff (cnt [2] as counted on the device, idx_h / slope_h / score_h / frac_h [2, cap], unordered) ->
+    (v_pm_sec, v_voi)."""
+    dur = n / float(fs)
+    voiced_fr = f0_h > 0
+    if not voiced_fr.any():
+        t = np.arange(unvoiced_step_s, dur - 2.0 / fs, unvoiced_step_s)
+        return np.round(t, 6), np.zeros(t.size)
+    # polarity: at a closure instant the vocal-tract response is (re-)excited -- the signal energy in the millisecond
+    # after it exceeds the energy in the millisecond before; half a period later it is just decaying
+    best, cand = -1e30, (np.zeros(0, dtype=np.int64), np.zeros(0), np.zeros(0))
+    for p in (0, 1):
+        k = min(int(cnt[p]), cap)
+        if k == 0:
+            continue
+        sc = float(score_h[p, :k].mean())
+        if sc > best:
+            order = np.argsort(idx_h[p, :k], kind="stable")
+            best, cand = sc, (idx_h[p, :k][order].astype(np.int64), slope_h[p, :k][order], frac_h[p, :k][order])
+    idx, slope, frac = cand
+    # Epoch time = the sub-sample zero of the filtered signal, plus the filter chain's own advance: every inclusive
+    # cumulative sum 1 / (1 - z^-1) leads the integrator it stands for by half a sample (four of them: two zero-frequency
+    # resonators), the first difference lags by half a sample -- 1.5 samples early in all, at any rate; the moving-mean
+    # removals are symmetric.  (Round 5: whole-sample crossings and no compensation gave -130 us at 16 kHz against
+    # synthetic truth, two samples; the rest of that figure is the test generator's own vocal-tract resonators, whose
+    # group delay at zero frequency is -1 sample each plus B / (2 pi f^2) seconds: tools/epoch_natural.py --bias-model.)
+    t_ep = (idx - frac + ZFF_ADVANCE_SMPLS) / float(fs)
+    # voicing of each crossing: the F0 frame whose centre is nearest
+    fr_of = np.clip(np.round((t_ep - 0.5 * win_s) / hop_s).astype(int), 0, f0_h.size - 1)
+    keep = voiced_fr[fr_of] if idx.size else np.zeros(0, dtype=bool)
+    if keep.any():
+        keep &= slope > 0.15 * np.median(slope[keep])
+    # the period implied by neighbouring crossings must be plausible for the local F0 (drops spurious crossings)
+    t_v = t_ep[keep]
+    f_v = f0_h[fr_of[keep]] if idx.size else np.zeros(0)
+    if t_v.size > 2:
+        # A crossing much closer to its predecessor than the crossings around it are to theirs is spurious.  The
+        # yardstick is the filter's OWN rhythm (median of the seven intervals around it), not the F0 track: where the
+        # correlation stage locks onto the double period (an octave error: F0 frames of 73 Hz for a 146 Hz voice),
+        # "closer than half the F0 period" dropped every second epoch of the stretch -- round 3's 8 % misses sat in the
+        # MIDDLE of voiced runs, with the crossing present and kept, not at voicing boundaries.  (Growing the voiced
+        # runs outwards by the filter's crossings was tried as well: no more identified cycles, twice the voicing error.)
+        dt = np.diff(t_v)
+        pad = np.r_[dt[:3][::-1], dt, dt[-3:][::-1]] if dt.size >= 3 else np.r_[dt, dt, dt, dt, dt, dt, dt][:dt.size + 6]
+        local = np.median(np.lib.stride_tricks.sliding_window_view(pad, 7), axis=1)
+        p_f0 = 1.0 / np.maximum(f_v[1:], 50.0)
+        # (never longer than the F0 track's period; never shorter than half of it -- an octave error at worst -- so
+        # that the noise crossings the correlation stage's 40 ms frames let through next to a voiced stretch, which
+        # have no rhythm of their own, are still thinned out)
+        local = np.maximum(np.minimum(local, p_f0), 0.5 * p_f0)
+        good = np.ones(t_v.size, dtype=bool)
+        good[1:][dt < 0.5 * local] = False
+        t_v = t_v[good]
+    # unvoiced marks every 5 ms outside voiced runs (REAPER -u 0.005); a voiced run ends when the next epoch is more
+    # than 20 ms away (1 / 50 Hz)
+    pm, voi = [], []
+    t_prev, max_gap = 0.0, 1.0 / 50.0
+    for k in range(t_v.size + 1):
+        t_next = t_v[k] if k < t_v.size else dur
+        if t_next - t_prev > max_gap:
+            t = t_prev + unvoiced_step_s
+            while t < t_next - 0.5 * unvoiced_step_s:
+                pm.append(t)
+                voi.append(0.0)
+                t += unvoiced_step_s
+        if k < t_v.size:
+            pm.append(t_next)
+            voi.append(1.0)
+            t_prev = t_next
+    pm, voi = np.asarray(pm), np.asarray(voi)
+    ok = (pm > 0) & (pm * fs < n - 2)
+    return np.round(pm[ok], 6), voi[ok]
 
 
 def track_epochs_batch(sigs, fs, engine=None, unvoiced_step_s=0.005, nccf_min=0.5, energy_db=-45.0):
@@ -77,7 +168,8 @@ def track_epochs_batch(sigs, fs, engine=None, unvoiced_step_s=0.005, nccf_min=0.
     d = e.to_device_packed([("off", off, np.int64), ("doff", doff, np.int64), ("foff", foff, np.int64)])
     xd = torch.empty(max(int(doff[-1]), 1), dtype=torch.float64, device=e.device)
     means = torch.empty(2 * U, dtype=torch.float64, device=e.device)
-    f0_d, pk_d, en_d = (torch.empty(max(int(foff[-1]), 1), dtype=torch.float32, device=e.device) for _ in range(3))
+    # zeros: the entries launch nothing for a batch without a decimated sample or without any sample, and the host reads these
+    f0_d, pk_d, en_d = (torch.zeros(max(int(foff[-1]), 1), dtype=torch.float32, device=e.device) for _ in range(3))
     e.launch("mpx_epoch_f0_track", sig, d["off"], U, dec, d["doff"], int(nd.max()), xd, means, d["foff"], int(T.max()), hop,
              win, l_min, n_lags, float(fs_d), f0_d, pk_d, en_d)
     f0_all, pk_all, en_all = (t.cpu().numpy().astype(np.float64) for t in (f0_d, pk_d, en_d))
@@ -87,22 +179,15 @@ def track_epochs_batch(sigs, fs, engine=None, unvoiced_step_s=0.005, nccf_min=0.
     f0_tracks, half_win = [], np.ones(U, dtype=np.int32)
     for u in range(U):
         a, b = int(foff[u]), int(foff[u + 1])
-        f0, peak, e_ref = f0_all[a:b], pk_all[a:b], en_all[a:b]
-        e_db = 10.0 * np.log10(e_ref / (e_ref.max() + 1e-30) + 1e-30)
-        voiced = (peak > nccf_min) & (e_db > energy_db)
-        voiced = _median5(voiced.astype(np.float64)) > 0.5           # isolated flips / octave slips
-        f0 = np.where(voiced, _median5(f0), 0.0)
+        f0, half_win[u] = _voicing_from_candidates(f0_all[a:b], pk_all[a:b], en_all[a:b], fs, nccf_min, energy_db)
         f0_tracks.append(f0)
-        if voiced.any():
-            t0 = float(np.median(1.0 / f0[voiced]))
-            half_win[u] = (int(round(1.5 * t0 * fs)) | 1) // 2
     # ---- zero-frequency filtering for the utterances that have voiced frames
     n_max = int(lens.max())
     cap = n_max // 16 + 64
     w = max(2, int(round(0.001 * fs)))
     total = max(int(off[-1]), 1)
     bufs = [torch.empty(total, dtype=torch.float64, device=e.device) for _ in range(3)]
-    counts = torch.empty(2 * U, dtype=torch.int32, device=e.device)
+    counts = torch.zeros(2 * U, dtype=torch.int32, device=e.device)
     c_idx = torch.zeros(2 * U * cap, dtype=torch.int32, device=e.device)
     c_slope, c_score, c_frac = (torch.zeros(2 * U * cap, dtype=torch.float32, device=e.device) for _ in range(3))
     d_half = e.to_device(half_win, np.int32)
@@ -116,79 +201,9 @@ def track_epochs_batch(sigs, fs, engine=None, unvoiced_step_s=0.005, nccf_min=0.
 
     out = []
     for u in range(U):
-        n = int(lens[u])
-        dur = n / float(fs)
-        f0_h = f0_tracks[u]
-        voiced_fr = f0_h > 0
-        if not voiced_fr.any():
-            t = np.arange(unvoiced_step_s, dur - 2.0 / fs, unvoiced_step_s)
-            out.append((np.round(t, 6), np.zeros(t.size)))
-            continue
-        # polarity: at a closure instant the vocal-tract response is (re-)excited -- the signal energy in the millisecond
-        # after it exceeds the energy in the millisecond before; half a period later it is just decaying
-        best, cand = -1e30, (np.zeros(0, dtype=np.int64), np.zeros(0), np.zeros(0))
-        for p in (0, 1):
-            k = min(int(cnt[2 * u + p]), cap)
-            if k == 0:
-                continue
-            sc = float(score_h[2 * u + p, :k].mean())
-            if sc > best:
-                order = np.argsort(idx_h[2 * u + p, :k], kind="stable")
-                best, cand = sc, (idx_h[2 * u + p, :k][order].astype(np.int64), slope_h[2 * u + p, :k][order],
-                                  frac_h[2 * u + p, :k][order])
-        idx, slope, frac = cand
-        # Epoch time = the sub-sample zero of the filtered signal, plus the filter chain's own advance: every inclusive
-        # cumulative sum 1 / (1 - z^-1) leads the integrator it stands for by half a sample (four of them: two zero-frequency
-        # resonators), the first difference lags by half a sample -- 1.5 samples early in all, at any rate; the moving-mean
-        # removals are symmetric.  (Round 5: whole-sample crossings and no compensation gave -130 us at 16 kHz against
-        # synthetic truth, two samples; the rest of that figure is the test generator's own vocal-tract resonators, whose
-        # group delay at zero frequency is -1 sample each plus B / (2 pi f^2) seconds: tools/epoch_natural.py --bias-model.)
-        t_ep = (idx - frac + ZFF_ADVANCE_SMPLS) / float(fs)
-        # voicing of each crossing: the F0 frame whose centre is nearest
-        fr_of = np.clip(np.round((t_ep - 0.5 * win_s) / hop_s).astype(int), 0, f0_h.size - 1)
-        keep = voiced_fr[fr_of] if idx.size else np.zeros(0, dtype=bool)
-        if keep.any():
-            keep &= slope > 0.15 * np.median(slope[keep])
-        # the period implied by neighbouring crossings must be plausible for the local F0 (drops spurious crossings)
-        t_v = t_ep[keep]
-        f_v = f0_h[fr_of[keep]] if idx.size else np.zeros(0)
-        if t_v.size > 2:
-            # A crossing much closer to its predecessor than the crossings around it are to theirs is spurious.  The
-            # yardstick is the filter's OWN rhythm (median of the seven intervals around it), not the F0 track: where the
-            # correlation stage locks onto the double period (an octave error: F0 frames of 73 Hz for a 146 Hz voice),
-            # "closer than half the F0 period" dropped every second epoch of the stretch -- round 3's 8 % misses sat in the
-            # MIDDLE of voiced runs, with the crossing present and kept, not at voicing boundaries.  (Growing the voiced
-            # runs outwards by the filter's crossings was tried as well: no more identified cycles, twice the voicing error.)
-            dt = np.diff(t_v)
-            pad = np.r_[dt[:3][::-1], dt, dt[-3:][::-1]] if dt.size >= 3 else np.r_[dt, dt, dt, dt, dt, dt, dt][:dt.size + 6]
-            local = np.median(np.lib.stride_tricks.sliding_window_view(pad, 7), axis=1)
-            p_f0 = 1.0 / np.maximum(f_v[1:], 50.0)
-            # (never longer than the F0 track's period; never shorter than half of it -- an octave error at worst -- so
-            # that the noise crossings the correlation stage's 40 ms frames let through next to a voiced stretch, which
-            # have no rhythm of their own, are still thinned out)
-            local = np.maximum(np.minimum(local, p_f0), 0.5 * p_f0)
-            good = np.ones(t_v.size, dtype=bool)
-            good[1:][dt < 0.5 * local] = False
-            t_v = t_v[good]
-        # unvoiced marks every 5 ms outside voiced runs (REAPER -u 0.005); a voiced run ends when the next epoch is more
-        # than 20 ms away (1 / 50 Hz)
-        pm, voi = [], []
-        t_prev, max_gap = 0.0, 1.0 / 50.0
-        for k in range(t_v.size + 1):
-            t_next = t_v[k] if k < t_v.size else dur
-            if t_next - t_prev > max_gap:
-                t = t_prev + unvoiced_step_s
-                while t < t_next - 0.5 * unvoiced_step_s:
-                    pm.append(t)
-                    voi.append(0.0)
-                    t += unvoiced_step_s
-            if k < t_v.size:
-                pm.append(t_next)
-                voi.append(1.0)
-                t_prev = t_next
-        pm, voi = np.asarray(pm), np.asarray(voi)
-        ok = (pm > 0) & (pm * fs < n - 2)
-        out.append((np.round(pm[ok], 6), voi[ok]))
+        r = slice(2 * u, 2 * u + 2)
+        out.append(_epochs_from_crossings(int(lens[u]), fs, f0_tracks[u], cnt[r], idx_h[r], slope_h[r], score_h[r], frac_h[r],
+                                          cap, hop_s, win_s, unvoiced_step_s))
     return out
 
 

@@ -172,8 +172,9 @@ def test_natural_recordings_against_label_voicing(capsys):
               % (", ".join("%s %.4f" % kv for kv in pooled.items()), min(r["agreement"] for r in rows),
                  " ".join("%.0f" % r["f0_median_hz"] for r in rows)))
     assert all(r["voiced_points"] > 80 and r["unvoiced_points"] > 80 for r in rows)
-    # measured on MI355X (profiles/r06_epoch_natural.json): see the bounds' margins there
-    assert pooled["agreement"] > 0.90 and pooled["voiced_recall"] > 0.88 and pooled["unvoiced_recall"] > 0.90
-    assert min(r["agreement"] for r in rows) > 0.80
-    assert pooled["f0_jump_rate"] < 0.06
+    # measured on MI355X: agreement 0.9745, voiced recall 0.9707, unvoiced recall 0.9769, worst file 0.9537, F0 jump rate
+    # 0.0109 -- the figures of profiles/r06_epoch_natural.json to every printed digit.  The bounds sit 0.03 from them.
+    assert pooled["agreement"] > 0.945 and pooled["voiced_recall"] > 0.941 and pooled["unvoiced_recall"] > 0.947
+    assert min(r["agreement"] for r in rows) > 0.924
+    assert pooled["f0_jump_rate"] < 0.04
     assert all(60.0 < r["f0_median_hz"] < 400.0 for r in rows)
