@@ -316,6 +316,17 @@ int mpx_analysis_lossless_backward(void* stream, int fft_len, const void* tables
  * mpx_roundtrip_slot_weights).
  */
 int mpx_roundtrip_slot_weights(float* weights_host, int32_t n_slots); /* as mpx_synth_comp_slot_weights, for this kernel */
+/*
+ * What the planner deals this kernel's frames by (mpx_host_deal_cuts).  mpx_roundtrip_frame_terms: per frame the terms
+ * (1, active_rows, extra_tiles) of its cost -- the 128-sample register rows the analysis gathers, summed over the frame's
+ * sample tiles, and the tiles after the first -- from the frame's host tables; terms_host: int32 [n_frames][3].
+ * mpx_roundtrip_slot_costs: per slot the integer coefficients (a, b, c) of those terms, by the age class of the slot's
+ * wave pair (10 ns of wall clock; fitted on the MI355X); coef_host: int32 [n_slots][3].  Frame f costs
+ * slot s  a_s + b_s rows_f + c_s extra_f.  Host functions: no stream, no device.
+ */
+int mpx_roundtrip_frame_terms(int fft_len, const int32_t* frame_left, const int32_t* frame_right, int64_t n_frames,
+                              int32_t* terms_host);
+int mpx_roundtrip_slot_costs(int32_t* coef_host, int32_t n_slots);
 int mpx_roundtrip_lossless_ola(void* stream, int fft_len, const void* tables, const float* sig, const int64_t* frame_pos,
                                const int32_t* frame_left, const int32_t* frame_right, int64_t n_frames,
                                const mpx_ola_run* runs, int32_t n_runs, const int32_t* slot_off, const int32_t* slot_runs,
@@ -859,6 +870,17 @@ int64_t mpx_host_plan_lossless_synthesis(int32_t n_utts, const double* f0, const
 int64_t mpx_host_ola_runs(int32_t n_utts, const int64_t* pm_rel, const int64_t* frame_off, const int64_t* starts,
                           const int64_t* out_lens, const int64_t* out_offs, int32_t fft_len, const int64_t* gcuts,
                           int64_t n_gcuts, mpx_ola_run* runs, int64_t cap_runs);
+
+/*
+ * mpx_host_deal_cuts: cuts for mpx_host_ola_runs that deal the frames by COST instead of by count.  Frame f costs slot s
+ * sum_k coef[s][k] * terms[f][k] (terms: int32 [n_frames][n_terms], coef: int32 [n_slots][n_terms], none negative; the
+ * sums are int64).  Finds the smallest integer T for which the greedy fill -- slots 0, 1, ... each take the longest run of
+ * consecutive frames whose summed cost is <= T -- consumes every frame, and writes that fill's cuts: cuts[0] == 0,
+ * ascending, cuts[n_slots] == n_frames (trailing slots may be empty); *t_out = T (may be null).  Integer arithmetic only:
+ * bit-identical to hostmath.deal_cuts.  Returns 0, or -1 on bad arguments.
+ */
+int64_t mpx_host_deal_cuts(const int32_t* terms, int64_t n_frames, int32_t n_terms, const int32_t* coef, int32_t n_slots,
+                           int64_t* cuts, int64_t* t_out);
 
 /*
  * mpx_host_plan_synthesis_batch: the whole host side of a compressed-feature synthesis launch (what the reference does per

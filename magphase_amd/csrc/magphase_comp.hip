@@ -129,11 +129,11 @@ template <int P, bool PRESTAGED = false, bool COMPACT = false>   // PRESTAGED: t
 __device__ __forceinline__ void noise_fft(const FrameGeom& g, int wtype, const float* tw, float* xbuf,
                                           unsigned xbuf_byte, int lane, float (&re)[P], float (&im)[P], float lc = 1.0f,
                                           float ls = 0.0f) {
-    constexpr int M = 64 * P, N = 2 * M, kTile = COMPACT ? 32 * P : 64 * P;
+    constexpr int M = 64 * P, N = 2 * M, kTile = noise_tile_len(P, COMPACT);
     MPX_MARK("zero_init");
 #pragma unroll
     for (int j = 0; j < P; ++j) re[j] = im[j] = 0.0f;
-    const int ntiles = (g.len + kTile - 1) / kTile;
+    const int ntiles = MPX_NOISE_TILES(g.len, kTile);   // (mpx_common.hpp: the planner's cost terms count the same tiles and rows)
     for (int t = 0; t < ntiles; ++t) {
         MPX_MARK("window");
         const int tile0 = t * kTile;
@@ -167,7 +167,7 @@ __device__ __forceinline__ void noise_fft(const FrameGeom& g, int wtype, const f
             for (int j = 0; j < P; ++j) {
                 constexpr int LBJ = ilog2(P);
                 const int m0 = 128 * j;
-                if ((m0 < n_lo) || (m0 + 127 >= n_hi)) {
+                if (MPX_NOISE_ROW_ACTIVE(m0, n_lo, n_hi)) {
                     const int rj = (COMPACT && MPX_COMP_DIT) ? brev(j, LBJ) : j;   // the DIT form wants register brev(j) <- z[l + 64 j]
                     // sample index relative to the tile, modulo N (tile0 is a multiple of the tile length, which divides N)
                     const unsigned d0 = (b0 + (unsigned)m0) & (unsigned)(N - 1), d1 = (d0 + 1u) & (unsigned)(N - 1);
@@ -1506,6 +1506,13 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_synth_comp_pair(const f
 // transform).  Both are held to the two-launch path's tolerances against the oracle.
 // Every frame index of [0, n_frames) must belong to exactly one run: a frame outside the runs is not analysed.
 // ---------------------------------------------------------------------------------------------
+#ifdef MPX_PROBE_ENDTIME
+// Probe build (tools/roundtrip_deal_probe.py), as k_synth_ola_pair's in magphase_hip.hip: every wave of k_roundtrip_pair
+// stores the constant-rate clock (100 MHz) when it enters and when it leaves its frame loop, its frame count and its
+// shader cycles -- per slot (= wave pair), the later of the two ends is when the slot's share was done.
+__device__ unsigned long long g_rt_endprobe[4 * 8192];   // per wave: start, end (100 MHz clock), frames, shader cycles
+#endif
+
 template <int P>
 __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const float* __restrict__ sig,
                                                                        const long long* __restrict__ fpos,
@@ -1528,6 +1535,11 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
     FrameGeom g = frame_geom(sig, fpos[cur.fi], fleft[cur.fi], fright[cur.fi], N);
     pair_stage_frame<P>(w, g, w.lane_id);
 
+#ifdef MPX_PROBE_ENDTIME
+    const unsigned long long probe_t0 = wall_clock64();
+    const unsigned long long probe_c0 = clock64();
+    int probe_frames = 0;
+#endif
     while (cur.valid) {
         int lane;
         float wa_s, wa_c, ws_s, ws_c;
@@ -1629,7 +1641,19 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
         // ROT: rows taken half a transform apart, the fftshift
         pair_ordered_ola<P, true>(w, cur, smem, runs, pm_rel, strips, pcm, xr, xi, lane, plain_add, all_rows);
         cur = nxt;
+#ifdef MPX_PROBE_ENDTIME
+        ++probe_frames;
+#endif
     }
+#ifdef MPX_PROBE_ENDTIME
+    if (w.lane_id == 0) {
+        const int pw = (blockIdx.x * kCompPairWaves + (int)(threadIdx.x >> 6)) % 8192;
+        g_rt_endprobe[4 * pw + 0] = probe_t0;
+        g_rt_endprobe[4 * pw + 1] = wall_clock64();
+        g_rt_endprobe[4 * pw + 2] = (unsigned long long)probe_frames;
+        g_rt_endprobe[4 * pw + 3] = clock64() - probe_c0;
+    }
+#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2623,6 +2647,77 @@ int mpx_roundtrip_slot_weights(float* weights_host, int32_t n_slots) {
     }
     return MPX_OK;
 }
+
+// Cost model of k_roundtrip_pair's frames, for the planner that deals them to the slots (hostmath.deal_cuts /
+// mpx_host_deal_cuts): frame f costs slot s  a_s + b_s rows_f + c_s extra_f  with (1, rows_f, extra_f) = frame_cost_terms --
+// the rows noise_fft's gather visits and the tiles it stages synchronously, counted by the functions the kernel itself
+// calls -- and (a, b, c) by the age class of the slot's wave pair (the rule of mpx_roundtrip_slot_weights).  Unit: 10 ns of
+// wall clock per frame of the pair's share (its two waves alternate over the share).  Uncalibrated, a = 100 / 141 / 200 and
+// b = c = 0 deal by frame count in the proportions of MPX_RT_W1 / MPX_RT_W2 = 71 / 50.
+#ifndef MPX_RT_COST_A0
+#define MPX_RT_COST_A0 793
+#endif
+#ifndef MPX_RT_COST_A1
+#define MPX_RT_COST_A1 1039
+#endif
+#ifndef MPX_RT_COST_A2
+#define MPX_RT_COST_A2 1514
+#endif
+#ifndef MPX_RT_COST_B0
+#define MPX_RT_COST_B0 14
+#endif
+#ifndef MPX_RT_COST_B1
+#define MPX_RT_COST_B1 16
+#endif
+#ifndef MPX_RT_COST_B2
+#define MPX_RT_COST_B2 15
+#endif
+#ifndef MPX_RT_COST_C0
+#define MPX_RT_COST_C0 0
+#endif
+#ifndef MPX_RT_COST_C1
+#define MPX_RT_COST_C1 0
+#endif
+#ifndef MPX_RT_COST_C2
+#define MPX_RT_COST_C2 0
+#endif
+int mpx_roundtrip_slot_costs(int32_t* coef_host, int32_t n_slots) {
+    if (!coef_host || n_slots < 0) return fail(MPX_ERR_ARG, "mpx_roundtrip_slot_costs: bad arguments%s");
+    static const int32_t kCost[3][3] = {{MPX_RT_COST_A0, MPX_RT_COST_B0, MPX_RT_COST_C0},
+                                        {MPX_RT_COST_A1, MPX_RT_COST_B1, MPX_RT_COST_C1},
+                                        {MPX_RT_COST_A2, MPX_RT_COST_B2, MPX_RT_COST_C2}};
+    for (int s = 0; s < n_slots; ++s) {
+        const int age = ((s % kCompPairs) * 2) / 4;
+        for (int k = 0; k < 3; ++k) coef_host[3 * s + k] = kCost[age][k];
+    }
+    return MPX_OK;
+}
+
+int mpx_roundtrip_frame_terms(int fft_len, const int32_t* frame_left, const int32_t* frame_right, int64_t n_frames,
+                              int32_t* terms_host) {
+    const int P = p_of(fft_len);
+    if (!P) return fail(MPX_ERR_ARG, "mpx_roundtrip_frame_terms: fft_len must be 1024, 2048 or 4096%s");
+    if (n_frames < 0 || (n_frames > 0 && (!frame_left || !frame_right || !terms_host)))
+        return fail(MPX_ERR_ARG, "mpx_roundtrip_frame_terms: bad arguments%s");
+    const bool compact = (P == 32) && comp_compact<32>();   // the kernel's own choice of tile
+    for (int64_t f = 0; f < n_frames; ++f) {
+        int t[3];
+        frame_cost_terms(frame_left[f], frame_right[f], fft_len, P, compact, t);
+        terms_host[3 * f + 0] = t[0];
+        terms_host[3 * f + 1] = t[1];
+        terms_host[3 * f + 2] = t[2];
+    }
+    return MPX_OK;
+}
+
+#ifdef MPX_PROBE_ENDTIME
+int mpx_probe_rt_endtimes(unsigned long long* host, int n_words) {   // probe builds only (not part of the ABI)
+    if (!host || n_words < 0 || n_words > 4 * 8192) return fail(MPX_ERR_ARG, "mpx_probe_rt_endtimes: bad arguments%s");
+    MPX_HIP_CHECK(hipDeviceSynchronize());
+    MPX_HIP_CHECK(hipMemcpyFromSymbol(host, HIP_SYMBOL(g_rt_endprobe), sizeof(unsigned long long) * (size_t)n_words));
+    return MPX_OK;
+}
+#endif
 
 int mpx_roundtrip_lossless_ola(void* stream, int fft_len, const void* tables, const float* sig, const int64_t* frame_pos,
                                const int32_t* frame_left, const int32_t* frame_right, int64_t n_frames,

@@ -531,6 +531,73 @@ int64_t mpx_host_ola_runs(int32_t n_utts, const int64_t* pm_rel, const int64_t* 
     return nr;
 }
 
+// hostmath.deal_cuts: consecutive shares of the frame sequence whose LARGEST slot cost is minimal.  Frame f costs slot s
+// sum_k coef[s][k] * terms[f][k] (int64; terms and coef must not be negative).  The smallest integer T for which the
+// greedy fill consumes every frame -- slots 0, 1, ... each take the longest run of consecutive frames whose summed cost
+// is <= T -- found by bisection (a larger T never consumes fewer frames); cuts = that fill's, ascending, cuts[0] == 0,
+// cuts[n_slots] == n_frames, trailing slots may be empty.  Slots with equal coefficients share one prefix-sum array, so a
+// fill is one search per slot.  Returns 0, or -1 on bad arguments.
+int64_t mpx_host_deal_cuts(const int32_t* terms, int64_t n_frames, int32_t n_terms, const int32_t* coef, int32_t n_slots,
+                           int64_t* cuts, int64_t* t_out) {
+    if (n_frames < 0 || n_terms < 1 || n_slots < 1 || !coef || !cuts || (n_frames > 0 && !terms)) return -1;
+    for (int64_t i = 0; i < n_frames * n_terms; ++i)
+        if (terms[i] < 0) return -1;
+    for (int64_t i = 0; i < (int64_t)n_slots * n_terms; ++i)
+        if (coef[i] < 0) return -1;
+    // distinct coefficient rows, in order of first appearance
+    std::vector<int32_t> cls((size_t)n_slots);
+    std::vector<int32_t> first;
+    for (int32_t s = 0; s < n_slots; ++s) {
+        size_t c = 0;
+        for (; c < first.size(); ++c)
+            if (std::equal(coef + (size_t)s * n_terms, coef + (size_t)(s + 1) * n_terms, coef + (size_t)first[c] * n_terms)) break;
+        if (c == first.size()) first.push_back(s);
+        cls[(size_t)s] = (int32_t)c;
+    }
+    // prefix[c][i] = cost of the frames [0, i) in a slot of class c
+    const size_t stride = (size_t)n_frames + 1;
+    std::vector<int64_t> prefix(first.size() * stride);
+    int64_t hi = 0;
+    for (size_t c = 0; c < first.size(); ++c) {
+        const int32_t* k = coef + (size_t)first[c] * n_terms;
+        int64_t* p = prefix.data() + c * stride;
+        p[0] = 0;
+        for (int64_t f = 0; f < n_frames; ++f) {
+            int64_t v = 0;
+            for (int32_t j = 0; j < n_terms; ++j) v += (int64_t)k[j] * (int64_t)terms[f * n_terms + j];
+            p[f + 1] = p[f] + v;
+        }
+        hi = std::max(hi, p[n_frames]);   // with T = the dearest class's cost of the whole batch, slot 0 takes everything
+    }
+    auto fill = [&](int64_t T, int64_t* out) -> bool {   // the greedy fill; out (if given) receives its cuts
+        int64_t i = 0;
+        if (out) out[0] = 0;
+        for (int32_t s = 0; s < n_slots; ++s) {
+            const int64_t* p = prefix.data() + (size_t)cls[(size_t)s] * stride;
+            // the last j >= i with p[j] - p[i] <= T  (np.searchsorted(p, p[i] + T, side="right") - 1): a share is a few
+            // dozen frames of tens of thousands, so gallop forward from i, then bisect the last stride
+            const int64_t target = p[i] + T;
+            int64_t step = 1;
+            while (i + step <= n_frames && p[i + step] <= target) {
+                i += step;
+                step <<= 1;
+            }
+            i = (std::upper_bound(p + i, p + std::min(i + step, n_frames + 1), target) - p) - 1;
+            if (out) out[s + 1] = i;
+        }
+        return i == n_frames;
+    };
+    int64_t lo = 0;   // smallest T with fill(T): lo <= T <= hi
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (fill(mid, nullptr)) hi = mid;
+        else lo = mid + 1;
+    }
+    fill(lo, cuts);
+    if (t_out) *t_out = lo;
+    return 0;
+}
+
 // hostmath.slot_cuts: frame indices that deal `total` frames to the slots (cuts[0] == 0, n_cuts = ns + 1).  wcum / wsum:
 // np.concatenate(([0.], np.cumsum(w))) and w.sum() of the slots' float64 weights, evaluated by numpy ONCE per engine (the
 // pairwise sum is numpy's); null = equal shares, np.round(np.linspace(0, total, ns + 1)).

@@ -132,12 +132,39 @@ struct FrameGeom {
     float invL, invR;
 };
 
+// Length and rotation of the frame with L samples left and R right of its epoch in an N-point transform, as frame_geom
+// below defines them, for the host (frame_cost_terms).
+__host__ __device__ __forceinline__ int frame_len(int L, int R, int N) { return (L + R + 1 < N) ? L + R + 1 : N; }
+__host__ __device__ __forceinline__ int frame_rot(int L, int N) { return (L < N) ? L : 0; }
+
+// What a frame costs in noise_fft (magphase_comp.hip) besides the fixed part: the samples are staged in tiles of
+// noise_tile_len (every tile after the first synchronously), and per tile the gather visits the 128-sample register rows
+// j < P that hold a sample of the frame -- MPX_NOISE_ROW_ACTIVE(128 j, n_lo, n_hi) with n_lo = len - rot (end of the
+// frame's right half) and n_hi = N - rot (start of its left half).  noise_fft's own tile count and row test ARE these
+// expressions, so the cost model of the round-trip planner (mpx_roundtrip_frame_terms) cannot drift from the kernel.
+// (Macros, not functions: through an inlined function the same two expressions came out of the compiler as other code in
+// every kernel that transforms a staged frame.)
+__host__ __device__ constexpr int noise_tile_len(int P, bool compact) { return compact ? 32 * P : 64 * P; }
+#define MPX_NOISE_TILES(len, tile_len) (((len) + (tile_len) - 1) / (tile_len))
+#define MPX_NOISE_ROW_ACTIVE(m0, n_lo, n_hi) (((m0) < (n_lo)) || ((m0) + 127 >= (n_hi)))
+// terms = (1, active_rows, extra_tiles): active_rows counts the (tile, j) pairs the gather visits, extra_tiles the
+// synchronously staged tiles.
+__host__ __device__ inline void frame_cost_terms(int L, int R, int N, int P, bool compact, int (&terms)[3]) {
+    const int len = frame_len(L, R, N), rot = frame_rot(L, N);
+    const int tile_len = noise_tile_len(P, compact), ntiles = MPX_NOISE_TILES(len, tile_len);
+    int rows = 0;
+    for (int j = 0; j < P; ++j) rows += MPX_NOISE_ROW_ACTIVE(128 * j, len - rot, N - rot) ? 1 : 0;
+    terms[0] = 1;
+    terms[1] = rows * ntiles;
+    terms[2] = ntiles - 1;
+}
+
 __device__ __forceinline__ FrameGeom frame_geom(const float* __restrict__ sig, long long pos, int L, int R, int N) {
     FrameGeom g;
     g.L = L;
     g.LR = L + R;
-    g.len = min(g.LR + 1, N);            // Q19: frames longer than N are truncated
-    g.rot = (L < N) ? L : 0;             // python slicing: rotation by >= N is the identity
+    g.len = min(g.LR + 1, N);            // Q19: frames longer than N are truncated        (== frame_len(L, R, N))
+    g.rot = (L < N) ? L : 0;             // python slicing: rotation by >= N is the identity (== frame_rot(L, N))
     g.kadd = (L == 0) ? 1 : 0;           // L == 0: the single rising sample has weight np.hanning(1) == 1
     g.invL = (L > 0) ? 1.0f / (float)L : 1.0f;
     g.invR = (R > 0) ? 1.0f / (float)R : 0.0f;

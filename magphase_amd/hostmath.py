@@ -294,7 +294,66 @@ def slot_cuts(total, n_slots, weights=None):
     return np.round(total * np.concatenate(([0.0], np.cumsum(w))) / w.sum()).astype(np.int64)
 
 
-def ola_runs(pm_rel_list, starts, out_lens, out_offs, fft_len, n_slots, frames_per_run=None, weights=None):
+def deal_cuts(terms, coef):
+    """Consecutive shares of the frame sequence whose LARGEST slot cost is minimal (the literal form of
+    mpx_host_deal_cuts, bit for bit).  terms: int [n_frames, n_terms], coef: int [n_slots, n_terms], none negative; frame
+    f costs slot s  sum_k coef[s, k] * terms[f, k]  (int64).  The smallest integer T for which the greedy fill -- slots
+    0, 1, ... each take the longest run of consecutive frames whose summed cost is <= T -- consumes every frame, by
+    bisection (a larger T never consumes fewer frames).  Returns (cuts int64[n_slots + 1], T): cuts[0] == 0, ascending,
+    cuts[-1] == n_frames; trailing slots may be empty."""
+    coef = np.asarray(coef, dtype=np.int64)
+    if coef.ndim != 2 or coef.shape[0] < 1 or coef.shape[1] < 1:
+        raise ValueError("deal_cuts: coef must be [n_slots, n_terms]")
+    terms = np.asarray(terms, dtype=np.int64).reshape(-1, coef.shape[1])
+    if np.any(terms < 0) or np.any(coef < 0):
+        raise ValueError("deal_cuts: terms and coefficients must not be negative")
+    n, ns = int(terms.shape[0]), int(coef.shape[0])
+    # slots with equal coefficients share one prefix-sum array: prefix[c][i] = cost of the frames [0, i) in class c
+    rows, cls = [], np.empty(ns, dtype=np.int64)
+    for s in range(ns):
+        key = tuple(coef[s].tolist())
+        if key not in rows:
+            rows.append(key)
+        cls[s] = rows.index(key)
+    prefix = [np.concatenate(([0], np.cumsum(terms @ np.asarray(k, dtype=np.int64)))).astype(np.int64) for k in rows]
+    cls = cls.tolist()
+
+    def fill(T):
+        cuts, i = [0], 0
+        for s in range(ns):
+            p = prefix[cls[s]]
+            i = int(np.searchsorted(p, p[i] + T, side="right")) - 1   # the last j >= i with p[j] - p[i] <= T
+            cuts.append(i)
+        return cuts
+
+    lo, hi = 0, max(int(p[n]) for p in prefix)   # with T = the dearest class's cost of the batch slot 0 takes everything
+    while lo < hi:
+        mid = lo + (hi - lo) // 2
+        if fill(mid)[-1] == n:
+            hi = mid
+        else:
+            lo = mid + 1
+    return np.asarray(fill(lo), dtype=np.int64), lo
+
+
+def roundtrip_frame_terms(left, right, fft_len):
+    """mpx_roundtrip_frame_terms in numpy (what the round-trip plan falls back to without the native planners): per frame
+    (1, active_rows, extra_tiles) of k_roundtrip_pair's analysis -- noise_fft's tile count and row test (csrc/mpx_common.hpp:
+    frame_cost_terms) on len = min(L + R + 1, N), rot = L if L < N else 0, tiles of 32 P samples for P = N / 128 = 32 and
+    64 P otherwise.  int32 [n_frames, 3]."""
+    N = int(fft_len)
+    P = N // 128
+    L, Rr = np.asarray(left, dtype=np.int64).reshape(-1), np.asarray(right, dtype=np.int64).reshape(-1)
+    ln = np.minimum(L + Rr + 1, N)
+    rot = np.where(L < N, L, 0)
+    tile = (32 if P == 32 else 64) * P
+    ntiles = (ln + tile - 1) // tile
+    m0 = 128 * np.arange(P, dtype=np.int64)[None, :]
+    rows = ((m0 < (ln - rot)[:, None]) | (m0 + 127 >= (N - rot)[:, None])).sum(axis=1)
+    return np.stack([np.ones_like(ln), rows * ntiles, ntiles - 1], axis=1).astype(np.int32)
+
+
+def ola_runs(pm_rel_list, starts, out_lens, out_offs, fft_len, n_slots, frames_per_run=None, weights=None, gcuts=None):
     """
     Plans the fused overlap-add (include/magphase_hip.h: mpx_synthesis_lossless_ola).  The batch's frames, in utterance
     order, are dealt to the device's pair slots in consecutive shares: equal ones (slot s gets the frames
@@ -302,6 +361,8 @@ def ola_runs(pm_rel_list, starts, out_lens, out_offs, fft_len, n_slots, frames_p
     speed per slot, mpx_synth_ola_slot_weights), shares in proportion to them -- the kernel ends when the slowest slot does.  A share that crosses an utterance boundary is two (or more) RUNS -- the end
     of one utterance and the beginning of the next; runs never cross utterances.  ``frames_per_run`` instead cuts every
     utterance on its own into runs of about that many frames and balances the slots longest-run-first (tests, tuning).
+    ``gcuts`` (int64[slots + 1], ascending, gcuts[0] == 0, gcuts[-1] == the frame count; equal neighbours = an empty
+    slot) replaces the shares by count: the caller dealt the frames itself (deal_cuts: by cost).
     Per run the positions are classified as head strip / final output / dropped (see mpx_ola_run) in the coordinates
     of the reference's OLA buffer (magphase.py:38-61): frame i covers [pm_rel[i], pm_rel[i] + N), the kept part is
     [start, start + out_len).  Only ADJACENT runs of an utterance may overlap: rel[next run's first frame] -
@@ -322,7 +383,7 @@ def ola_runs(pm_rel_list, starts, out_lens, out_offs, fft_len, n_slots, frames_p
         target, gcuts = int(frames_per_run), None
     else:
         target = max(1, -(-total // n_slots))
-        gcuts = slot_cuts(total, n_slots, weights)
+        gcuts = slot_cuts(total, n_slots, weights) if gcuts is None else np.asarray(gcuts, dtype=np.int64)
     recs = []
     f_base = 0
     for u, rel in enumerate(pm_rel_list):

@@ -105,8 +105,40 @@ def plan_lossless_synthesis(f0_list, fs_list, fft_len):
     return dict(v_pm=v_pm[:F], pm_rel=pm_rel[:F], frame_off=frame_off, out_start=out_start, out_len=out_len)
 
 
-def ola_runs(pm_rel_cat, frame_off, starts, out_lens, out_offs, fft_len, n_slots, weights=None):
-    """hostmath.ola_runs (default equal-share mode) on the concatenated frame positions -> (runs, slot_off, slot_runs)."""
+def deal_cuts(terms, coef):
+    """hostmath.deal_cuts in the library (mpx_host_deal_cuts) -> (cuts int64[n_slots + 1], T)."""
+    if not enabled():
+        raise PlanFallback()
+    lib = _lib.load()
+    coef = np.ascontiguousarray(coef, dtype=np.int32)
+    if coef.ndim != 2 or coef.shape[0] < 1 or coef.shape[1] < 1:
+        raise PlanFallback()
+    terms = np.ascontiguousarray(terms, dtype=np.int32).reshape(-1, coef.shape[1])
+    cuts = np.empty(coef.shape[0] + 1, dtype=np.int64)
+    t = np.zeros(1, dtype=np.int64)
+    if int(lib.mpx_host_deal_cuts(terms.ctypes.data, int(terms.shape[0]), int(coef.shape[1]), coef.ctypes.data,
+                                  int(coef.shape[0]), cuts.ctypes.data, t.ctypes.data)) != 0:
+        raise PlanFallback()
+    return cuts, int(t[0])
+
+
+def roundtrip_frame_terms(left, right, fft_len):
+    """mpx_roundtrip_frame_terms -> int32 [n_frames, 3] (hostmath.roundtrip_frame_terms is the numpy form)."""
+    if not enabled():
+        raise PlanFallback()
+    left, right = np.ascontiguousarray(left, dtype=np.int32), np.ascontiguousarray(right, dtype=np.int32)
+    if left.shape != right.shape or left.ndim != 1:
+        raise PlanFallback()
+    terms = np.empty((left.size, 3), dtype=np.int32)
+    if int(_lib.load().mpx_roundtrip_frame_terms(int(fft_len), left.ctypes.data, right.ctypes.data, int(left.size),
+                                                 terms.ctypes.data)) != 0:
+        raise PlanFallback()
+    return terms
+
+
+def ola_runs(pm_rel_cat, frame_off, starts, out_lens, out_offs, fft_len, n_slots, weights=None, gcuts=None):
+    """hostmath.ola_runs (default equal-share mode, or the caller's gcuts) on the concatenated frame positions ->
+    (runs, slot_off, slot_runs)."""
     if not enabled():
         raise PlanFallback()
     lib = _lib.load()
@@ -114,7 +146,7 @@ def ola_runs(pm_rel_cat, frame_off, starts, out_lens, out_offs, fft_len, n_slots
     U = int(frame_off.size - 1)
     total = int(frame_off[-1])
     n_slots = max(1, int(n_slots))
-    gcuts = np.ascontiguousarray(hm.slot_cuts(total, n_slots, weights))
+    gcuts = np.ascontiguousarray(hm.slot_cuts(total, n_slots, weights) if gcuts is None else gcuts, dtype=np.int64)
     pm_rel = np.ascontiguousarray(pm_rel_cat, dtype=np.int64)
     starts, out_lens, out_offs = (np.ascontiguousarray(a, dtype=np.int64) for a in (starts, out_lens, out_offs))
     cap = U + int(gcuts.size) + 1

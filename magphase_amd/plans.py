@@ -86,9 +86,11 @@ class _FlatRows:
         return (self[u] for u in range(len(self)))
 
 
-def _plan_ola_runs(plan, pm_rel_list, starts, out_lens, out_off_host, fft_len, n_slots, frames_per_run, up, weights=None):
+def _plan_ola_runs(plan, pm_rel_list, starts, out_lens, out_off_host, fft_len, n_slots, frames_per_run, up, weights=None,
+                   gcuts=None):
     """Shared by the two synthesis plans: runs + slot work lists (hostmath.ola_runs / balance_chunks) -> upload list.
-    weights: the slots' relative speeds (Engine.synth_ola_slot_weights) or None for equal shares."""
+    weights: the slots' relative speeds (Engine.synth_ola_slot_weights) or None for equal shares; gcuts: the caller's own
+    cuts of the frame sequence instead of shares by count (hostmath.ola_runs; ignored with frames_per_run)."""
     fpr = frames_per_run or int(os.environ.get("MAGPHASE_OLA_FRAMES_PER_RUN", 0)) or None
     try:
         if fpr:
@@ -102,10 +104,11 @@ def _plan_ola_runs(plan, pm_rel_list, starts, out_lens, out_off_host, fft_len, n
             f_off = np.concatenate(([0], np.cumsum(sizes)))
         runs, slot_off, slot_runs = hostplan.ola_runs(rel_cat, f_off, starts, out_lens,
                                                       np.asarray(out_off_host)[:len(sizes)], fft_len, n_slots,
-                                                      weights=weights)
+                                                      weights=weights, gcuts=gcuts)
     except hostplan.PlanFallback:
         runs, slot_off, slot_runs = hm.ola_runs(pm_rel_list, starts, out_lens, out_off_host, fft_len, n_slots,
-                                                frames_per_run=fpr, weights=None if fpr else weights)
+                                                frames_per_run=fpr, weights=None if fpr else weights,
+                                                gcuts=None if fpr else gcuts)
     plan.n_runs = int(runs.size)
     plan.runs_host = runs
     plan.strip_floats = plan.n_runs * (int(fft_len) + 64)
@@ -168,10 +171,13 @@ class LosslessAnalysisPlan:
     Host math follows magphase.py:2877-2879 (pm_sec*fs), libaudio.py:435-447, magphase.py:77-98, :2198-2199.
     """
 
-    def __init__(self, engine, utts, fft_len=None, prepared=None):
+    def __init__(self, engine, utts, fft_len=None, prepared=None, keep_frame_tabs=False):
         # prepared: a PreparedAnalysis of these utterances (Engine.prepare_analysis, e.g. from the planner thread); None:
         # prepared here when the batch is in the plain shape the native path takes, else the generic path below
+        # keep_frame_tabs: keep a host copy of the frame tables (pos, left, right) in self._host_tabs (LosslessRoundTripPlan
+        # deals its frames by them)
         self.engine = engine
+        self._keep_tabs = bool(keep_frame_tabs)
         utts, on_dev = _signal_inputs(engine, utts)
         if on_dev:      # some v_sig is a tensor on the engine's device: the samples never visit the host
             if prepared is not None:
@@ -296,9 +302,10 @@ class LosslessAnalysisPlan:
             self.sig = _widen_pcm16(e, e.upload_staged((total + 1) // 2 + 2), total)
         else:
             self.sig = e.upload_staged(total) if staged else e.to_device(buf, np.float32)
-        desc = e.to_device_packed([("pos", np.concatenate(pos) if pos else np.zeros(0), np.int64),     # one H2D copy
-                                   ("left", np.concatenate(left) if left else np.zeros(0), np.int32),
-                                   ("right", np.concatenate(right) if right else np.zeros(0), np.int32)])
+        cat = [np.concatenate(x) if x else np.zeros(0) for x in (pos, left, right)]
+        if self._keep_tabs:
+            self._host_tabs = tuple(cat)
+        desc = e.to_device_packed([("pos", cat[0], np.int64), ("left", cat[1], np.int32), ("right", cat[2], np.int32)])     # one H2D copy
         self.pos, self.left, self.right = desc["pos"], desc["left"], desc["right"]
 
     def _from_device(self, engine, utts, fft_len):
@@ -370,6 +377,10 @@ class LosslessAnalysisPlan:
                 self.long_frame_lens[u].append(n)
         F, total = p.total_frames, p.total_smpls
         o_pos, o_left, o_right, o_voi = p.offs
+        if self._keep_tabs:   # (before the slot is handed to the upload: its descriptor block is reused afterwards)
+            d = p.slot["desc_np"]
+            self._host_tabs = tuple(d[o:o + w * F].view(t).copy()
+                                    for o, w, t in ((o_pos, 8, np.int64), (o_left, 4, np.int32), (o_right, 4, np.int32)))
         slot, p.slot = p.slot, None          # from here on the upload's event guards the slot
         sd, dd, ev = e._slot_upload(slot, p.stage_bytes, p.desc_bytes)
         self._ready = ev
@@ -395,8 +406,12 @@ class LosslessSynthesisPlan:
     All float64/int host math; device gets int tables.
     """
 
-    def __init__(self, engine, f0_list, fs_list, fft_len, frames_per_run=None, comp_slots=False):
+    def __init__(self, engine, f0_list, fs_list, fft_len, frames_per_run=None, comp_slots=False, gcuts=None, n_slots=None):
         # comp_slots: the slot count and weights of the compressed / round-trip pair kernels (mpx_synth_comp_slots)
+        # n_slots: overrides the engine's slot count (small tests; the launch grid follows it)
+        # gcuts: the caller's cuts of the frame sequence, one share per slot, or a callable(n_slots, total_frames) that
+        #        returns them or None (LosslessRoundTripPlan deals by cost); None: shares by count
+        n_slots_arg = n_slots
         self.engine = engine
         self.fft_len = fft_len
         pm_rel, starts, lens, nfr = [], [], [], []
@@ -440,7 +455,14 @@ class LosslessSynthesisPlan:
         else:
             n_slots = e.synth_ola_slots() if hasattr(e, "synth_ola_slots") else 1024
             weights = e.synth_ola_slot_weights() if hasattr(e, "synth_ola_slot_weights") else None
-        _plan_ola_runs(self, pm_rel, starts, lens, self.out_off_host, fft_len, n_slots, frames_per_run, _up, weights=weights)
+        if n_slots_arg is not None:
+            n_slots = max(1, int(n_slots_arg))
+            if weights is not None:   # the weights follow the slot's place in its workgroup: the first n_slots of them
+                weights = np.asarray(weights)[:n_slots] if len(weights) >= n_slots else None
+        if callable(gcuts):
+            gcuts = gcuts(n_slots, self.total_frames)
+        _plan_ola_runs(self, pm_rel, starts, lens, self.out_off_host, fft_len, n_slots, frames_per_run, _up, weights=weights,
+                       gcuts=gcuts)
         for _k, _t in e.to_device_packed(_up).items():
             setattr(self, _k, _t)
 
@@ -484,23 +506,58 @@ class LosslessRoundTripPlan:
     and the waveform synthesis_from_lossless builds from them.
     """
 
-    def __init__(self, engine, utts, fft_len=None, frames_per_run=None):
+    def __init__(self, engine, utts, fft_len=None, frames_per_run=None, n_slots=None):
+        # n_slots: overrides the engine's slot count (small tests)
         self.engine = engine
+        self.deal = "count"   # how the frames were dealt to the slots: "cost" (_deal_by_cost) or "count"
         if not utts:   # an empty batch: nothing to plan, run() returns empty tensors
             self.analysis = self.synthesis = None
             self.fft_len = fft_len or 4096
             self.total_frames = self.total_out = 0
             self.out_off_host = np.zeros(1, dtype=np.int64)
             return
-        self.analysis = LosslessAnalysisPlan(engine, utts, fft_len=fft_len)
+        self.analysis = LosslessAnalysisPlan(engine, utts, fft_len=fft_len, keep_frame_tabs=True)
         self.fft_len = self.analysis.fft_len
+        by_cost = (os.environ.get("MAGPHASE_RT_DEAL", "cost") != "count" and not frames_per_run
+                   and not os.environ.get("MAGPHASE_OLA_FRAMES_PER_RUN"))
         self.synthesis = LosslessSynthesisPlan(engine, self.analysis.v_f0, self.analysis.fs, self.fft_len,
-                                               frames_per_run=frames_per_run, comp_slots="roundtrip")
+                                               frames_per_run=frames_per_run, comp_slots="roundtrip", n_slots=n_slots,
+                                               gcuts=self._deal_by_cost if by_cost else None)
         if self.synthesis.total_frames != self.analysis.total_frames:
             raise ValueError("round trip: the synthesis plan must cover exactly the analysed frames")
         self.total_frames = self.analysis.total_frames
         self.total_out = self.synthesis.total_out
         self.out_off_host = self.synthesis.out_off_host
+
+    def _deal_by_cost(self, n_slots, total_frames):
+        """The cuts that deal the batch's frames to k_roundtrip_pair's slots by what they cost there, not by their number:
+        a frame's cost grows with its length (the register rows its gather visits, a second sample tile beyond 1024
+        samples), and a batch's long frames sit together in its low-pitched utterances -- shares of equal COUNT leave the
+        slots that got those frames working while the others' compute units idle at the end of the launch.  Terms per frame
+        from the analysis plan's left / right tables (mpx_roundtrip_frame_terms), coefficients per slot from the library
+        (mpx_roundtrip_slot_costs: fitted per age class of the wave pair), min-max dealing (mpx_host_deal_cuts; the numpy
+        twins when the native planners are off).  None -- shares by count, as every other plan -- with fewer frames than
+        slots, or when neither form of the planner is to be had.  MAGPHASE_RT_DEAL=count (read at plan build) switches
+        the dealing off: the A/B switch."""
+        tabs = getattr(self.analysis, "_host_tabs", None)
+        if tabs is None or total_frames < n_slots or int(np.size(tabs[1])) != total_frames:
+            return None
+        coef = np.zeros((n_slots, 3), dtype=np.int32)
+        _lib.check(self.engine.lib.mpx_roundtrip_slot_costs(coef.ctypes.data, int(n_slots)), "mpx_roundtrip_slot_costs")
+        if os.environ.get("MAGPHASE_RT_COSTS"):   # experiment: "a0,b0,c0,a1,b1,c1,a2,b2,c2" by age rank of the pair
+            k9 = np.asarray([int(x) for x in os.environ["MAGPHASE_RT_COSTS"].split(",")], dtype=np.int32).reshape(3, 3)
+            coef = np.ascontiguousarray(k9[((np.arange(n_slots) % 6) * 2) // 4])
+        try:
+            terms = hostplan.roundtrip_frame_terms(tabs[1], tabs[2], self.fft_len)
+            cuts, _t = hostplan.deal_cuts(terms, coef)
+        except hostplan.PlanFallback:
+            try:
+                terms = hm.roundtrip_frame_terms(tabs[1], tabs[2], self.fft_len)
+                cuts, _t = hm.deal_cuts(terms, coef)
+            except ValueError:   # the numpy twin refuses its input: the shares by count are always there
+                return None
+        self.deal = "cost"
+        return cuts
 
     def run(self, feats=None, strips=None, out=None):
         e, a, s = self.engine, self.analysis, self.synthesis
