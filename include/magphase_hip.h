@@ -332,6 +332,24 @@ int mpx_roundtrip_lossless_ola(void* stream, int fft_len, const void* tables, co
                                const mpx_ola_run* runs, int32_t n_runs, const int32_t* slot_off, const int32_t* slot_runs,
                                int32_t n_slots, const int32_t* pm_rel, float* out_mag, float* out_real, float* out_imag,
                                float* strips, float* pcm_out, int64_t ld);
+/*
+ * The same launch with flags.  The frame that is rebuilt is the windowed frame that was analysed, so at fft_len 4096 a
+ * frame with frame_left <= 512 and frame_right <= 511 (support class 4 of mpx_roundtrip_support_classes; every other frame
+ * and every other fft_len: the full class fft_len / 256) is zero outside 8 of its 32 register rows of 128 samples, and by
+ * default the kernel neither transforms nor overlap-adds the other rows: the feature rows are unchanged, the waveform
+ * loses the float32 rounding residue the full transform adds outside the frame.  MPX_RT_FULL_SUPPORT: every frame takes
+ * the full class.  mpx_roundtrip_lossless_ola is this call with flags 0.  mpx_roundtrip_support_classes: the class of each
+ * frame from its host tables (host function: no stream, no device); class_host: int32 [n_frames].
+ */
+#define MPX_RT_FULL_SUPPORT 1u
+int mpx_roundtrip_lossless_ola_flags(void* stream, int fft_len, const void* tables, const float* sig,
+                                     const int64_t* frame_pos, const int32_t* frame_left, const int32_t* frame_right,
+                                     int64_t n_frames, const mpx_ola_run* runs, int32_t n_runs, const int32_t* slot_off,
+                                     const int32_t* slot_runs, int32_t n_slots, const int32_t* pm_rel, float* out_mag,
+                                     float* out_real, float* out_imag, float* strips, float* pcm_out, int64_t ld,
+                                     uint32_t flags);
+int mpx_roundtrip_support_classes(int fft_len, const int32_t* frame_left, const int32_t* frame_right, int64_t n_frames,
+                                  int32_t* class_host);
 
 /*
  * One iteration of the pitch-synchronous Griffin-Lim algorithm (magphase.py:3320-3372, the loop body after the first

@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmagphase_hip.so")
 
 vp, i32, i64, sz, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_double   # (C int is i32)
+u32 = ctypes.c_uint32
 
 # every symbol include/magphase_hip.h declares: name -> (restype, argtypes), in the header's order
 # (tests/test_cabi_symbols.py checks the header against this table and that the .so exports them all)
@@ -48,6 +49,8 @@ PROTOTYPES = {
                                              vp, i64]),
     "mpx_ola_fixup": (i32, [vp, i32, vp, i32, vp, vp]),
     "mpx_roundtrip_lossless_ola": (i32, [vp, i32] + [vp] * 5 + [i64, vp, i32, vp, vp, i32] + [vp] * 6 + [i64]),
+    "mpx_roundtrip_lossless_ola_flags": (i32, [vp, i32] + [vp] * 5 + [i64, vp, i32, vp, vp, i32] + [vp] * 6 + [i64, u32]),
+    "mpx_roundtrip_support_classes": (i32, [i32, vp, vp, i64, vp]),
     "mpx_roundtrip_slot_weights": (i32, [vp, i32]),
     "mpx_roundtrip_frame_terms": (i32, [i32, vp, vp, i64, vp]),
     "mpx_roundtrip_slot_costs": (i32, [vp, i32]),

@@ -120,15 +120,102 @@ __device__ __forceinline__ int warp_swz(int r15) {
 // ---------------------------------------------------------------------------------------------
 // noise frame -> half spectrum in registers
 // ---------------------------------------------------------------------------------------------
+// noise_fft's zero fill, window and gather (the loop in its body, which see) for the rows of support class W alone (P/2:
+// all rows); the registers of the other rows are not touched.  A copy of that loop and not its replacement: called from
+// there, the same statements come out of the compiler as other (equivalent) code in every kernel that transforms a frame.
+template <int P, bool PRESTAGED, bool COMPACT, int W>
+__device__ __forceinline__ void noise_window_gather(const FrameGeom& g, int wtype, float* xbuf, unsigned xbuf_byte, int lane,
+                                                    float (&re)[P], float (&im)[P]) {
+    constexpr int M = 64 * P, N = 2 * M, kTile = noise_tile_len(P, COMPACT);
+    MPX_MARK("zero_init");
+#pragma unroll
+    for (int j = 0; j < P; ++j)
+        if (j < W || j >= P - W) re[(COMPACT && MPX_COMP_DIT) ? brev(j, ilog2(P)) : j] = im[(COMPACT && MPX_COMP_DIT) ? brev(j, ilog2(P)) : j] = 0.0f;
+    const int ntiles = MPX_NOISE_TILES(g.len, kTile);   // (mpx_common.hpp: the planner's cost terms count the same tiles and rows)
+    for (int t = 0; t < ntiles; ++t) {
+        MPX_MARK("window");
+        const int tile0 = t * kTile;
+        if (!PRESTAGED || t > 0) {
+            stage_samples_async(g, tile0, kTile, xbuf_byte, lane);
+            staged_wait<0>();
+        }
+        const int hi = min(g.len, tile0 + kTile);
+        // the window type is per frame (wave-uniform): one loop per type, not a select per sample
+        if (wtype == 0) {
+            for (int k = tile0 + lane; k < hi; k += 64)
+                xbuf[k - tile0] *= half_window(k, g.L, g.LR, g.kadd, g.invL, g.invR, 0);
+        } else {
+            for (int k = tile0 + lane; k < hi; k += 64)
+                xbuf[k - tile0] *= half_window(k, g.L, g.LR, g.kadd, g.invL, g.invR, 1);
+        }
+        wave_sync();
+        MPX_MARK("gather");
+        // (the gather of noise_fft, rows of the class only)
+        {
+            int n_lo = g.len - g.rot, n_hi = N - g.rot;
+            asm volatile("" : "+s"(n_lo), "+s"(n_hi));   // evaluated here, per tile: not hoisted as 32 lane masks
+            const unsigned span = (unsigned)(hi - tile0);
+            const unsigned b0 = (unsigned)(2 * lane + g.rot) - (unsigned)tile0;
+#pragma unroll
+            for (int j = 0; j < P; ++j) {
+                constexpr int LBJ = ilog2(P);
+                const int m0 = 128 * j;
+                if ((j < W || j >= P - W) && MPX_NOISE_ROW_ACTIVE(m0, n_lo, n_hi)) {
+                    const int rj = (COMPACT && MPX_COMP_DIT) ? brev(j, LBJ) : j;   // the DIT form wants register brev(j) <- z[l + 64 j]
+                    // sample index relative to the tile, modulo N (tile0 is a multiple of the tile length, which divides N)
+                    const unsigned d0 = (b0 + (unsigned)m0) & (unsigned)(N - 1), d1 = (d0 + 1u) & (unsigned)(N - 1);
+                    const float v0 = xbuf[min(d0, (unsigned)(kTile - 1))], v1 = xbuf[min(d1, (unsigned)(kTile - 1))];
+                    re[rj] = (d0 < span) ? v0 : re[rj];
+                    im[rj] = (d1 < span) ? v1 : im[rj];
+                }
+            }
+        }
+        wave_sync();
+    }
+}
+
 // Windowed noise frame (magphase.py:886-897: windowing() with per-frame window list, epoch moved to index 0 by
 // frm_list_to_matrix + fftshift) -> N-point real FFT -> Ns[k] for the bins kappa(lane) + 64 j, j = 0..P-1
 // (natural j), plus the Nyquist bin (real) on the lane with kappa == 0.  Synchronous staging (no prefetch).
 // COMPACT (P == 32): half-height exchange buffer (tiles of 32 P samples) and half twiddle table (wave_fft_front_compact;
 // (lc, ls) = W_128^lane) -- k_synth_comp_pair at 12 waves per CU.
-template <int P, bool PRESTAGED = false, bool COMPACT = false>   // PRESTAGED: the caller already copied tile 0 into xbuf and waited for it
+// NW > 0 (compact DIF form only): where `narrow` (wave-uniform) holds, the frame is of support class NW
+// (frame_support_class, mpx_common.hpp; the caller's promise) -- only the rows j < NW and j >= P - NW are gathered, the
+// others are constants 0, and the stages of the first in-register pass that meet those zeros are pruned for them.  Two
+// straight-line instances of the gather with those stages, one wave-uniform branch around them; everything else is shared.
+template <int P, bool PRESTAGED = false, bool COMPACT = false, int NW = 0>   // PRESTAGED: the caller already copied tile 0 into xbuf and waited for it
 __device__ __forceinline__ void noise_fft(const FrameGeom& g, int wtype, const float* tw, float* xbuf,
                                           unsigned xbuf_byte, int lane, float (&re)[P], float (&im)[P], float lc = 1.0f,
-                                          float ls = 0.0f) {
+                                          float ls = 0.0f, bool narrow = false) {
+    static_assert(NW == 0 || (COMPACT && !MPX_COMP_DIT), "support classes: the compact DIF form only");
+    if constexpr (NW > 0) {
+        // one wave-uniform choice per frame between two straight-line instances of the gather and of the stages of the
+        // first in-register pass that meet the class's zeros (stride > S0); the rows outside the class are never written
+        // before the pruned stages define them
+        constexpr unsigned kZin = support_zero_rows<P>(NW);
+        constexpr int S0 = zin_clear_stride<P>(kZin);
+        static_assert(S0 >= 1 && S0 < P / 2, "a class prunes some, not all, stages of the first pass");
+        if (narrow) {
+            noise_window_gather<P, PRESTAGED, COMPACT, NW>(g, wtype, xbuf, xbuf_byte, lane, re, im);
+            mpx_pin_live<~kZin>(re), mpx_pin_live<~kZin>(im);
+            MPX_MARK("fft_forward");
+            fft_inreg_pruned_stage<P, -1, P / 2, kZin, kAllRegs, 2 * S0>(re, im);
+            MPX_ARM_END_CLASS();
+        } else {
+            noise_window_gather<P, PRESTAGED, COMPACT, P / 2>(g, wtype, xbuf, xbuf_byte, lane, re, im);
+            mpx_pin(re), mpx_pin(im);
+            MPX_MARK("fft_forward");
+            fft_inreg_stages<P, -1, P / 2, 2 * S0>(re, im);
+            MPX_ARM_END_FULL();
+        }
+        const float4 pk = tw_half_pad<P>(tw, lane);
+        fft_inreg_stages<P, -1, S0>(re, im);
+        wave_fft_front_compact_rest<P, -1>(re, im, tw, xbuf, lane, pk.z, pk.w);
+        fft_inreg<P, -1>(re, im);
+        (void)lc;
+        (void)ls;
+        return;
+    }
     constexpr int M = 64 * P, N = 2 * M, kTile = noise_tile_len(P, COMPACT);
     MPX_MARK("zero_init");
 #pragma unroll
@@ -201,15 +288,15 @@ __device__ __forceinline__ void noise_fft(const FrameGeom& g, int wtype, const f
 // (X[k] = E + T, X[M-k] = conj(E - T)): P lane exchanges and P/2 split evaluations per lane instead of 2P and P of the
 // per-bin form.  The kappa == 0 lane's q == 0 pair is (DC, Nyquist); bin M/2 is its own mirror and comes out separately
 // (nh_*, meaningful on the kappa == 0 lane).
-template <int P, bool PRESTAGED = false, bool COMPACT = false>
+template <int P, bool PRESTAGED = false, bool COMPACT = false, int NW = 0>   // NW, narrow: support class, see noise_fft
 __device__ __forceinline__ void noise_spectrum_paired(const FrameGeom& g, int wtype, const float* tw, float* xbuf,
                                                       unsigned xbuf_byte, int lane, float wl_c, float wl_s,
                                                       float (&no_r)[P / 2], float (&no_i)[P / 2], float (&nm_r)[P / 2],
                                                       float (&nm_i)[P / 2], float& nh_r, float& nh_i, float lc = 1.0f,
-                                                      float ls = 0.0f) {
+                                                      float ls = 0.0f, bool narrow = false) {
     constexpr int LB = ilog2(P);
     float re[P], im[P];
-    noise_fft<P, PRESTAGED, COMPACT>(g, wtype, tw, xbuf, xbuf_byte, lane, re, im, lc, ls);
+    noise_fft<P, PRESTAGED, COMPACT, NW>(g, wtype, tw, xbuf, xbuf_byte, lane, re, im, lc, ls, narrow);
     mpx_pin(re), mpx_pin(im);
     MPX_MARK("split");
     if constexpr (COMPACT) {   // the split twiddle W_N^kappa from the table row's pad: not live across the transform
@@ -976,16 +1063,17 @@ __device__ __forceinline__ void pair_frame_lane(const PairWave& w, int& lane, fl
 }
 
 // Analysis of the staged frame g (Hann halves): X[k] of the own bins k = lane + 64 q (no_*) and of their mirrors M - k
-// (nm_*), bin M/2 on lane 0 (nh_*).
-template <int P>
+// (nm_*), bin M/2 on lane 0 (nh_*).  NW, narrow: the frame's support class (noise_fft).
+template <int P, int NW = 0>
 __device__ __forceinline__ void pair_analysis_spectrum(const PairWave& w, const FrameGeom& g, int lane, float wa_c,
                                                        float wa_s, float (&no_r)[P / 2], float (&no_i)[P / 2],
-                                                       float (&nm_r)[P / 2], float (&nm_i)[P / 2], float& nh_r, float& nh_i) {
+                                                       float (&nm_r)[P / 2], float (&nm_i)[P / 2], float& nh_r, float& nh_i,
+                                                       bool narrow = false) {
     constexpr bool kCompact = comp_compact<P>();
     MPX_MARK("frame_setup");
     staged_wait<0>();
-    noise_spectrum_paired<P, true, kCompact>(g, 0, w.tw, w.xbuf, w.xbuf_byte, lane, wa_c, wa_s, no_r, no_i, nm_r, nm_i, nh_r,
-                                             nh_i);
+    noise_spectrum_paired<P, true, kCompact, NW>(g, 0, w.tw, w.xbuf, w.xbuf_byte, lane, wa_c, wa_s, no_r, no_i, nm_r, nm_i,
+                                                 nh_r, nh_i, 1.0f, 0.0f, narrow);
     if (P != 32) {   // FFT output lanes hold bins kappa(lane) + 64 q; the rows and the merge want bins lane + 64 q
         const int src = kappa<P>(lane);
 #pragma unroll
@@ -1037,19 +1125,48 @@ __device__ __forceinline__ void pair_inverse_fft_back(float (&xr)[P], float (&xi
     if constexpr (comp_compact<P>() && MPX_COMP_DIT) wave_fft_dit_back<P, +1>(xr, xi);
     else fft_inreg<P, +1>(xr, xi);
 }
+// The registers of the inverse transform's output (DIF form: register i <-> row brev(i)) that hold the rows
+// P/2 - W <= q < P/2 + W of the fftshifted frame (ring_add_plane's ROT: frame row q = output row (q + P/2) mod P).
+template <int P>
+constexpr unsigned support_out_regs(int W) {
+    unsigned o = 0u;
+    for (int q = 0; q < P; ++q)
+        if (support_row_live(q, W, P)) o |= 1u << brev((q + P / 2) % P, ilog2(P));
+    return o;
+}
+// ... and the transform that forms only those where `narrow` (wave-uniform) holds (DIF form): the last stages, some of whose
+// outputs the overlap-add of a class-NW frame does not read, in two instances; the registers it skips keep stale values.
+template <int P, int NW>
+__device__ __forceinline__ void pair_inverse_fft_back_class(float (&xr)[P], float (&xi)[P], bool narrow) {
+    static_assert(!(comp_compact<P>() && MPX_COMP_DIT), "support classes: the DIF form only");
+    constexpr unsigned kOut = support_out_regs<P>(NW);
+    constexpr int S1 = out_prune_stride<P>(kOut);   // the stages of stride <= S1 have outputs nobody reads
+    static_assert(S1 >= 1 && S1 < P / 2, "a class prunes some, not all, stages of the last pass");
+    fft_inreg_stages<P, +1, P / 2, 2 * S1>(xr, xi);
+    if (narrow) {
+        fft_inreg_pruned_stage<P, +1, S1, 0u, kOut>(xr, xi);
+        MPX_ARM_END_CLASS();
+    } else {
+        fft_inreg_stages<P, +1, S1>(xr, xi);
+        MPX_ARM_END_FULL();
+    }
+}
 
 // The ordered section of frame cur.fi: waits for the frame's ticket, streams out of the pair's ring what no later frame
 // reaches, adds the frame (xr = samples 2n, xi = samples 2n + 1) at its strip position, and passes the ticket on; the
 // last frame of a run streams out the rest and leaves the ring cleared.  combine(old, value, n) / live(q) as ring_add;
 // ROT: the rows are taken half a transform apart (the fftshift, see ring_add_plane).
-template <int P, bool ROT, typename CFn, typename LFn>
+// NW > 0 (k_roundtrip_pair): where `narrow` (wave-uniform) holds, only the rows of support class NW are added -- a second
+// straight-line instance of the ring add whose row set is a compile-time constant; xr / xi then hold only those rows.
+template <int P, bool ROT, int NW = 0, typename CFn, typename LFn>
 __device__ __forceinline__ void pair_ordered_ola(const PairWave& w, const PairCursor& cur, float* smem,
                                                  const RunDesc* __restrict__ runs, const int* __restrict__ pm_rel,
                                                  float* __restrict__ strips, float* __restrict__ pcm, float (&xr)[P],
-                                                 float (&xi)[P], int lane, CFn combine, LFn live) {
+                                                 float (&xi)[P], int lane, CFn combine, LFn live, bool narrow = false) {
     constexpr int R = ring_len<P>();
     constexpr bool kDit = comp_compact<P>() && MPX_COMP_DIT;
-    mpx_pin(xr), mpx_pin(xi);
+    static_assert(NW == 0 || (ROT && !kDit && (kCompPairWaves > 8)), "class row sets: the rotated DIF form only");
+    if constexpr (NW == 0) mpx_pin(xr), mpx_pin(xi);
     MPX_MARK("ticket");
     const int fi = cur.fi;
     int* const turn = w.turn;
@@ -1071,8 +1188,24 @@ __device__ __forceinline__ void pair_ordered_ola(const PairWave& w, const PairCu
     if constexpr (kCompPairWaves > 8 || ROT) {   // 16 ring values in registers at a time (<= 168 VGPRs)
         constexpr int CH = (P < MPX_COMP_CH) ? P : MPX_COMP_CH;
         const RingAddr ra = ring_addr<P>(w.ring_byte, x, lane);
-        ring_add_plane<P, 0, CH, kDit, ROT>(smem, ra, xr, lane, combine, live);
-        ring_add_plane<P, 1, CH, kDit, ROT>(smem, ra, xi, lane, combine, live);
+        if constexpr (NW > 0) {
+            if (narrow) {
+                constexpr unsigned kOut = support_out_regs<P>(NW);
+                mpx_pin_live<kOut>(xr), mpx_pin_live<kOut>(xi);
+                auto live_nw = [](int q) { return support_row_live(q, NW, P); };
+                ring_add_plane<P, 0, CH, kDit, ROT>(smem, ra, xr, lane, combine, live_nw);
+                ring_add_plane<P, 1, CH, kDit, ROT>(smem, ra, xi, lane, combine, live_nw);
+                MPX_ARM_END_CLASS();
+            } else {
+                mpx_pin(xr), mpx_pin(xi);
+                ring_add_plane<P, 0, CH, kDit, ROT>(smem, ra, xr, lane, combine, live);
+                ring_add_plane<P, 1, CH, kDit, ROT>(smem, ra, xi, lane, combine, live);
+                MPX_ARM_END_FULL();
+            }
+        } else {
+            ring_add_plane<P, 0, CH, kDit, ROT>(smem, ra, xr, lane, combine, live);
+            ring_add_plane<P, 1, CH, kDit, ROT>(smem, ra, xi, lane, combine, live);
+        }
     } else {
         ring_add<P>(smem, w.ring_byte, x, xr, xi, lane, combine, live);
     }
@@ -1513,7 +1646,14 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_synth_comp_pair(const f
 __device__ unsigned long long g_rt_endprobe[4 * 8192];   // per wave: start, end (100 MHz clock), frames, shader cycles
 #endif
 
-template <int P>
+// CLS: frames of a narrow support class (frame_support_class, mpx_common.hpp: the windowed frame is zero outside a few
+// register rows, and so is the frame rebuilt from it) take instances of the gather, the first forward pass, the last
+// inverse pass and the ring add whose row sets are compile-time constants -- one wave-uniform decision per frame, taken
+// from the frame's own (L, R).  false: every frame takes the full class (MAGPHASE_RT_SUPPORT=full; every N but 4096).
+#ifndef MPX_RT_FORCE_NARROW
+#define MPX_RT_FORCE_NARROW 0   // 1 (timing experiments only, wrong results): every frame is treated as the narrow class
+#endif
+template <int P, bool CLS = false>
 __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const float* __restrict__ sig,
                                                                        const long long* __restrict__ fpos,
                                                                        const int* __restrict__ fleft,
@@ -1527,6 +1667,8 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
                                                                        float* __restrict__ oimag, float* __restrict__ strips,
                                                                        float* __restrict__ pcm, long long ld) {
     constexpr int M = 64 * P, N = 2 * M, HP = P / 2;
+    constexpr bool kCls = CLS && P == 32 && comp_compact<P>() && !MPX_COMP_DIT;   // the forms that have pruned passes
+    constexpr int NW = kCls ? kSupportNarrow : 0;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     PairWave w;
     if (!pair_wave_setup<P>(w, smem, tw_g, runs, slot_off, slot_runs, nslots)) return;
@@ -1547,11 +1689,14 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
         PairCursor nxt = cur;
         pair_cursor_advance(nxt, w.wi_end, w.half, runs, slot_runs);
         const int fi = cur.fi;
+        // the staged frame's support class (g is this frame's until the next one is staged below)
+        bool narrow = false;
+        if constexpr (kCls) narrow = MPX_RT_FORCE_NARROW || (frame_support_class(g.L, g.LR - g.L, N) == NW);
 
         float xr[P], xi[P];
         {
             float no_r[HP], no_i[HP], nm_r[HP], nm_i[HP], nh_r, nh_i;
-            pair_analysis_spectrum<P>(w, g, lane, wa_c, wa_s, no_r, no_i, nm_r, nm_i, nh_r, nh_i);
+            pair_analysis_spectrum<P, NW>(w, g, lane, wa_c, wa_s, no_r, no_i, nm_r, nm_i, nh_r, nh_i, narrow);
             // ---- per bin pair q: lossless features (magphase.py:466-474; as k_analysis: X == 0 -> all three 0), their
             // stores, and the pair's step of the Hermitian merge -- feat_merge_paired's arithmetic on the values just
             // stored (X = mag (R + jI) / |R + jI|, magphase.py:1761-1766), pair by pair so that a pair's four inputs die
@@ -1634,12 +1779,13 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
             g = frame_geom(sig, fpos[nxt.fi], fleft[nxt.fi], fright[nxt.fi], N);
             pair_stage_next<P>(w, g, lane);
         }
-        pair_inverse_fft_back<P>(xr, xi);
+        if constexpr (kCls) pair_inverse_fft_back_class<P, NW>(xr, xi, narrow);
+        else pair_inverse_fft_back<P>(xr, xi);
         constexpr float kScale = 0.5f / (float)M;   // the inverse transform's scale, on the overlap-add's multiply-add
         auto plain_add = [](float o, float v, int) { return fmaf(v, kScale, o); };
         auto all_rows = [](int) { return true; };
         // ROT: rows taken half a transform apart, the fftshift
-        pair_ordered_ola<P, true>(w, cur, smem, runs, pm_rel, strips, pcm, xr, xi, lane, plain_add, all_rows);
+        pair_ordered_ola<P, true, NW>(w, cur, smem, runs, pm_rel, strips, pcm, xr, xi, lane, plain_add, all_rows, narrow);
         cur = nxt;
 #ifdef MPX_PROBE_ENDTIME
         ++probe_frames;
@@ -2719,11 +2865,32 @@ int mpx_probe_rt_endtimes(unsigned long long* host, int n_words) {   // probe bu
 }
 #endif
 
+int mpx_roundtrip_support_classes(int fft_len, const int32_t* frame_left, const int32_t* frame_right, int64_t n_frames,
+                                  int32_t* class_host) {
+    if (!p_of(fft_len)) return fail(MPX_ERR_ARG, "mpx_roundtrip_support_classes: fft_len must be 1024, 2048 or 4096%s");
+    if (n_frames < 0 || (n_frames > 0 && (!frame_left || !frame_right || !class_host)))
+        return fail(MPX_ERR_ARG, "mpx_roundtrip_support_classes: bad arguments%s");
+    for (int64_t f = 0; f < n_frames; ++f) class_host[f] = frame_support_class(frame_left[f], frame_right[f], fft_len);
+    return MPX_OK;
+}
+
 int mpx_roundtrip_lossless_ola(void* stream, int fft_len, const void* tables, const float* sig, const int64_t* frame_pos,
                                const int32_t* frame_left, const int32_t* frame_right, int64_t n_frames,
                                const mpx_ola_run* runs, int32_t n_runs, const int32_t* slot_off, const int32_t* slot_runs,
                                int32_t n_slots, const int32_t* pm_rel, float* out_mag, float* out_real, float* out_imag,
                                float* strips, float* pcm_out, int64_t ld) {
+    return mpx_roundtrip_lossless_ola_flags(stream, fft_len, tables, sig, frame_pos, frame_left, frame_right, n_frames, runs,
+                                            n_runs, slot_off, slot_runs, n_slots, pm_rel, out_mag, out_real, out_imag, strips,
+                                            pcm_out, ld, 0u);
+}
+
+int mpx_roundtrip_lossless_ola_flags(void* stream, int fft_len, const void* tables, const float* sig,
+                                     const int64_t* frame_pos, const int32_t* frame_left, const int32_t* frame_right,
+                                     int64_t n_frames, const mpx_ola_run* runs, int32_t n_runs, const int32_t* slot_off,
+                                     const int32_t* slot_runs, int32_t n_slots, const int32_t* pm_rel, float* out_mag,
+                                     float* out_real, float* out_imag, float* strips, float* pcm_out, int64_t ld,
+                                     uint32_t flags) {
+    if (flags & ~(uint32_t)MPX_RT_FULL_SUPPORT) return fail(MPX_ERR_ARG, "mpx_roundtrip_lossless_ola: unknown flag%s");
     const int P = p_of(fft_len);
     if (!P) return fail(MPX_ERR_ARG, "mpx_roundtrip_lossless_ola: fft_len must be 1024, 2048 or 4096%s");
     if (n_frames < 0 || n_runs < 0 || n_slots < 0) return fail(MPX_ERR_ARG, "mpx_roundtrip_lossless_ola: negative count%s");
@@ -2734,17 +2901,20 @@ int mpx_roundtrip_lossless_ola(void* stream, int fft_len, const void* tables, co
         return fail(MPX_ERR_ARG, "mpx_roundtrip_lossless_ola: null pointer%s");
     hipStream_t s = (hipStream_t)stream;
     const dim3 pgrid((n_slots + kCompPairs - 1) / kCompPairs), pblock(kCompPairWaves * 64);
-#define MPX_LAUNCH_RT(PP)                                                                                              \
+#define MPX_LAUNCH_RT(PP, CLS)                                                                                         \
     do {                                                                                                             \
-        if (int rc = set_lds(k_roundtrip_pair<PP>, lds_bytes_comp_pair<PP>())) return rc;            \
-        hipLaunchKernelGGL(k_roundtrip_pair<PP>, pgrid, pblock, lds_bytes_comp_pair<PP>(), s, sig,   \
+        auto KK = k_roundtrip_pair<PP, CLS>;                                                                         \
+        if (int rc = set_lds(KK, lds_bytes_comp_pair<PP>())) return rc;                                              \
+        hipLaunchKernelGGL(KK, pgrid, pblock, lds_bytes_comp_pair<PP>(), s, sig,                                     \
                            (const long long*)frame_pos, frame_left, frame_right, (const RunDesc*)runs, slot_off,     \
                            slot_runs, (int)n_slots, pm_rel, (const float*)tables, out_mag, out_real, out_imag, strips, \
                            pcm_out, (long long)ld);                                                                  \
     } while (0)
-    if (P == 32) MPX_LAUNCH_RT(32);
-    else if (P == 16) MPX_LAUNCH_RT(16);
-    else MPX_LAUNCH_RT(8);
+    // support classes (k_roundtrip_pair's CLS): only N = 4096 has a narrow class
+    if (P == 32 && !(flags & MPX_RT_FULL_SUPPORT)) MPX_LAUNCH_RT(32, true);
+    else if (P == 32) MPX_LAUNCH_RT(32, false);
+    else if (P == 16) MPX_LAUNCH_RT(16, false);
+    else MPX_LAUNCH_RT(8, false);
 #undef MPX_LAUNCH_RT
     MPX_HIP_CHECK(hipGetLastError());
     return MPX_OK;

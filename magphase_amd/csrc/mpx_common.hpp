@@ -64,6 +64,17 @@ __device__ __forceinline__ int rfl(int v) { return __builtin_amdgcn_readfirstlan
 #endif
 // ... and, in those builds, the values that cross a phase boundary pinned at it (an empty asm that "uses and defines" them):
 // the arithmetic of the phase before cannot sink below the marker, that of the phase after cannot rise above it.
+// ... only the registers of the set LIVE (bit i <=> a[i]): the others stay dead for the compiler
+template <unsigned LIVE, int K>
+__device__ __forceinline__ void mpx_pin_live(float (&a)[K]) {
+#ifdef MPX_PHASE_MARKS
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+        if ((LIVE >> i) & 1u) asm volatile("" : "+v"(a[i]));
+#else
+    (void)a;
+#endif
+}
 template <int K>
 __device__ __forceinline__ void mpx_pin(float (&a)[K]) {
 #ifdef MPX_PHASE_MARKS
@@ -158,6 +169,36 @@ __host__ __device__ inline void frame_cost_terms(int L, int R, int N, int P, boo
     terms[1] = rows * ntiles;
     terms[2] = ntiles - 1;
 }
+
+// Support class of a frame in the round-trip kernel (k_roundtrip_pair), which rebuilds the windowed frame it has just
+// analysed: class W says that the frame's samples lie in the register rows j < W or j >= P - W of the rotated analysis
+// input (noise_fft's gather: row j <-> n in [128 j, 128 j + 127] of y[n] = x[(n + rot) mod N]) and in the rows
+// P/2 - W <= q < P/2 + W of the rebuilt, fftshifted frame (ring_add_plane: row q <-> samples [128 q, 128 q + 127]).
+// With rot = L and len = L + R + 1 < N the right half (epoch included) is n in [0, R] and the left half n in [N - L, N - 1];
+// the fftshift moves them to [N/2, N/2 + R] and [N/2 - L, N/2 - 1].  Both layouts therefore ask the same of a class:
+// R <= 128 W - 1 and L <= 128 W (L == 0, kadd: the frame then has no left half at all).  Frames truncated at N (Q19), L >= N
+// (no rotation) and everything else take the full class W = P/2.  Classes: 4 and full; only N = 4096 has the narrow one.
+constexpr int kSupportNarrow = 4;
+__host__ __device__ inline int frame_support_class(int L, int R, int N) {
+    const int P = N / 128;
+    if (P == 32 && L >= 0 && R >= 0 && L <= 128 * kSupportNarrow && R <= 128 * kSupportNarrow - 1) return kSupportNarrow;
+    return P / 2;
+}
+// The two arms of a wave-uniform choice between a class instance and the full one end in these (distinct, empty) asm
+// statements: without them the compiler merges the arms' common tails, the register index of the merged code becomes a
+// run-time value, and the register array it indexes moves to scratch memory.
+#define MPX_ARM_END_CLASS() asm volatile("; end of the class arm")
+#define MPX_ARM_END_FULL() asm volatile("; end of the full arm")
+// the register rows of class W as bit sets: rows of the rotated analysis input that are NOT in the class (known zero) ...
+template <int P>
+__host__ __device__ constexpr unsigned support_zero_rows(int W) {
+    unsigned z = 0u;
+    for (int j = 0; j < P; ++j)
+        if (!(j < W || j >= P - W)) z |= 1u << j;
+    return z;
+}
+// ... and whether row q of the rebuilt frame is in it
+__host__ __device__ constexpr bool support_row_live(int q, int W, int P) { return q >= P / 2 - W && q < P / 2 + W; }
 
 __device__ __forceinline__ FrameGeom frame_geom(const float* __restrict__ sig, long long pos, int L, int R, int N) {
     FrameGeom g;

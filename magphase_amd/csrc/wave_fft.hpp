@@ -128,6 +128,120 @@ __device__ __forceinline__ void fft_inreg(float (&re)[P], float (&im)[P]) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Pruned forms of fft_inreg for a transform whose input is known to be zero in some registers (ZIN: bit i set <=> register
+// i holds an exact 0 on entry) or of whose output only some registers are read (OUT: bit i set <=> register i is read).
+// Both sets are template constants: every stage is straight-line code with its butterflies chosen at compile time.
+// Only the first stages of a transform can meet known zeros and only the last ones can skip outputs, so a caller that
+// chooses between a pruned and the full form at run time branches around those stages alone (fft_inreg_stages for the
+// others): zin_clear_stride / out_prune_stride say which.
+//   ZIN: a butterfly whose b is zero leaves a in place and forms a w; one whose a is zero copies b and forms (-b) w; one
+//        with both zero is skipped.  Each returns what the full butterfly returns for a zero operand (up to the sign of a
+//        zero: a + 0 turns -0 into +0, the copy keeps it), so the results compare equal to fft_inreg's.  (-b is formed in
+//        a register of its own, behind a compiler barrier: seen as a negation, the compiler folds it into the twiddle
+//        product and fuses the OTHER product of a w into the multiply-add -- a different rounding than the full form's.)
+//   OUT: an output that nothing downstream reads is not formed; its register keeps a stale value.
+// ---------------------------------------------------------------------------------------------
+// ZIN after stage s (stride s) given the set before it
+template <int P>
+__host__ __device__ constexpr unsigned dif_zero_after(int s, unsigned z) {
+    unsigned o = 0u;
+    for (int g = 0; g < P; g += 2 * s)
+        for (int k = 0; k < s; ++k) {
+            const int i0 = g + k, i1 = g + k + s;
+            if (((z >> i0) & 1u) && ((z >> i1) & 1u)) o |= (1u << i0) | (1u << i1);
+        }
+    return o;
+}
+// registers read after stage s (by the stages of stride < s, or as output) given the set OUT read after the last stage
+template <int P>
+__host__ __device__ constexpr unsigned dif_need_after(int s, unsigned out) {
+    unsigned need = out;
+    for (int t = 1; t < s; t <<= 1) {
+        unsigned n2 = 0u;
+        for (int g = 0; g < P; g += 2 * t)
+            for (int k = 0; k < t; ++k) {
+                const int i0 = g + k, i1 = g + k + t;
+                if (((need >> i0) | (need >> i1)) & 1u) n2 |= (1u << i0) | (1u << i1);
+            }
+        need = n2;
+    }
+    return need;
+}
+constexpr unsigned kAllRegs = ~0u;
+// the stride of the first stage that meets no known zero (P/2 when ZIN is empty; 0: every stage meets one)
+template <int P>
+__host__ __device__ constexpr int zin_clear_stride(unsigned z) {
+    int s = P / 2;
+    while (s >= 1 && (z & (P >= 32 ? ~0u : ((1u << (P & 31)) - 1u))) != 0u) {
+        z = dif_zero_after<P>(s, z);
+        s >>= 1;
+    }
+    return s;
+}
+// the stride of the first stage some of whose outputs are not read (0: every stage's outputs are all read)
+template <int P>
+__host__ __device__ constexpr int out_prune_stride(unsigned out) {
+    int s = 0;
+    for (int t = 1; t <= P / 2; t <<= 1)
+        if ((dif_need_after<P>(t, out) & (P >= 32 ? ~0u : ((1u << (P & 31)) - 1u))) != (P >= 32 ? ~0u : ((1u << (P & 31)) - 1u))) s = t;
+    return s;
+}
+
+// the stages of stride S .. S_LAST
+template <int P, int SIGN, int S, unsigned ZIN, unsigned OUT, int S_LAST = 1>
+__device__ __forceinline__ void fft_inreg_pruned_stage(float (&re)[P], float (&im)[P]) {
+    constexpr unsigned NEED = dif_need_after<P>(S, OUT);
+#pragma unroll
+    for (int g = 0; g < P; g += 2 * S) {
+#pragma unroll
+        for (int k = 0; k < S; ++k) {
+            const int i0 = g + k, i1 = g + k + S;
+            const int t = k * (16 / S);  // twiddle W_{2S}^k = W_32^t, t in [0,16)
+            const bool za = (ZIN >> i0) & 1u, zb = (ZIN >> i1) & 1u;
+            const bool n0 = (NEED >> i0) & 1u, n1 = (NEED >> i1) & 1u;
+            if ((za && zb) || (!n0 && !n1)) continue;
+            float tr, ti;
+            if (zb) {            // b == 0: a stays, a w
+                tr = re[i0];
+                ti = im[i0];
+            } else if (za) {     // a == 0: b, (-b) w
+                tr = -re[i1];
+                ti = -im[i1];
+                asm volatile("" : "+v"(tr), "+v"(ti));
+                re[i0] = re[i1];
+                im[i0] = im[i1];
+            } else {
+                const float ar = re[i0], ai = im[i0], br = re[i1], bi = im[i1];
+                tr = ar - br;
+                ti = ai - bi;
+                if (n0) {
+                    re[i0] = ar + br;
+                    im[i0] = ai + bi;
+                }
+            }
+            if (!n1) continue;
+            if (t == 0) {
+                re[i1] = tr;
+                im[i1] = ti;
+            } else if (t == 8) {  // W = SIGN * i
+                re[i1] = (SIGN < 0) ? ti : -ti;
+                im[i1] = (SIGN < 0) ? -tr : tr;
+            } else {
+                const float c = c32(t), sn = (SIGN < 0) ? -s32(t) : s32(t);
+                re[i1] = tr * c - ti * sn;
+                im[i1] = tr * sn + ti * c;
+            }
+        }
+    }
+    if constexpr (S > S_LAST) fft_inreg_pruned_stage<P, SIGN, S / 2, dif_zero_after<P>(S, ZIN), OUT, S_LAST>(re, im);
+}
+// the stages of fft_inreg with the strides S_HI .. S_LO (fft_inreg = all of them: P/2 .. 1)
+template <int P, int SIGN, int S_HI, int S_LO = 1>
+__device__ __forceinline__ void fft_inreg_stages(float (&re)[P], float (&im)[P]) {
+    fft_inreg_pruned_stage<P, SIGN, S_HI, 0u, kAllRegs, S_LO>(re, im);
+}
+
+// ---------------------------------------------------------------------------------------------
 // P-point radix-2 DIT FFT on statically indexed registers: input register r holds element brev(r), output register i
 // holds index i (natural).  Same transform as fft_inreg; the butterflies are out0 = a + w b, out1 = 2 a - out0 in fused
 // multiply-adds: 6 instructions for a general twiddle where the DIF form (sum, difference, complex multiply) takes 8 --
@@ -483,11 +597,21 @@ __device__ __forceinline__ void lds_transpose_half(float (&x)[P], float* xbuf, i
 
 // wave_fft_front with the half table (twh: tw_half_floats<P>() floats) and the half-height buffer (P/2 * kXStride floats).
 // (lc, ls) = (cos, sin)(2 pi lane / 128), the caller's per-lane constant.
+// (in two parts: a caller with a form of its own of the first in-register pass follows it with wave_fft_front_compact_rest)
+template <int P, int SIGN>
+__device__ __forceinline__ void wave_fft_front_compact_rest(float (&re)[P], float (&im)[P], const float* twh, float* xbuf,
+                                                            int lane, float lc, float ls);
 template <int P, int SIGN>
 __device__ __forceinline__ void wave_fft_front_compact(float (&re)[P], float (&im)[P], const float* twh, float* xbuf,
                                                        int lane, float lc, float ls) {
     static_assert(P == 32, "compact form: P == 32 only");
     fft_inreg<P, SIGN>(re, im);
+    wave_fft_front_compact_rest<P, SIGN>(re, im, twh, xbuf, lane, lc, ls);
+}
+template <int P, int SIGN>
+__device__ __forceinline__ void wave_fft_front_compact_rest(float (&re)[P], float (&im)[P], const float* twh, float* xbuf,
+                                                            int lane, float lc, float ls) {
+    static_assert(P == 32, "compact form: P == 32 only");
     const float4* trow = reinterpret_cast<const float4*>(twh + lane * tw_half_stride<P>());
 #pragma unroll
     for (int q = 0; q < P / 4; ++q) {

@@ -1476,15 +1476,16 @@ class Engine:
                     ranges, rowt, int(n_rows), out[0], out[1], out[2], self.feat_ld(first, first, first))
         return out
 
-    def roundtrip_lossless_ola(self, fft_len, plan_a, plan_s, feats, strips, pcm_out):
-        """Copy synthesis in one launch (mpx_roundtrip_lossless_ola): plan_a's frames are analysed, their feature rows
+    def roundtrip_lossless_ola(self, fft_len, plan_a, plan_s, feats, strips, pcm_out, full_support=False):
+        """Copy synthesis in one launch (mpx_roundtrip_lossless_ola_flags): plan_a's frames are analysed, their feature rows
         written to feats = (mag, real, imag) and overlap-added by plan_s' runs (a LosslessSynthesisPlan built for this
-        kernel's slots from plan_a's v_f0); ola_fixup(plan_s, strips, pcm_out) completes the run boundaries."""
+        kernel's slots from plan_a's v_f0); ola_fixup(plan_s, strips, pcm_out) completes the run boundaries.
+        full_support: every frame takes the full support class (MPX_RT_FULL_SUPPORT)."""
         mag, real, imag = feats
-        self.launch("mpx_roundtrip_lossless_ola", int(fft_len), self.tables(fft_len), plan_a.sig, plan_a.pos, plan_a.left,
+        self.launch("mpx_roundtrip_lossless_ola_flags", int(fft_len), self.tables(fft_len), plan_a.sig, plan_a.pos, plan_a.left,
                     plan_a.right, int(plan_a.total_frames), plan_s.runs, int(plan_s.n_runs), plan_s.slot_off,
                     plan_s.slot_runs, int(plan_s.n_slots), plan_s.pm_rel, mag, real, imag, strips, pcm_out,
-                    self.feat_ld(mag, real, imag))
+                    self.feat_ld(mag, real, imag), 1 if full_support else 0)
         return pcm_out
 
     def griffin_lim_ola(self, fft_len, plan, target, sig_in, sig_out, strips, phase_out=None):

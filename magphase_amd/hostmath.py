@@ -353,6 +353,18 @@ def roundtrip_frame_terms(left, right, fft_len):
     return np.stack([np.ones_like(ln), rows * ntiles, ntiles - 1], axis=1).astype(np.int32)
 
 
+def roundtrip_support_classes(left, right, fft_len):
+    """mpx_roundtrip_support_classes in numpy (csrc/mpx_common.hpp: frame_support_class): class W of a frame of
+    k_roundtrip_pair -- its samples lie in the register rows j < W or j >= P - W of the rotated analysis input and in the
+    rows P/2 - W <= q < P/2 + W of the rebuilt frame.  4 where N = 4096, 0 <= L <= 512 and 0 <= R <= 511; otherwise the
+    full class P / 2 = N / 256.  int32 [n_frames]."""
+    N = int(fft_len)
+    P = N // 128
+    L, Rr = np.asarray(left, dtype=np.int64).reshape(-1), np.asarray(right, dtype=np.int64).reshape(-1)
+    narrow = (P == 32) & (L >= 0) & (Rr >= 0) & (L <= 128 * 4) & (Rr <= 128 * 4 - 1)
+    return np.where(narrow, 4, P // 2).astype(np.int32)
+
+
 def ola_runs(pm_rel_list, starts, out_lens, out_offs, fft_len, n_slots, frames_per_run=None, weights=None, gcuts=None):
     """
     Plans the fused overlap-add (include/magphase_hip.h: mpx_synthesis_lossless_ola).  The batch's frames, in utterance

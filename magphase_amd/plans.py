@@ -510,6 +510,9 @@ class LosslessRoundTripPlan:
         # n_slots: overrides the engine's slot count (small tests)
         self.engine = engine
         self.deal = "count"   # how the frames were dealt to the slots: "cost" (_deal_by_cost) or "count"
+        # MAGPHASE_RT_SUPPORT=full (read here, at plan build): every frame takes the full support class -- the A/B switch of
+        # the kernel's compact-support instances (csrc/mpx_common.hpp: frame_support_class)
+        self.full_support = os.environ.get("MAGPHASE_RT_SUPPORT", "") == "full"
         if not utts:   # an empty batch: nothing to plan, run() returns empty tensors
             self.analysis = self.synthesis = None
             self.fft_len = fft_len or 4096
@@ -567,7 +570,8 @@ class LosslessRoundTripPlan:
             out = e.empty((self.total_out,))
         if self.total_frames == 0:
             return feats, out
-        _run_ola(e, lambda strips, out: e.roundtrip_lossless_ola(self.fft_len, a, s, feats, strips, out),
+        _run_ola(e, lambda strips, out: e.roundtrip_lossless_ola(self.fft_len, a, s, feats, strips, out,
+                                                                 full_support=self.full_support),
                  self.fft_len, s, strips, out, self.total_out)
         return feats, out
 
