@@ -217,6 +217,10 @@ int mpx_synthesis_lossless_ola(void* stream, int fft_len, const void* tables, co
                                float* pcm_out, int64_t ld /* row pitch of mag/real/imag */);
 int mpx_ola_fixup(void* stream, int fft_len, const mpx_ola_run* runs, int32_t n_runs, const float* strips,
                   float* pcm_out);
+/* The same with the launch sized by the run table's widest fix range: max_width = the largest fix_hi - (fix_lo & ~63) of
+ * the runs (0 <= max_width <= fft_len + 127; 0: nothing to fix, no launch).  Ranges wider than max_width are not completed. */
+int mpx_ola_fixup_width(void* stream, int fft_len, const mpx_ola_run* runs, int32_t n_runs, const float* strips,
+                        float* pcm_out, int32_t max_width);
 /*
  * mpx_synthesis_lossless_ola with row tables (constant-rate lossless synthesis, magphase.py:2242-2252 + :1759-1776):
  * frame f is synthesised from the row (1 - row_t[f]) x[row0[f]] + row_t[f] x[row1[f]] of each of mag / real / imag
@@ -350,6 +354,15 @@ int mpx_roundtrip_lossless_ola_flags(void* stream, int fft_len, const void* tabl
                                      uint32_t flags);
 int mpx_roundtrip_support_classes(int fft_len, const int32_t* frame_left, const int32_t* frame_right, int64_t n_frames,
                                   int32_t* class_host);
+/*
+ * What the kernel that mpx_roundtrip_lossless_ola_flags launches for (fft_len, flags) can add to its overlap-add ring, per
+ * frame: extents_host: int32 [n_frames][2], the half-open range (ext_lo, ext_hi) of frame samples.  (1536, 2560) for a frame
+ * of support class 4 at fft_len 4096 where the launched instance has the pruned passes; (0, fft_len) for every other frame,
+ * and for every frame under MPX_RT_FULL_SUPPORT or in a build without those passes.  The planner sizes the seams between
+ * runs by these (mpx_host_ola_runs_extents).  Host function: no stream, no device.
+ */
+int mpx_roundtrip_frame_extents(int fft_len, const int32_t* frame_left, const int32_t* frame_right, int64_t n_frames,
+                                uint32_t flags, int32_t* extents_host);
 
 /*
  * One iteration of the pitch-synchronous Griffin-Lim algorithm (magphase.py:3320-3372, the loop body after the first
@@ -888,6 +901,16 @@ int64_t mpx_host_plan_lossless_synthesis(int32_t n_utts, const double* f0, const
 int64_t mpx_host_ola_runs(int32_t n_utts, const int64_t* pm_rel, const int64_t* frame_off, const int64_t* starts,
                           const int64_t* out_lens, const int64_t* out_offs, int32_t fft_len, const int64_t* gcuts,
                           int64_t n_gcuts, mpx_ola_run* runs, int64_t cap_runs);
+/*
+ * The same with per-frame extents (int32 [frames][2], global frame index: the half-open range of a frame's samples that
+ * can be non-zero, 0 <= ext_lo <= ext_hi <= fft_len; mpx_roundtrip_frame_extents).  A run then ends where its frames'
+ * extents end (never before its predecessor's end), its successor's head strip ends there, and a fix range begins no
+ * earlier than the successor's first extent: the seams move no zeros.  Everything outside the extents must be an exact
+ * zero the kernel never adds.  extents == NULL: mpx_host_ola_runs' result.  Bit-identical to hostmath.ola_runs(extents=).
+ */
+int64_t mpx_host_ola_runs_extents(int32_t n_utts, const int64_t* pm_rel, const int64_t* frame_off, const int64_t* starts,
+                                  const int64_t* out_lens, const int64_t* out_offs, int32_t fft_len, const int64_t* gcuts,
+                                  int64_t n_gcuts, const int32_t* extents, mpx_ola_run* runs, int64_t cap_runs);
 
 /*
  * mpx_host_deal_cuts: cuts for mpx_host_ola_runs that deal the frames by COST instead of by count.  Frame f costs slot s

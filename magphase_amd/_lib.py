@@ -48,9 +48,11 @@ PROTOTYPES = {
     "mpx_analysis_lossless_backward": (i32, [vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, i64,
                                              vp, i64]),
     "mpx_ola_fixup": (i32, [vp, i32, vp, i32, vp, vp]),
+    "mpx_ola_fixup_width": (i32, [vp, i32, vp, i32, vp, vp, i32]),
     "mpx_roundtrip_lossless_ola": (i32, [vp, i32] + [vp] * 5 + [i64, vp, i32, vp, vp, i32] + [vp] * 6 + [i64]),
     "mpx_roundtrip_lossless_ola_flags": (i32, [vp, i32] + [vp] * 5 + [i64, vp, i32, vp, vp, i32] + [vp] * 6 + [i64, u32]),
     "mpx_roundtrip_support_classes": (i32, [i32, vp, vp, i64, vp]),
+    "mpx_roundtrip_frame_extents": (i32, [i32, vp, vp, i64, u32, vp]),
     "mpx_roundtrip_slot_weights": (i32, [vp, i32]),
     "mpx_roundtrip_frame_terms": (i32, [i32, vp, vp, i64, vp]),
     "mpx_roundtrip_slot_costs": (i32, [vp, i32]),
@@ -81,6 +83,7 @@ PROTOTYPES = {
                                        i64] + [vp] * 9 + [i64, vp, i32]),
     "mpx_host_plan_lossless_synthesis": (i64, [i32, vp, vp, vp, i32] + [vp] * 4),
     "mpx_host_ola_runs": (i64, [i32] + [vp] * 5 + [i32, vp, i64, vp, i64]),
+    "mpx_host_ola_runs_extents": (i64, [i32] + [vp] * 5 + [i32, vp, i64, vp, vp, i64]),
     "mpx_host_deal_cuts": (i64, [vp, i64, i32, vp, i32, vp, vp]),
     "mpx_host_widen_f32": (i32, [vp, vp, i64, i32]),
     "mpx_host_narrow_f64": (i32, [vp, vp, i64, i32]),

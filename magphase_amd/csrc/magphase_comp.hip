@@ -1653,6 +1653,10 @@ __device__ unsigned long long g_rt_endprobe[4 * 8192];   // per wave: start, end
 #ifndef MPX_RT_FORCE_NARROW
 #define MPX_RT_FORCE_NARROW 0   // 1 (timing experiments only, wrong results): every frame is treated as the narrow class
 #endif
+// Whether k_roundtrip_pair<P, CLS> has the pruned passes: the one condition the kernel and the host's view of what its
+// frames add to the ring (mpx_roundtrip_frame_extents) both read.
+template <int P>
+constexpr bool roundtrip_prunes(bool cls) { return cls && P == 32 && comp_compact<P>() && !MPX_COMP_DIT; }
 template <int P, bool CLS = false>
 __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const float* __restrict__ sig,
                                                                        const long long* __restrict__ fpos,
@@ -1667,7 +1671,7 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
                                                                        float* __restrict__ oimag, float* __restrict__ strips,
                                                                        float* __restrict__ pcm, long long ld) {
     constexpr int M = 64 * P, N = 2 * M, HP = P / 2;
-    constexpr bool kCls = CLS && P == 32 && comp_compact<P>() && !MPX_COMP_DIT;   // the forms that have pruned passes
+    constexpr bool kCls = roundtrip_prunes<P>(CLS);   // the forms that have pruned passes
     constexpr int NW = kCls ? kSupportNarrow : 0;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     PairWave w;
@@ -2871,6 +2875,33 @@ int mpx_roundtrip_support_classes(int fft_len, const int32_t* frame_left, const 
     if (n_frames < 0 || (n_frames > 0 && (!frame_left || !frame_right || !class_host)))
         return fail(MPX_ERR_ARG, "mpx_roundtrip_support_classes: bad arguments%s");
     for (int64_t f = 0; f < n_frames; ++f) class_host[f] = frame_support_class(frame_left[f], frame_right[f], fft_len);
+    return MPX_OK;
+}
+
+// What the instance that mpx_roundtrip_lossless_ola_flags launches for (fft_len, flags) can add to the ring, per frame: the
+// samples of the rows support_row_live names for a frame the kernel takes as narrow, the whole frame otherwise -- and the
+// whole frame throughout where that instance has no pruned passes (the launch's own choice of CLS, roundtrip_prunes).
+int mpx_roundtrip_frame_extents(int fft_len, const int32_t* frame_left, const int32_t* frame_right, int64_t n_frames,
+                                uint32_t flags, int32_t* extents_host) {
+    if (flags & ~(uint32_t)MPX_RT_FULL_SUPPORT) return fail(MPX_ERR_ARG, "mpx_roundtrip_frame_extents: unknown flag%s");
+    const int P = p_of(fft_len);
+    if (!P) return fail(MPX_ERR_ARG, "mpx_roundtrip_frame_extents: fft_len must be 1024, 2048 or 4096%s");
+    if (n_frames < 0 || (n_frames > 0 && (!frame_left || !frame_right || !extents_host)))
+        return fail(MPX_ERR_ARG, "mpx_roundtrip_frame_extents: bad arguments%s");
+    const bool cls = (P == 32) && !(flags & MPX_RT_FULL_SUPPORT);   // MPX_LAUNCH_RT's choice below
+    const bool prunes = (P == 32) && roundtrip_prunes<32>(cls);
+    int n_lo = fft_len, n_hi = 0;   // the samples of the narrow class's live rows
+    for (int q = 0; q < P; ++q)
+        if (support_row_live(q, kSupportNarrow, P)) {
+            n_lo = (128 * q < n_lo) ? 128 * q : n_lo;
+            n_hi = (128 * q + 128 > n_hi) ? 128 * q + 128 : n_hi;
+        }
+    for (int64_t f = 0; f < n_frames; ++f) {
+        const bool narrow = prunes && (MPX_RT_FORCE_NARROW ||
+                                       frame_support_class(frame_left[f], frame_right[f], fft_len) == kSupportNarrow);
+        extents_host[2 * f + 0] = narrow ? n_lo : 0;
+        extents_host[2 * f + 1] = narrow ? n_hi : fft_len;
+    }
     return MPX_OK;
 }
 

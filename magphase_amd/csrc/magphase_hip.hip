@@ -1177,4 +1177,20 @@ int mpx_ola_fixup(void* stream, int fft_len, const mpx_ola_run* runs, int32_t n_
     return MPX_OK;
 }
 
+// mpx_ola_fixup with the column blocks sized by the plan's widest fix range (max over the runs of fix_hi - (fix_lo & ~63),
+// which the caller computed from its run table) instead of by the widest a head strip can hold.
+int mpx_ola_fixup_width(void* stream, int fft_len, const mpx_ola_run* runs, int32_t n_runs, const float* strips,
+                        float* pcm_out, int32_t max_width) {
+    if (!p_of(fft_len)) return fail(MPX_ERR_ARG, "mpx_ola_fixup_width: fft_len must be 1024, 2048 or 4096%s");
+    if (n_runs < 0) return fail(MPX_ERR_ARG, "mpx_ola_fixup_width: negative count%s");
+    if (max_width < 0 || max_width > fft_len + 127) return fail(MPX_ERR_ARG, "mpx_ola_fixup_width: width out of range%s");
+    if (n_runs == 0 || max_width == 0) return MPX_OK;   // no run has anything to fix: no launch
+    if (!runs || !strips || !pcm_out) return fail(MPX_ERR_ARG, "mpx_ola_fixup_width: null pointer%s");
+    if (n_runs > 2147483647 / 2) return fail(MPX_ERR_ARG, "mpx_ola_fixup_width: too many runs%s");
+    const dim3 block(256), grid((unsigned)n_runs, (unsigned)((max_width + 1023) / 1024));
+    hipLaunchKernelGGL(k_ola_fixup, grid, block, 0, (hipStream_t)stream, (const RunDesc*)runs, strips, pcm_out);
+    MPX_HIP_CHECK(hipGetLastError());
+    return MPX_OK;
+}
+
 }  // extern "C"

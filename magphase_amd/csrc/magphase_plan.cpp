@@ -450,9 +450,11 @@ int64_t mpx_host_plan_lossless_synthesis(int32_t n_utts, const double* f0, const
 
 // hostmath.ola_runs in its default mode (global equal shares `gcuts`, computed by the caller).  runs: capacity
 // n_utts + n_gcuts records; returns the number of runs or a negative error.
-int64_t mpx_host_ola_runs(int32_t n_utts, const int64_t* pm_rel, const int64_t* frame_off, const int64_t* starts,
-                          const int64_t* out_lens, const int64_t* out_offs, int32_t fft_len, const int64_t* gcuts,
-                          int64_t n_gcuts, mpx_ola_run* runs, int64_t cap_runs) {
+// extents: null (every frame fills [rel, rel + N)), or per frame (global index) the half-open range (ext_lo, ext_hi) of its
+// samples that can be non-zero -- the seams between runs are then sized by what the frames really reach.
+static int64_t ola_runs_impl(int32_t n_utts, const int64_t* pm_rel, const int64_t* frame_off, const int64_t* starts,
+                             const int64_t* out_lens, const int64_t* out_offs, int32_t fft_len, const int64_t* gcuts,
+                             int64_t n_gcuts, const int32_t* extents, mpx_ola_run* runs, int64_t cap_runs) {
     if (n_utts < 0 || fft_len <= 0 || n_gcuts < 1) return -1;
     if (n_utts > 0 && (!pm_rel || !frame_off || !starts || !out_lens || !out_offs || !gcuts || !runs)) return -1;
     const int64_t N = fft_len, strip_floats = N + 64;
@@ -494,7 +496,19 @@ int64_t mpx_host_ola_runs(int32_t n_utts, const int64_t* pm_rel, const int64_t* 
         int64_t prev_hi = 0;
         for (int64_t i = 0; i < k; ++i) {
             const int64_t fb = cuts[(size_t)i], fe = cuts[(size_t)i + 1];
-            const int64_t hi = rel[fe - 1] + N;
+            // hi: the end of what the run's frames (and its predecessors') reach; lo_t: where its own frames begin
+            int64_t hi = rel[fe - 1] + N, lo_t = rel[fb];
+            if (extents) {
+                hi = prev_hi;
+                if (fe > fb) lo_t = INT64_MAX;
+                for (int64_t j = fb; j < fe; ++j) {
+                    const int64_t e_lo = extents[2 * (f_base + j)], e_hi = extents[2 * (f_base + j) + 1];
+                    if (e_lo < 0 || e_hi < e_lo || e_hi > N) return -3000000;
+                    hi = std::max(hi, rel[j] + e_hi);
+                    lo_t = std::min(lo_t, rel[j] + e_lo);
+                }
+            }
+            if (lo_t > prev_hi) lo_t = prev_hi;   // (a head that begins past the predecessor's end: nothing to fix)
             const int64_t lo = (rel[fb] < prev_hi) ? rel[fb] : prev_hi;
             int64_t m = (lo - start + o0) % 64;   // numpy's % : non-negative for a positive divisor
             if (m < 0) m += 64;
@@ -508,7 +522,7 @@ int64_t mpx_host_ola_runs(int32_t n_utts, const int64_t* pm_rel, const int64_t* 
             int64_t out_hi = (own_hi < start + out_len ? own_hi : start + out_len) - x0;
             if (out_hi < out_lo) out_hi = out_lo;
             const int64_t flush_end = (hi > own_hi ? hi : own_hi) - x0;
-            const int64_t fix_lo = (lo > start ? lo : start) - x0;
+            const int64_t fix_lo = std::max(std::max(lo, lo_t), start) - x0;
             int64_t fix_hi = (prev_hi < start + out_len ? prev_hi : start + out_len) - x0;
             fix_hi = (i > 0) ? (fix_hi > fix_lo ? fix_hi : fix_lo) : fix_lo;
             mpx_ola_run& r = runs[nr];
@@ -529,6 +543,20 @@ int64_t mpx_host_ola_runs(int32_t n_utts, const int64_t* pm_rel, const int64_t* 
         }
     }
     return nr;
+}
+
+int64_t mpx_host_ola_runs(int32_t n_utts, const int64_t* pm_rel, const int64_t* frame_off, const int64_t* starts,
+                          const int64_t* out_lens, const int64_t* out_offs, int32_t fft_len, const int64_t* gcuts,
+                          int64_t n_gcuts, mpx_ola_run* runs, int64_t cap_runs) {
+    return ola_runs_impl(n_utts, pm_rel, frame_off, starts, out_lens, out_offs, fft_len, gcuts, n_gcuts, nullptr, runs,
+                         cap_runs);
+}
+
+int64_t mpx_host_ola_runs_extents(int32_t n_utts, const int64_t* pm_rel, const int64_t* frame_off, const int64_t* starts,
+                                  const int64_t* out_lens, const int64_t* out_offs, int32_t fft_len, const int64_t* gcuts,
+                                  int64_t n_gcuts, const int32_t* extents, mpx_ola_run* runs, int64_t cap_runs) {
+    return ola_runs_impl(n_utts, pm_rel, frame_off, starts, out_lens, out_offs, fft_len, gcuts, n_gcuts, extents, runs,
+                         cap_runs);
 }
 
 // hostmath.deal_cuts: consecutive shares of the frame sequence whose LARGEST slot cost is minimal.  Frame f costs slot s

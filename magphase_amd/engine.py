@@ -1498,7 +1498,13 @@ class Engine:
         return sig_out
 
     def ola_fixup(self, fft_len, plan, strips, pcm_out):
-        self.launch("mpx_ola_fixup", int(fft_len), plan.runs, int(plan.n_runs), strips, pcm_out)
+        """Completes the run boundaries; a run table that knows its widest fix range (fix_width: the round-trip plan's
+        seams by frame extents, plans._SeamRuns) gets a launch sized by it (mpx_ola_fixup_width)."""
+        width = getattr(plan, "fix_width", None)
+        if width is None:
+            self.launch("mpx_ola_fixup", int(fft_len), plan.runs, int(plan.n_runs), strips, pcm_out)
+        else:
+            self.launch("mpx_ola_fixup_width", int(fft_len), plan.runs, int(plan.n_runs), strips, pcm_out, int(width))
         return pcm_out
 
 

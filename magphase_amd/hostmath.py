@@ -365,7 +365,24 @@ def roundtrip_support_classes(left, right, fft_len):
     return np.where(narrow, 4, P // 2).astype(np.int32)
 
 
-def ola_runs(pm_rel_list, starts, out_lens, out_offs, fft_len, n_slots, frames_per_run=None, weights=None, gcuts=None):
+def roundtrip_frame_extents(left, right, fft_len, full_support=False):
+    """mpx_roundtrip_frame_extents in numpy, for the library's default build: per frame the half-open range (ext_lo,
+    ext_hi) of its samples that k_roundtrip_pair can add to the overlap-add ring.  A frame of support class W below the
+    full one adds the register rows P/2 - W <= q < P/2 + W only (csrc/mpx_common.hpp: support_row_live), samples
+    [128 (P/2 - W), 128 (P/2 + W)) -- class 4 at N = 4096: (1536, 2560); every other frame, every other N and every frame
+    under full_support (MPX_RT_FULL_SUPPORT: the instance without pruned passes is launched): (0, N).  A library built
+    without the pruned instances answers (0, N) throughout; the plans ask the library, never this twin.
+    int32 [n_frames, 2]."""
+    N = int(fft_len)
+    P = N // 128
+    W = roundtrip_support_classes(left, right, N).astype(np.int64)
+    if full_support:
+        W = np.full_like(W, P // 2)
+    return np.stack([128 * (P // 2 - W), 128 * (P // 2 + W)], axis=1).astype(np.int32)
+
+
+def ola_runs(pm_rel_list, starts, out_lens, out_offs, fft_len, n_slots, frames_per_run=None, weights=None, gcuts=None,
+             extents=None):
     """
     Plans the fused overlap-add (include/magphase_hip.h: mpx_synthesis_lossless_ola).  The batch's frames, in utterance
     order, are dealt to the device's pair slots in consecutive shares: equal ones (slot s gets the frames
@@ -380,6 +397,13 @@ def ola_runs(pm_rel_list, starts, out_lens, out_offs, fft_len, n_slots, frames_p
     [start, start + out_len).  Only ADJACENT runs of an utterance may overlap: rel[next run's first frame] -
     rel[own first frame - 1] >= N for every run with both neighbours (a cut violating it is MOVED FORWARD to the first
     frame that satisfies it, _enforce_span; only a cut with no such frame left in the utterance is dropped).
+
+    ``extents`` (int [total frames, 2], or None): per frame the half-open range (ext_lo, ext_hi) of its samples that can be
+    non-zero (roundtrip_frame_extents; None: (0, N), a dense frame).  The seams between runs are then sized by what the
+    frames really reach: a run ends at hi_t = the largest rel + ext_hi of its frames (and never before its predecessor's
+    end), its successor's head strip, the positions both write, ends there, and the fix range begins no earlier than
+    lo_t = the smallest rel + ext_lo of the successor's frames.  Everything outside the extents must be an exact zero
+    that the kernel never adds to its ring.  The cuts keep their N-wide rule.
 
     pm_rel_list: per utterance int64[F_u]; starts / out_lens: ola_plan's (out_start, out_len) per utterance;
     out_offs: int64[U+1] offsets of the utterances in pcm_out.
@@ -396,6 +420,11 @@ def ola_runs(pm_rel_list, starts, out_lens, out_offs, fft_len, n_slots, frames_p
     else:
         target = max(1, -(-total // n_slots))
         gcuts = slot_cuts(total, n_slots, weights) if gcuts is None else np.asarray(gcuts, dtype=np.int64)
+    if extents is not None:
+        extents = np.asarray(extents, dtype=np.int64).reshape(-1, 2)
+        if extents.shape[0] != total or np.any(extents[:, 0] < 0) or np.any(extents[:, 1] < extents[:, 0]) \
+                or np.any(extents[:, 1] > N):
+            raise ValueError("ola_runs: extents must be [total frames, 2] with 0 <= ext_lo <= ext_hi <= N")
     recs = []
     f_base = 0
     for u, rel in enumerate(pm_rel_list):
@@ -412,7 +441,17 @@ def ola_runs(pm_rel_list, starts, out_lens, out_offs, fft_len, n_slots, frames_p
         fb, fe = cuts[:-1], cuts[1:]
         k = fb.size
         hi = rel[fe - 1] + N                          # end of the run's last frame
+        lo_t = rel[fb]                                # beginning of its first
+        if extents is not None:   # ... of what its frames reach, and never before the end of the previous run
+            p_lo, p_hi = rel + extents[f_base:f_base + n, 0], rel + extents[f_base:f_base + n, 1]
+            hi, lo_t, reach = hi.copy(), lo_t.copy(), 0
+            for i in range(k):
+                if fe[i] > fb[i]:
+                    reach = max(reach, int(p_hi[fb[i]:fe[i]].max()))
+                    lo_t[i] = p_lo[fb[i]:fe[i]].min()
+                hi[i] = reach
         prev_hi = np.concatenate(([0], hi[:-1]))      # positions < prev_hi also get the previous run's frames
+        lo_t = np.minimum(lo_t, prev_hi)              # (a head that begins past the predecessor's end: nothing to fix)
         # first position the run is responsible for: its first frame, or the end of the previous run's last frame if
         # that comes first (consecutive frames further apart than N leave a gap of zeros, which this run writes)
         lo = np.minimum(rel[fb], prev_hi)
@@ -429,7 +468,7 @@ def ola_runs(pm_rel_list, starts, out_lens, out_offs, fft_len, n_slots, frames_p
         out_hi = np.minimum(own_hi, start + out_len) - x0
         out_hi = np.maximum(out_hi, out_lo)
         flush_end = np.maximum(hi, own_hi) - x0
-        fix_lo = np.maximum(lo, start) - x0
+        fix_lo = np.maximum(np.maximum(lo, lo_t), start) - x0
         fix_hi = np.minimum(prev_hi, start + out_len) - x0
         fix_hi = np.where(np.arange(k) > 0, np.maximum(fix_hi, fix_lo), fix_lo)
         r = np.zeros(k, dtype=OLA_RUN_DTYPE)

@@ -136,9 +136,9 @@ def roundtrip_frame_terms(left, right, fft_len):
     return terms
 
 
-def ola_runs(pm_rel_cat, frame_off, starts, out_lens, out_offs, fft_len, n_slots, weights=None, gcuts=None):
+def ola_runs(pm_rel_cat, frame_off, starts, out_lens, out_offs, fft_len, n_slots, weights=None, gcuts=None, extents=None):
     """hostmath.ola_runs (default equal-share mode, or the caller's gcuts) on the concatenated frame positions ->
-    (runs, slot_off, slot_runs)."""
+    (runs, slot_off, slot_runs).  extents: per-frame (ext_lo, ext_hi) or None (mpx_host_ola_runs_extents)."""
     if not enabled():
         raise PlanFallback()
     lib = _lib.load()
@@ -151,9 +151,17 @@ def ola_runs(pm_rel_cat, frame_off, starts, out_lens, out_offs, fft_len, n_slots
     starts, out_lens, out_offs = (np.ascontiguousarray(a, dtype=np.int64) for a in (starts, out_lens, out_offs))
     cap = U + int(gcuts.size) + 1
     runs = np.zeros(cap, dtype=OLA_RUN_DTYPE)
-    n = int(lib.mpx_host_ola_runs(U, pm_rel.ctypes.data, frame_off.ctypes.data, starts.ctypes.data, out_lens.ctypes.data,
-                                  out_offs.ctypes.data, int(fft_len), gcuts.ctypes.data, int(gcuts.size),
-                                  runs.ctypes.data, cap))
+    if extents is None:
+        n = int(lib.mpx_host_ola_runs(U, pm_rel.ctypes.data, frame_off.ctypes.data, starts.ctypes.data,
+                                      out_lens.ctypes.data, out_offs.ctypes.data, int(fft_len), gcuts.ctypes.data,
+                                      int(gcuts.size), runs.ctypes.data, cap))
+    else:
+        extents = np.ascontiguousarray(extents, dtype=np.int32).reshape(-1, 2)
+        if extents.shape[0] != total:
+            raise PlanFallback()
+        n = int(lib.mpx_host_ola_runs_extents(U, pm_rel.ctypes.data, frame_off.ctypes.data, starts.ctypes.data,
+                                              out_lens.ctypes.data, out_offs.ctypes.data, int(fft_len), gcuts.ctypes.data,
+                                              int(gcuts.size), extents.ctypes.data, runs.ctypes.data, cap))
     if n < 0:
         raise PlanFallback()
     runs = runs[:n]

@@ -87,28 +87,34 @@ class _FlatRows:
 
 
 def _plan_ola_runs(plan, pm_rel_list, starts, out_lens, out_off_host, fft_len, n_slots, frames_per_run, up, weights=None,
-                   gcuts=None):
+                   gcuts=None, extents=None):
     """Shared by the two synthesis plans: runs + slot work lists (hostmath.ola_runs / balance_chunks) -> upload list.
     weights: the slots' relative speeds (Engine.synth_ola_slot_weights) or None for equal shares; gcuts: the caller's own
-    cuts of the frame sequence instead of shares by count (hostmath.ola_runs; ignored with frames_per_run)."""
+    cuts of the frame sequence instead of shares by count (hostmath.ola_runs; ignored with frames_per_run).
+    extents: what each frame of ONE kernel can add to the ring (hostmath.ola_runs), or None.  The plan's own run table
+    (plan.runs / plan.runs_host) is always the one for dense frames, which every overlap-add kernel may use; with extents a
+    second table of the same runs, its seams sized by them, is planned beside it (plan.seam_runs / plan.seam_runs_host,
+    plan.seam_fix_width = its widest fix range) for that kernel alone -- _SeamRuns."""
     fpr = frames_per_run or int(os.environ.get("MAGPHASE_OLA_FRAMES_PER_RUN", 0)) or None
-    try:
-        if fpr:
-            raise hostplan.PlanFallback()      # per-utterance run lengths (tests, tuning): the numpy planner only
-        if isinstance(pm_rel_list, _FlatRows):   # already one array + offsets (CompressedSynthesisPlan)
-            rel_cat, f_off = np.asarray(pm_rel_list.flat, dtype=np.int64), pm_rel_list.off
-            sizes = np.diff(f_off)
-        else:
-            sizes = [int(np.size(r)) for r in pm_rel_list]
-            rel_cat = np.concatenate([np.asarray(r, dtype=np.int64) for r in pm_rel_list]) if pm_rel_list else np.zeros(0, np.int64)
-            f_off = np.concatenate(([0], np.cumsum(sizes)))
-        runs, slot_off, slot_runs = hostplan.ola_runs(rel_cat, f_off, starts, out_lens,
-                                                      np.asarray(out_off_host)[:len(sizes)], fft_len, n_slots,
-                                                      weights=weights, gcuts=gcuts)
-    except hostplan.PlanFallback:
-        runs, slot_off, slot_runs = hm.ola_runs(pm_rel_list, starts, out_lens, out_off_host, fft_len, n_slots,
-                                                frames_per_run=fpr, weights=None if fpr else weights,
-                                                gcuts=None if fpr else gcuts)
+
+    def plan_runs(ext):
+        try:
+            if fpr:
+                raise hostplan.PlanFallback()      # per-utterance run lengths (tests, tuning): the numpy planner only
+            if isinstance(pm_rel_list, _FlatRows):   # already one array + offsets (CompressedSynthesisPlan)
+                rel_cat, f_off = np.asarray(pm_rel_list.flat, dtype=np.int64), pm_rel_list.off
+                sizes = np.diff(f_off)
+            else:
+                sizes = [int(np.size(r)) for r in pm_rel_list]
+                rel_cat = np.concatenate([np.asarray(r, dtype=np.int64) for r in pm_rel_list]) if pm_rel_list else np.zeros(0, np.int64)
+                f_off = np.concatenate(([0], np.cumsum(sizes)))
+            return hostplan.ola_runs(rel_cat, f_off, starts, out_lens, np.asarray(out_off_host)[:len(sizes)], fft_len,
+                                     n_slots, weights=weights, gcuts=gcuts, extents=ext)
+        except hostplan.PlanFallback:
+            return hm.ola_runs(pm_rel_list, starts, out_lens, out_off_host, fft_len, n_slots, frames_per_run=fpr,
+                               weights=None if fpr else weights, gcuts=None if fpr else gcuts, extents=ext)
+
+    runs, slot_off, slot_runs = plan_runs(None)
     plan.n_runs = int(runs.size)
     plan.runs_host = runs
     plan.strip_floats = plan.n_runs * (int(fft_len) + 64)
@@ -116,6 +122,34 @@ def _plan_ola_runs(plan, pm_rel_list, starts, out_lens, out_off_host, fft_len, n
     up.append(("runs", runs.view(np.uint8), np.uint8))
     up.append(("slot_off", slot_off, np.int32))
     up.append(("slot_runs", slot_runs, np.int32))
+    if extents is not None:
+        seam, s_off, s_runs = plan_runs(extents)
+        # the same frames in the same runs on the same slots: the seam fields alone differ
+        if not (np.array_equal(seam["frame_begin"], runs["frame_begin"]) and np.array_equal(seam["frame_end"], runs["frame_end"])
+                and np.array_equal(seam["strip_off"], runs["strip_off"]) and np.array_equal(s_off, slot_off)
+                and np.array_equal(s_runs, slot_runs)):
+            raise ValueError("run planning with extents must keep the runs of the dense plan")
+        # as k_ola_fixup walks a range: from the 64-element block fix_lo lies in to fix_hi (runs with nothing to fix: 0)
+        width = np.where(seam["fix_hi"] > seam["fix_lo"], seam["fix_hi"] - (seam["fix_lo"] & ~63), 0)
+        plan.seam_runs_host = seam
+        plan.seam_fix_width = int(width.max()) if width.size else 0
+        up.append(("seam_runs", seam.view(np.uint8), np.uint8))
+
+
+class _SeamRuns:
+    """A synthesis plan seen through its second run table (_plan_ola_runs with extents): what the launch of the one kernel
+    whose frames have those extents and the fix-up after it read -- the same runs, slots, positions and strips as the plan's
+    own, dense table, the seam fields sized by the extents, and the widest fix range for Engine.ola_fixup."""
+
+    def __init__(self, plan):
+        self.runs, self.runs_host, self.fix_width = plan.seam_runs, plan.seam_runs_host, plan.seam_fix_width
+        self.n_runs, self.n_slots, self.strip_floats = plan.n_runs, plan.n_slots, plan.strip_floats
+        self.slot_off, self.slot_runs, self.pm_rel = plan.slot_off, plan.slot_runs, plan.pm_rel
+        # mpx_ola_fixup_width leaves a range wider than the width it is given uncompleted and cannot see the table: the
+        # width must cover every range as k_ola_fixup walks it
+        r = self.runs_host
+        assert not r.size or self.fix_width >= int(np.max(np.where(r["fix_hi"] > r["fix_lo"],
+                                                                   r["fix_hi"] - (r["fix_lo"] & ~63), 0)))
 
 
 def _run_ola(engine, entry, fft_len, runs, strips, out, total_out):
@@ -406,7 +440,10 @@ class LosslessSynthesisPlan:
     All float64/int host math; device gets int tables.
     """
 
-    def __init__(self, engine, f0_list, fs_list, fft_len, frames_per_run=None, comp_slots=False, gcuts=None, n_slots=None):
+    def __init__(self, engine, f0_list, fs_list, fft_len, frames_per_run=None, comp_slots=False, gcuts=None, n_slots=None,
+                 extents=None):
+        # extents: int [total frames, 2], what each frame of one kernel can add to the ring, or a callable(total frames) that
+        #          returns them or None: a second run table for that kernel beside the plan's own (_plan_ola_runs, _SeamRuns)
         # comp_slots: the slot count and weights of the compressed / round-trip pair kernels (mpx_synth_comp_slots)
         # n_slots: overrides the engine's slot count (small tests; the launch grid follows it)
         # gcuts: the caller's cuts of the frame sequence, one share per slot, or a callable(n_slots, total_frames) that
@@ -461,8 +498,10 @@ class LosslessSynthesisPlan:
                 weights = np.asarray(weights)[:n_slots] if len(weights) >= n_slots else None
         if callable(gcuts):
             gcuts = gcuts(n_slots, self.total_frames)
+        if callable(extents):
+            extents = extents(self.total_frames)
         _plan_ola_runs(self, pm_rel, starts, lens, self.out_off_host, fft_len, n_slots, frames_per_run, _up, weights=weights,
-                       gcuts=gcuts)
+                       gcuts=gcuts, extents=extents)
         for _k, _t in e.to_device_packed(_up).items():
             setattr(self, _k, _t)
 
@@ -513,8 +552,13 @@ class LosslessRoundTripPlan:
         # MAGPHASE_RT_SUPPORT=full (read here, at plan build): every frame takes the full support class -- the A/B switch of
         # the kernel's compact-support instances (csrc/mpx_common.hpp: frame_support_class)
         self.full_support = os.environ.get("MAGPHASE_RT_SUPPORT", "") == "full"
+        # MAGPHASE_RT_SEAMS=full (read here, at plan build; implied by MAGPHASE_RT_SUPPORT=full): the seams between runs are
+        # sized as if every frame filled its N samples -- the A/B switch of the seams sized by what the frames really add
+        # (_frame_extents, hostmath.ola_runs)
+        self.full_seams = self.full_support or os.environ.get("MAGPHASE_RT_SEAMS", "") == "full"
         if not utts:   # an empty batch: nothing to plan, run() returns empty tensors
-            self.analysis = self.synthesis = None
+            self.analysis = self.synthesis = self.seams = None
+            self.seam_geometry = "dense" if self.full_seams else "extents"
             self.fft_len = fft_len or 4096
             self.total_frames = self.total_out = 0
             self.out_off_host = np.zeros(1, dtype=np.int64)
@@ -525,12 +569,39 @@ class LosslessRoundTripPlan:
                    and not os.environ.get("MAGPHASE_OLA_FRAMES_PER_RUN"))
         self.synthesis = LosslessSynthesisPlan(engine, self.analysis.v_f0, self.analysis.fs, self.fft_len,
                                                frames_per_run=frames_per_run, comp_slots="roundtrip", n_slots=n_slots,
-                                               gcuts=self._deal_by_cost if by_cost else None)
+                                               gcuts=self._deal_by_cost if by_cost else None,
+                                               extents=None if self.full_seams else self._frame_extents)
         if self.synthesis.total_frames != self.analysis.total_frames:
             raise ValueError("round trip: the synthesis plan must cover exactly the analysed frames")
         self.total_frames = self.analysis.total_frames
         self.total_out = self.synthesis.total_out
         self.out_off_host = self.synthesis.out_off_host
+        # What run() launches by.  self.synthesis stays a complete plan for dense frames (its run table serves any
+        # overlap-add kernel, k_synth_ola_pair on rows from elsewhere included); the table whose seams are sized by what THIS
+        # kernel's frames add is the round trip's own: self.seams / self.runs_host (the dense one under MAGPHASE_RT_SEAMS=full)
+        self.seams = _SeamRuns(self.synthesis) if hasattr(self.synthesis, "seam_runs") else self.synthesis
+        # the geometry run() really has: "extents", or "dense" -- asked for (full_seams), or because the analysis plan kept
+        # no host tables to take the extents from (dense is always valid; this attribute is where that shows)
+        self.seam_geometry = "extents" if isinstance(self.seams, _SeamRuns) else "dense"
+
+    @property
+    def runs_host(self):
+        """The run table run() launches by, as a host array (OLA_RUN_DTYPE); empty for an empty batch."""
+        return self.seams.runs_host if self.seams is not None else np.zeros(0, dtype=hm.OLA_RUN_DTYPE)
+
+    def _frame_extents(self, total_frames):
+        """Per frame the samples that the instance of k_roundtrip_pair this plan launches can add to the ring
+        (mpx_roundtrip_frame_extents: the library's own answer, from the kernel's compile-time condition and the launch
+        flags), for the run planner's seams.  None -- dense frames -- without the analysis plan's host tables."""
+        tabs = getattr(self.analysis, "_host_tabs", None)
+        if tabs is None or int(np.size(tabs[1])) != total_frames or int(np.size(tabs[2])) != total_frames:
+            return None
+        left, right = (np.ascontiguousarray(t, dtype=np.int32) for t in (tabs[1], tabs[2]))
+        ext = np.empty((total_frames, 2), dtype=np.int32)
+        _lib.check(self.engine.lib.mpx_roundtrip_frame_extents(int(self.fft_len), left.ctypes.data, right.ctypes.data,
+                                                               int(total_frames), 1 if self.full_support else 0,
+                                                               ext.ctypes.data), "mpx_roundtrip_frame_extents")
+        return ext
 
     def _deal_by_cost(self, n_slots, total_frames):
         """The cuts that deal the batch's frames to k_roundtrip_pair's slots by what they cost there, not by their number:
@@ -563,7 +634,7 @@ class LosslessRoundTripPlan:
         return cuts
 
     def run(self, feats=None, strips=None, out=None):
-        e, a, s = self.engine, self.analysis, self.synthesis
+        e, a, s = self.engine, self.analysis, self.seams
         if feats is None:
             feats = tuple(e.empty_feats(self.total_frames, self.fft_len // 2 + 1) for _ in range(3))
         if out is None:
