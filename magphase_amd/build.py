@@ -22,11 +22,14 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-UNITS = ["magphase_hip.hip", "magphase_comp.hip", "magphase_f64.hip", "magphase_epochs.hip", "magphase_probe.hip", "magphase_merlin.hip", "magphase_noise.hip", "magphase_true_env.hip",
-         "magphase_type2.hip", "magphase_pack.hip", "magphase_grad.hip",
-         "magphase_host.cpp", "magphase_plan.cpp", "magphase_mtjump.cpp"]
+# Slowest first (single-job compile times, docs/LAB_NOTES.md: 47, 46, 36, 8, 7, 5 s, the rest 2-4 s each): the pool below
+# runs 8 compiles at a time, and a long unit started last would set the wall time of a clean build.
+UNITS = ["magphase_f64.hip", "magphase_warp.hip", "magphase_comp.hip", "magphase_hip.hip", "magphase_grad.hip",
+         "magphase_true_env.hip", "magphase_plan.cpp", "magphase_mtjump.cpp", "magphase_output.hip", "magphase_host.cpp",
+         "magphase_epochs.hip", "magphase_noise.hip", "magphase_pack.hip", "magphase_probe.hip", "magphase_type2.hip",
+         "magphase_merlin.hip"]
 SRCS = [os.path.join(CSRC, u) for u in UNITS]
-SRC = SRCS[0]
+SRC = os.path.join(CSRC, "magphase_hip.hip")
 HEADERS = [os.path.join(CSRC, "wave_fft.hpp"), os.path.join(CSRC, "wave_fft_f64.hpp"),
            os.path.join(CSRC, "mpx_common.hpp"), os.path.join(CSRC, "host_pool.hpp"),
            os.path.join(os.path.dirname(HERE), "include", "magphase_hip.h")]

@@ -392,7 +392,7 @@ constexpr int kFusedRedStride = 68;
 #define MPX_FUSED_M4 1
 #endif
 
-// the warp's operand prologue / epilogue (same formulas as magphase_comp.hip: warp_prologue / warp_epilogue)
+// the warp's operand prologue / epilogue (same formulas as magphase_warp.hip: warp_prologue / warp_epilogue)
 __device__ __forceinline__ float fused_prologue_mag(int mode, float x) {
     if (mode == 0) return __builtin_amdgcn_logf(fmaf(x, x, 1.0e-8f)) * 0.69314718055994531f;
     return (x > 0.0f) ? __logf(x) : -1.0e10f;
@@ -724,7 +724,7 @@ __global__ __launch_bounds__(kFusedWaves * 64) void k_analysis_warp_fused(
             __syncthreads();
             // a FRESH accumulator per chunk (16 or 32 terms), added to the round's totals afterwards: the partial sums of
             // one long float32 chain over operands of size ~10 cost 2e-6 on the phase features (the staged GEMM's two-level
-            // accumulation, magphase_comp.hip)
+            // accumulation, magphase_warp.hip)
             f32x4_t ca[T];
 #pragma unroll
             for (int t = 0; t < T; ++t) ca[t] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
@@ -819,7 +819,7 @@ __global__ __launch_bounds__(kFusedWaves * 64) void k_analysis_warp_fused(
 //               (a round with more than 16 constant-rate frames -- F0 below ~100 Hz -- sweeps again);
 //   phases      linear up to the 1e-8 floor term of their operand: the product runs on the variable-rate frames as in
 //               k_analysis_warp_fused and its phase_dim outputs are interpolated afterwards (k_warp_phase_rows,
-//               magphase_comp.hip), exactly as the staged path does since round 3 (mpx_mel_warp_rows).
+//               magphase_warp.hip), exactly as the staged path does since round 3 (mpx_mel_warp_rows).
 // A workgroup takes a CONTIGUOUS range of frames (frames_per_wg = 8 R - 1): its first round's window starts one frame early
 // (that frame is transformed twice per launch boundary: once per workgroup), every later round finds the halo -- |X| of the
 // previous round's last frame, 8 KB -- where wave 7 left it in global memory (`halo`, two round parities per workgroup; the

@@ -11,7 +11,7 @@
 //                           every frame interpolates two feature rows (constant -> variable frame rate) as it loads them.
 //   k_rows_lerp             one wavefront per output row: out = (1-t) rows[r0] + t rows[r1] for mag / real / imag.
 // No MFMA in this file: nothing on the lossless path is a dense contraction; the mel
-// warp / unwarp GEMMs of the compressed path (magphase_comp.hip) run on the fp32 MFMA.
+// warp / unwarp GEMMs of the compressed path (magphase_warp.hip) run on the fp32 MFMA.
 #include "mpx_common.hpp"
 
 namespace mpx {

@@ -5,7 +5,7 @@
 // recurring sequence over GF(2) whose characteristic polynomial phi has degree 19937.  With g(x) = x^J mod phi,
 //     X[n + J] = xor over the set bits i of g of X[n + i]            (n >= 624: words the recurrence produced)
 // so the 624-word window J words further on is a xor of windows of the next 19937 + 623 words -- a parallel reduction
-// (k_mt_jump in magphase_comp.hip) instead of J sequential steps.  This file computes phi once (Berlekamp-Massey on
+// (k_mt_seq + k_mt_xor in magphase_noise.hip) instead of J sequential steps.  This file computes phi once (Berlekamp-Massey on
 // 2 x 19937 output bits) and the ladder x^(J 2^l) mod phi by square-and-multiply, bit-packed in 64-bit words.
 // Nothing here is taken from an implementation: the recurrence constants are the published MT19937 parameters
 // (Matsumoto & Nishimura 1998), the jump identity is Haramoto et al. 2008.

@@ -253,7 +253,7 @@ def _warp_swz(r15):
 
 
 def test_mel_warp_lds_swizzle_is_conflict_free_and_round2_layout_was_not():
-    """k_mel_warp_mfma (magphase_comp.hip): fragment reads (lane -> row li = lane & 15, k group g = lane >> 4, step q) and
+    """k_mel_warp_mfma (magphase_warp.hip): fragment reads (lane -> row li = lane & 15, k group g = lane >> 4, step q) and
     staging writes (thread -> chunk c4 = t & 15 of row t >> 4) on the swizzled dense layout; the padded layout of round 2
     (row stride 68) conflicts in every read -- the 31 % SQ_LDS_BANK_CONFLICT of profiles/r02_v12."""
     for wave in range(4):
