@@ -624,6 +624,46 @@ int mpx_warp_phase_rows(void* stream, int64_t n_frames, int32_t phase_dim, const
                         float* out_imag);
 
 /*
+ * Backward pass of the mel warp (mpx_mel_warp / mpx_mel_warp_rows, cepstral magnitudes): up to three jobs in ONE launch,
+ *     grad_x[r][k] = d(x~[r][k]) * sum_{i < n_out} g[r][i] W[i][k],   k < n_bins,
+ * the product [rows x n_out] . [n_out x n_bins] on the f32 matrix instructions; g rows are dense ([rows x n_out]), the
+ * operand rows mag / real / imag have the row pitch ld, the output rows the pitch ld_grad (both >= n_bins; nothing is
+ * written between the rows).
+ *   magnitude job: g_mag [n_mag_rows x mag_dim], w_mag [mag_dim x n_bins], grad_mag [n_mag_rows x n_bins];
+ *                  x~[r] = mag[r], or with row0 / row1 / row_t (all null or all given, n_mag_rows entries)
+ *                  fma(mag[row1[r]] - mag[row0[r]], row_t[r], mag[row0[r]]), the forward's interpolated operand (the result
+ *                  is then per OUTPUT frame: mpx_rows_lerp_adjoint folds it onto the rows of mag);
+ *                  d = 2 x~ / (x~^2 + 1e-8), the derivative of ln(x~^2 + 1e-8): 0 at x~ == 0.
+ *   phase jobs:    h_real / h_imag [n_phase_rows x phase_dim], w_phase [phase_dim x n_bins], operands real / imag (plain
+ *                  rows), grad_real / grad_imag [n_phase_rows x n_bins]; d = 2 - 2e-8 e^{-2x}, the derivative of
+ *                  2x + 1e-8 e^{-2x}.  h is taken ALREADY MASKED by the forward's voicing mask and clip
+ *                  (mpx_phase_grad_mask; at the constant rate folded onto the variable-rate rows by
+ *                  mpx_rows_lerp_adjoint at n_bins = phase_dim in between).  live [n_phase_rows] or null: a row with
+ *                  live == 0 is one whose h is zero by construction (an unvoiced frame; a row no voiced frame reads) --
+ *                  it is written as zeros whatever its operand row holds, and a 64-row tile without a live row is
+ *                  written as zeros without reading its operands.
+ * A job whose grad_X is null is skipped (its other pointers are not looked at, nothing of it is written); a job with
+ * zero rows launches nothing; with nothing to do the call returns 0 without a launch.  n_out (mag_dim / phase_dim of a
+ * job that runs) must be in 1..64.  Every element of a non-null grad_X is written exactly once with plain stores: no
+ * atomics, deterministic.  Arguments are checked before the device is touched.
+ */
+int mpx_mel_warp_backward(void* stream, int32_t n_bins, const float* g_mag, const float* w_mag, int32_t mag_dim,
+                          const float* mag, int64_t n_mag_rows, const int32_t* row0, const int32_t* row1,
+                          const float* row_t, float* grad_mag, const float* h_real, const float* h_imag,
+                          const float* w_phase, int32_t phase_dim, const float* real, const float* imag,
+                          int64_t n_phase_rows, const float* live, float* grad_real, float* grad_imag, int64_t ld,
+                          int64_t ld_grad);
+
+/*
+ * The upstream gradients of the two phase streams through the voicing mask and clip of mpx_mel_warp's epilogue
+ * (magphase.py:2527-2532): h[f][j] = g[f][j] where voiced[f] != 0 and |out[f][j]| < 1, else 0 -- out_real / out_imag are
+ * the forward's own outputs, a clipped value is exactly +-1.0f, and the gradient there is defined as zero.  All matrices
+ * dense [n_frames x phase_dim].  A null h_X skips that stream.
+ */
+int mpx_phase_grad_mask(void* stream, int64_t n_frames, int32_t phase_dim, const float* voiced, const float* out_real,
+                        const float* out_imag, const float* g_real, const float* g_imag, float* h_real, float* h_imag);
+
+/*
  * Minimum-phase spectrum of a magnitude spectrum by the complex cepstrum (la.build_min_phase_from_mag_spec,
  * libaudio.py:920-934; synthesis_from_compressed(per_phase_type='min_phase'), magphase.py:937-938).
  * For output frame f: m = (1-row_t)*mag[row0] + row_t*mag[row1] ([rows x H]); out_mag[f] = m and

@@ -96,6 +96,8 @@ PROTOTYPES = {
     "mpx_mel_warp_fbank": (i32, [vp, i64, i32] + [vp] * 7 + [i32, vp, i32] + [vp] * 4 + [i64]),
     "mpx_mel_warp_rows": (i32, [vp, i64, i32] + [vp] * 7 + [i32, vp, i32] + [vp] * 4 + [i64, i32, i64, vp, vp, vp]),
     "mpx_warp_phase_rows": (i32, [vp, i64, i32] + [vp] * 8),
+    "mpx_mel_warp_backward": (i32, [vp, i32, vp, vp, i32, vp, i64] + [vp] * 7 + [i32, vp, vp, i64, vp, vp, vp, i64, i64]),
+    "mpx_phase_grad_mask": (i32, [vp, i64, i32] + [vp] * 7),
     "mpx_min_phase": (i32, [vp, i32] + [vp] * 5 + [i64, vp, vp, vp, i64]),
     "mpx_true_envelope": (i32, [vp, i32, vp, vp, vp, i64, i64, i32, f64, i32, vp, i64, vp, vp, vp]),
     "mpx_frame_gain": (i32, [vp, i32] + [vp] * 5 + [i64, vp, i32]),

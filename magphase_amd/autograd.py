@@ -1,6 +1,6 @@
 """
-Autograd for the lossless features, both directions.  Imported lazily by magphase.py, and only when a device tensor that
-requires grad goes in with return_device=True and grad mode on.
+Autograd for the lossless features, both directions, and for the compressed analysis.  Imported lazily by magphase.py, and
+only when a device tensor that requires grad goes in with return_device=True and grad mode on.
 
 Synthesis: a torch.autograd.Function around the unchanged forward launch of
 synthesis_from_lossless_batch / synthesis_from_lossless_const_rate_batch, with the gradients with respect to
@@ -14,8 +14,17 @@ forward's own output rows (X = mag (real + j imag): nothing else is kept).  Not 
 the clamp region of the forward's 1 / |X|, which holds X == 0 -- the gradient with respect to X is defined as zero: a
 silent frame gives zeros, never Inf or NaN.
 
-No double backward.  The compressed and type-2 synthesis, and the constant-rate, type-2 and compressed analysis, have
-no backward pass.
+Compressed analysis (section 3.3j): a third Function around the unchanged forward launch of analysis_compressed_batch
+(CompressedAnalysisPlan.run(), whichever of its paths it takes), at the variable and the constant rate, with the gradient
+with respect to the samples v_sig computed by CompressedAnalysisPlan.run_backward: the lossless rows are recomputed (only
+the three small output matrices are kept), k_phase_grad_mask and k_mel_warp_bwd take the gradients back through the two
+mel warps -- the phase streams' voicing mask and clip are read from the forward's own outputs, and the gradient at a
+clipped element (exactly +-1.0f) is defined as zero --, k_rows_lerp_adjoint through the constant-rate interpolation, and
+the lossless analysis' backward kernels do the rest.  Not differentiable: v_pm_sec, v_voi and fs; v_lf0_smth and v_shift
+come from the host and carry no grad_fn.
+
+No double backward.  The compressed and type-2 synthesis, and the constant-rate lossless and type-2 analysis, have no
+backward pass.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -103,3 +112,40 @@ def analyze(plan, sigs):
     """plan.run(), differentiable with respect to the v_sig in sigs that are tensors requiring grad.  Returns the three
     float32 [total_frames x H] matrices (with grad_fn)."""
     return _LosslessAnalysis.apply(plan, *sigs)
+
+
+class _CompressedAnalysis(torch.autograd.Function):
+    """forward(plan, *sigs): plan = a CompressedAnalysisPlan built from the utterances whose v_sig are sigs (tensors or
+    host arrays); plan.run() is the forward launch, plan.run_backward(...) the backward ones.  Outputs: the three float32
+    matrices of the batch ([total_out_frames x mag_dim], [.. x phase_dim] twice); the per-utterance results are row views of
+    them.  Only these three are kept for the backward pass."""
+
+    @staticmethod
+    def forward(ctx, plan, *sigs):
+        mag, real, imag = plan.run()
+        ctx.plan = plan
+        ctx.like = [(s.dtype, tuple(s.shape)) if torch.is_tensor(s) else None for s in sigs]
+        ctx.set_materialize_grads(False)     # an output nobody differentiated arrives as None: not read by the kernels
+        ctx.save_for_backward(mag, real, imag)
+        return mag, real, imag
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        outs = ctx.saved_tensors
+        need_in = ctx.needs_input_grad[1:]
+        grads = tuple(g if g is None or (g.dtype == torch.float32 and g.is_contiguous())
+                      else g.to(torch.float32).contiguous() for g in grads)
+        with torch.cuda.device(outs[0].device):
+            gsig = ctx.plan.run_backward(outs, grads)
+        out, a = [], 0
+        for like, need, n in zip(ctx.like, need_in, ctx.plan.lossless.n_smpls):
+            out.append(gsig[a:a + n].to(like[0]).reshape(like[1]) if like is not None and need else None)
+            a += n
+        return (None,) + tuple(out)
+
+
+def analyze_compressed(plan, sigs):
+    """plan.run() of a CompressedAnalysisPlan, differentiable with respect to the v_sig in sigs that are tensors requiring
+    grad.  Returns the three float32 device matrices (with grad_fn)."""
+    return _CompressedAnalysis.apply(plan, *sigs)

@@ -319,6 +319,156 @@ __global__ __launch_bounds__(256) void k_warp_phase_rows(const float* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------
+// Backward pass of the mel warp: grad_x[r][k] = d(x~[r][k]) * sum_{i < nout} g[r][i] W[i][k], the product
+// [rows x nout <= 64] . [nout x H] on v_mfma_f32_16x16x4_f32 -- a short reduction and a wide output: the kernel is made of
+// the rows x H floats it writes (and the rows x H operands it reads for d).  One workgroup = 64 rows: the g tile is staged
+// in LDS once (zeros past nout and past the last row), every wave takes its A fragments of the four 16-row sub-tiles from
+// there into registers and then walks the bins in 16-wide column tiles (wave w: tiles w, w + 4, ...), so the workgroup reads
+// each column of W once.  Oriented C[row][bin]: register r of a lane is row 4 (lane >> 4) + r, bin lane & 15 -- a store
+// instruction writes four rows' 64 contiguous bytes.  The reduction index of instruction e of step q in lane group
+// g = lane >> 4 is i = 16 q + 4 g + e (any order sums the same set): a lane's A fragment of a step is one ds_read_b128.
+// The last column tile (H = 64 q + 1: the Nyquist bin alone) runs like the others on clamped addresses with its stores
+// masked.  d, by the job's mode:
+//   0  magnitudes, x~ = the row itself or fma(x[row1] - x[row0], t, x[row0]) (the forward's arithmetic): d = 2 x~ / (x~^2 + 1e-8)
+//   1  phase streams: d = 2 - 2e-8 e^{-2 x}
+// g of a phase job arrives already masked (k_phase_grad_mask; at the constant rate folded onto the variable-rate rows by
+// k_rows_lerp_adjoint in between).  live: optional per-row flags of a phase job -- a row whose flag is 0 has g == 0 by
+// construction and is written as zeros whatever its operand row holds; a tile without a live row is written as zeros and
+// reads nothing.  Plain vector stores, every output element written exactly once: deterministic.
+// ---------------------------------------------------------------------------------------------
+struct WarpBwdJob {
+    const float* g;      // [rows x nout] upstream gradient (phase jobs: masked)
+    const float* W;      // [nout x H]
+    const float* x;      // operand rows of the forward, pitch ldx
+    float* out;          // [rows x H], pitch ldo
+    const float* live;   // [rows] or null
+    const int* row0;     // row tables of the magnitude job, or null
+    const int* row1;
+    const float* rowt;
+    long long rows;
+    int nout;
+    int mode;
+};
+struct WarpBwdJobs {
+    WarpBwdJob j[3];
+};
+
+constexpr int kBwdGStride = 68;   // floats per LDS row of the g tile (16-byte aligned rows)
+
+template <int MODE>
+__device__ __forceinline__ float warp_bwd_deriv(float x) {
+    if (MODE == 0) return (2.0f * x) / fmaf(x, x, 1.0e-8f);   // 0 at x == 0
+    return fmaf(-2.0e-8f, __expf(-2.0f * x), 2.0f);
+}
+
+template <int MODE, bool INTERP>
+__device__ __forceinline__ void mel_warp_bwd_block(const WarpBwdJob& job, float (*Gs)[kBwdGStride], long long* s_o0,
+                                                   long long* s_o1, float* s_rt, float* s_live, int H, long long ldx,
+                                                   long long ldo) {
+    const long long rows = job.rows;
+    const long long f0 = (long long)blockIdx.x * kWarpTile;
+    if (f0 >= rows) return;   // the jobs of a launch need not have the same row count
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = rfl((int)(tid >> 6));
+    const int li = lane & 15, g = lane >> 4;
+    const int nrows = (int)min((long long)kWarpTile, rows - f0);
+    const int nout = job.nout;
+    if (job.live) {
+        const int pred = (tid < nrows) && (job.live[f0 + min(tid, nrows - 1)] != 0.0f);
+        if (!__syncthreads_or(pred)) {   // no live row: zeros, nothing read
+            for (int r = wave; r < nrows; r += 4) {
+                float* orow = job.out + (f0 + r) * ldo;
+                for (int c = lane; c < H; c += 64) orow[c] = 0.0f;
+            }
+            return;
+        }
+    }
+    if (tid < kWarpTile) {
+        const long long f = f0 + min(tid, nrows - 1);   // rows past the last repeat it: read, never stored
+        s_o0[tid] = (INTERP ? (long long)job.row0[f] : f) * ldx;
+        s_o1[tid] = INTERP ? (long long)job.row1[f] * ldx : 0;
+        s_rt[tid] = INTERP ? job.rowt[f] : 0.0f;
+        s_live[tid] = (tid < nrows && (!job.live || job.live[f] != 0.0f)) ? 1.0f : 0.0f;
+    }
+#pragma unroll
+    for (int p = 0; p < (kWarpTile * 64) / 256; ++p) {
+        const int idx = tid + 256 * p;
+        const int r = idx >> 6, c = idx & 63;
+        Gs[r][c] = (r < nrows && c < nout) ? job.g[(f0 + r) * nout + c] : 0.0f;
+    }
+    __syncthreads();
+    const int nq = (nout + 15) >> 4;   // 16-wide steps of the reduction in use
+    const int nct = (H + 15) >> 4;
+    for (int ct = wave; ct < nct; ct += 4) {
+        const int bin = 16 * ct + li;
+        const int binc = min(bin, H - 1);
+        float b[4][4];   // the column tile's W fragments, shared by the four sub-tiles
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)   // rows past nout meet a zero of g: any finite value of W will do
+                b[q][e] = (q < nq) ? job.W[(long long)min(16 * q + 4 * g + e, nout - 1) * H + binc] : 0.0f;
+#pragma unroll 1   // (unrolled, the compiler keeps every sub-tile's row offsets and addresses in registers and spills)
+        for (int s = 0; s < 4; ++s) {   // rows 16 s .. 16 s + 15
+            float x0[4], x1[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int fl = 16 * s + 4 * g + r;
+                x0[r] = job.x[s_o0[fl] + binc];
+                x1[r] = INTERP ? job.x[s_o1[fl] + binc] : 0.0f;
+            }
+            f32x4 acc = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (q < nq) {   // wave-uniform
+                    const float4 aq = *reinterpret_cast<const float4*>(&Gs[16 * s + li][16 * q + 4 * g]);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(aq.x, b[q][0], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(aq.y, b[q][1], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(aq.z, b[q][2], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(aq.w, b[q][3], acc, 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int fl = 16 * s + 4 * g + r;
+                const float x = INTERP ? fmaf(x1[r] - x0[r], s_rt[fl], x0[r]) : x0[r];
+                const float v = (s_live[fl] != 0.0f) ? warp_bwd_deriv<MODE>(x) * acc[r] : 0.0f;
+                if (fl < nrows && bin < H) job.out[(f0 + fl) * ldo + bin] = v;
+            }
+        }
+    }
+}
+
+// <= 128 VGPRs: four workgroups (19 KB of LDS each) per CU -- the kernel waits on memory, not on its 64 MFMAs per tile
+__attribute__((amdgpu_waves_per_eu(4, 4)))
+__global__ __launch_bounds__(256) void k_mel_warp_bwd(WarpBwdJobs jobs, int H, long long ldx, long long ldo) {
+    __shared__ __attribute__((aligned(16))) float Gs[kWarpTile][kBwdGStride];
+    __shared__ long long s_o0[kWarpTile], s_o1[kWarpTile];
+    __shared__ float s_rt[kWarpTile], s_live[kWarpTile];
+    const WarpBwdJob& job = jobs.j[blockIdx.y];
+    if (job.mode != 0)
+        mel_warp_bwd_block<1, false>(job, Gs, s_o0, s_o1, s_rt, s_live, H, ldx, ldo);
+    else if (job.row0)
+        mel_warp_bwd_block<0, true>(job, Gs, s_o0, s_o1, s_rt, s_live, H, ldx, ldo);
+    else
+        mel_warp_bwd_block<0, false>(job, Gs, s_o0, s_o1, s_rt, s_live, H, ldx, ldo);
+}
+
+// The upstream gradient of the two phase streams through the forward's voicing mask and clip (warp_epilogue, mode 1):
+// h = g where the frame is voiced and the forward's output lies strictly inside (-1, 1), else 0 -- a clipped output is
+// exactly +-1.0f, and the gradient there is defined as zero.  A null g / h pair is skipped.
+__global__ __launch_bounds__(256) void k_phase_grad_mask(long long n_el, int nout, const float* __restrict__ voi,
+                                                         const float* __restrict__ out_r, const float* __restrict__ out_i,
+                                                         const float* __restrict__ g_r, const float* __restrict__ g_i,
+                                                         float* __restrict__ h_r, float* __restrict__ h_i) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n_el) return;
+    const bool voiced = voi[idx / nout] != 0.0f;
+    if (h_r) h_r[idx] = (voiced && fabsf(out_r[idx]) < 1.0f) ? g_r[idx] : 0.0f;
+    if (h_i) h_i[idx] = (voiced && fabsf(out_i[idx]) < 1.0f) ? g_i[idx] : 0.0f;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Mel unwarp on the matrix cores: out[F x H] = op(A[F x K] . U[K x H]) with v_mfma_f32_32x32x2_f32 (f32 in, f32
 // accumulate: bit-for-bit an fmaf chain in k order, so the result equals the VALU form's).  One wave = one task =
 // 32 frames x kUnwarpColTiles column tiles of 32 bins.  Nothing is staged in LDS: A (F x K, a few MB) and U (K x H,
@@ -834,6 +984,63 @@ int mpx_warp_phase_rows(void* stream, int64_t n_frames, int32_t phase_dim, const
     const long long n_el = (long long)n_frames * phase_dim;
     hipLaunchKernelGGL(k_warp_phase_rows, dim3((unsigned)((n_el + 255) / 256)), dim3(256), 0, (hipStream_t)stream, tmp_real,
                        tmp_imag, row0, row1, row_t, voiced, (long long)n_frames, (int)phase_dim, out_real, out_imag);
+    MPX_HIP_CHECK(hipGetLastError());
+    return MPX_OK;
+}
+
+int mpx_mel_warp_backward(void* stream, int32_t n_bins, const float* g_mag, const float* w_mag, int32_t mag_dim,
+                          const float* mag, int64_t n_mag_rows, const int32_t* row0, const int32_t* row1,
+                          const float* row_t, float* grad_mag, const float* h_real, const float* h_imag,
+                          const float* w_phase, int32_t phase_dim, const float* real, const float* imag,
+                          int64_t n_phase_rows, const float* live, float* grad_real, float* grad_imag, int64_t ld,
+                          int64_t ld_grad) {
+    const bool do_mag = grad_mag != nullptr, do_ph = grad_real != nullptr || grad_imag != nullptr;
+    if (n_bins <= 0 || n_mag_rows < 0 || n_phase_rows < 0) return fail(MPX_ERR_ARG, "mpx_mel_warp_backward: bad size%s");
+    if (ld < n_bins || ld_grad < n_bins) return fail(MPX_ERR_ARG, "mpx_mel_warp_backward: row pitch < n_bins%s");
+    if ((do_mag && (mag_dim <= 0 || mag_dim > kWarpTile)) || (do_ph && (phase_dim <= 0 || phase_dim > kWarpTile)))
+        return fail(MPX_ERR_ARG, "mpx_mel_warp_backward: n_out must be in 1..64%s");
+    if ((row0 == nullptr) != (row1 == nullptr) || (row0 == nullptr) != (row_t == nullptr))
+        return fail(MPX_ERR_ARG, "mpx_mel_warp_backward: row0/row1/row_t must be all null or all given%s");
+    const long long max_rows = (long long)kWarpTile * 0x7fffffffLL;
+    if (n_mag_rows > max_rows || n_phase_rows > max_rows) return fail(MPX_ERR_ARG, "mpx_mel_warp_backward: too many rows%s");
+    WarpBwdJobs jobs;
+    int n_jobs = 0;
+    long long max_f = 0;
+    if (do_mag && n_mag_rows > 0) {
+        if (!g_mag || !w_mag || !mag) return fail(MPX_ERR_ARG, "mpx_mel_warp_backward: null pointer (magnitude job)%s");
+        jobs.j[n_jobs++] = {g_mag, w_mag, mag, grad_mag, nullptr, row0, row1, row_t, (long long)n_mag_rows, (int)mag_dim, 0};
+        max_f = (long long)n_mag_rows;
+    }
+    if (do_ph && n_phase_rows > 0) {
+        if (!w_phase || (grad_real && (!h_real || !real)) || (grad_imag && (!h_imag || !imag)))
+            return fail(MPX_ERR_ARG, "mpx_mel_warp_backward: null pointer (phase job)%s");
+        if (grad_real)
+            jobs.j[n_jobs++] = {h_real, w_phase, real, grad_real, live, nullptr, nullptr, nullptr, (long long)n_phase_rows,
+                                (int)phase_dim, 1};
+        if (grad_imag)
+            jobs.j[n_jobs++] = {h_imag, w_phase, imag, grad_imag, live, nullptr, nullptr, nullptr, (long long)n_phase_rows,
+                                (int)phase_dim, 1};
+        max_f = max_f > (long long)n_phase_rows ? max_f : (long long)n_phase_rows;
+    }
+    if (n_jobs == 0) return MPX_OK;   // nothing asked for, or no rows: nothing launched
+    for (int k = n_jobs; k < 3; ++k) jobs.j[k] = jobs.j[0];   // (never indexed: the grid has n_jobs rows)
+    const dim3 grid((unsigned)((max_f + kWarpTile - 1) / kWarpTile), (unsigned)n_jobs);
+    hipLaunchKernelGGL(k_mel_warp_bwd, grid, dim3(256), 0, (hipStream_t)stream, jobs, (int)n_bins, (long long)ld,
+                       (long long)ld_grad);
+    MPX_HIP_CHECK(hipGetLastError());
+    return MPX_OK;
+}
+
+int mpx_phase_grad_mask(void* stream, int64_t n_frames, int32_t phase_dim, const float* voiced, const float* out_real,
+                        const float* out_imag, const float* g_real, const float* g_imag, float* h_real, float* h_imag) {
+    if (n_frames < 0 || phase_dim <= 0) return fail(MPX_ERR_ARG, "mpx_phase_grad_mask: bad size%s");
+    if (n_frames == 0 || (!h_real && !h_imag)) return MPX_OK;
+    if (!voiced || (h_real && (!out_real || !g_real)) || (h_imag && (!out_imag || !g_imag)))
+        return fail(MPX_ERR_ARG, "mpx_phase_grad_mask: null pointer%s");
+    const long long n_el = (long long)n_frames * phase_dim;
+    if ((n_el + 255) / 256 > 0x7fffffffLL) return fail(MPX_ERR_ARG, "mpx_phase_grad_mask: too many elements%s");
+    hipLaunchKernelGGL(k_phase_grad_mask, dim3((unsigned)((n_el + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_el,
+                       (int)phase_dim, voiced, out_real, out_imag, g_real, g_imag, h_real, h_imag);
     MPX_HIP_CHECK(hipGetLastError());
     return MPX_OK;
 }

@@ -1476,6 +1476,70 @@ class Engine:
                     ranges, rowt, int(n_rows), out[0], out[1], out[2], self.feat_ld(first, first, first))
         return out
 
+    def phase_grad_mask(self, out_real, out_imag, voi, g_real, g_imag):
+        """mpx_phase_grad_mask: the upstream gradients g_real / g_imag (contiguous float32 [F x phase_dim], or None) of the
+        compressed analysis' phase streams through its voicing mask and clip, read from the forward's own outputs
+        out_real / out_imag and voi [F] -> (h_real, h_imag), None where g is None."""
+        have = [g for g in (g_real, g_imag) if g is not None]
+        if not have:
+            return (None, None)
+        F, pd = int(out_real.shape[0]), int(out_real.shape[1])
+        for g in have:
+            if g.dtype != _torch().float32 or tuple(g.shape) != (F, pd) or not g.is_contiguous():
+                raise ValueError("phase_grad_mask: gradients must be contiguous float32 [%d x %d]" % (F, pd))
+        h = tuple(self.empty((F, pd)) if g is not None else None for g in (g_real, g_imag))
+        self.launch("mpx_phase_grad_mask", F, pd, voi, out_real, out_imag, g_real, g_imag, h[0], h[1])
+        return h
+
+    def mel_warp_backward(self, n_bins, mag=None, phase=None, out=None):
+        """mpx_mel_warp_backward (k_mel_warp_bwd), its one caller: grad_x = d(x~) * (g . W) for up to three jobs in one launch.
+        mag = (g [rows x mag_dim], w_mag [mag_dim x n_bins], x rows, rows_tables) or None, rows_tables = (row0, row1, rowt)
+        device tables of `rows` entries (x~ interpolated as the forward does) or None (x~ = the rows of x);
+        phase = (h_real, h_imag, w_phase [phase_dim x n_bins], x_real, x_imag, live) or None: h already masked
+        (phase_grad_mask), either may be None, live = float32 [rows] flags or None.
+        g / h: contiguous float32; x: feature rows of one pitch (unit column stride).  out: (grad_mag, grad_real, grad_imag)
+        to write into (None where a job does not run; rows of one pitch), allocated when not given.
+        Returns (grad_mag, grad_real, grad_imag), [rows x n_bins] each, None for a job that did not run."""
+        torch = _torch()
+        H = int(n_bins)
+
+        def dense(g, n_out, what):
+            if g.dtype != torch.float32 or g.dim() != 2 or int(g.shape[1]) != n_out or not g.is_contiguous():
+                raise ValueError("mel_warp_backward: %s must be a contiguous float32 [rows x %d]" % (what, n_out))
+            return int(g.shape[0])
+
+        args_m = [None, None, 0, None, 0, None, None, None]
+        args_p = [None, None, None, 0, None, None, 0, None]
+        rows_m = rows_p = 0
+        xs = []
+        if mag is not None:
+            g, w, x, tabs = mag
+            rows_m = dense(g, int(w.shape[0]), "g_mag")
+            r0, r1, rt = tabs if tabs is not None else (None, None, None)
+            args_m = [g, w, int(w.shape[0]), x, rows_m, r0, r1, rt]
+            xs.append(x)
+        want_r = want_i = False
+        if phase is not None:
+            hr, hi, w, xr, xi, live = phase
+            for h in (hr, hi):
+                if h is not None:
+                    rows_p = dense(h, int(w.shape[0]), "h_real / h_imag")
+            want_r, want_i = hr is not None, hi is not None
+            args_p = [hr, hi, w, int(w.shape[0]), xr if want_r else None, xi if want_i else None, rows_p, live]
+            xs += [x for x, k in ((xr, want_r), (xi, want_i)) if k]
+        want = (mag is not None, want_r, want_i)
+        if out is None:
+            out = tuple(self.empty_feats(rows_m if k == 0 else rows_p, H) if w_ else None for k, w_ in enumerate(want))
+        if not xs:
+            return out
+        outs = [o for o in out if o is not None]
+        for t in xs + outs:
+            if int(t.shape[1]) != H:
+                raise ValueError("mel_warp_backward: rows must have %d bins" % H)
+        self.launch("mpx_mel_warp_backward", H, *args_m, out[0], *args_p, out[1], out[2],
+                    self.feat_ld(*(xs * 3)[:3]), self.feat_ld(*(outs * 3)[:3]))
+        return out
+
     def roundtrip_lossless_ola(self, fft_len, plan_a, plan_s, feats, strips, pcm_out, full_support=False):
         """Copy synthesis in one launch (mpx_roundtrip_lossless_ola_flags): plan_a's frames are analysed, their feature rows
         written to feats = (mag, real, imag) and overlap-added by plan_s' runs (a LosslessSynthesisPlan built for this

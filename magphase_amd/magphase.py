@@ -890,6 +890,14 @@ def analysis_compressed_batch(utts, fft_len=None, mag_dim=60, phase_dim=10, b_co
     as_float32 downloads), for a training loop that extracts features on the fly; v_lf0_smth, v_shift, fs and fft_len are
     host values as always.  Not with async_out.  The launches go to torch's CURRENT stream of the engine's device: work
     that consumes the matrices on that stream needs no further synchronisation.
+    v_sig may be a 1-D torch tensor on the engine's device (float32 / float16 / bfloat16 / float64, any element stride), as
+    for analysis_lossless_batch: the samples stay on the device, and the rows equal those of the host-array call on the
+    same float32 samples bit for bit.  Not with prepared= (built from host arrays).
+    Autograd: with return_device, grad mode on and a device v_sig that requires grad, m_mag_mel_log / m_real_mel /
+    m_imag_mel carry a grad_fn and tensor.backward() reaches v_sig, at both frame rates (magphase_amd/autograd.py,
+    DESIGN.md section 3.3j; the forward launch and its values are the same).  The gradient of a phase coefficient that
+    sits on the clip at +-1 is defined as zero.  Not differentiable: v_pm_sec, v_voi and fs; v_lf0_smth and v_shift carry
+    no grad_fn; no double backward.
     """
     if return_device and async_out:
         raise ValueError("return_device and async_out exclude each other (async_out is a download)")
@@ -910,7 +918,7 @@ def analysis_compressed_batch(utts, fft_len=None, mag_dim=60, phase_dim=10, b_co
             raise ValueError("async_out needs as_float32")
         (h_mag, h_real, h_imag), ticket = engine.to_host_f32_async(list(plan.run()))
     elif return_device:
-        h_mag, h_real, h_imag = plan.run()
+        h_mag, h_real, h_imag = _run_compressed_analysis(plan, utts)
     else:
         h_mag, h_real, h_imag = ((engine.to_host_f32 if as_float32 else engine.to_host_f64)(t_) for t_ in plan.run())
     res = []
@@ -939,6 +947,21 @@ def analysis_compressed_batch(utts, fft_len=None, mag_dim=60, phase_dim=10, b_co
             ticket.release()
         raise
     return (res, ticket) if async_out else res
+
+
+def _run_compressed_analysis(plan, utts):
+    """plan.run() -> the batch's three float32 device matrices, for return_device.  Through autograd.analyze_compressed --
+    the same launch inside a torch.autograd.Function -- when grad mode is on and some v_sig is a device tensor that requires
+    grad (a CPU tensor is a host array to the plan; a prepared= batch was built from host arrays)."""
+    import sys
+
+    torch = sys.modules.get("torch")
+    if (torch is not None and torch.is_grad_enabled()
+            and any(torch.is_tensor(u[0]) and u[0].requires_grad and u[0].device.type != "cpu" for u in utts)):
+        from .autograd import analyze_compressed
+
+        return analyze_compressed(plan, [u[0] for u in utts])
+    return plan.run()
 
 
 def format_for_modelling(m_mag, m_real, m_imag, v_f0, fs, mag_dim=60, phase_dim=45, b_mag_fbank_mel=False,

@@ -1381,6 +1381,7 @@ class CompressedAnalysisPlan:
             row0, row1, rowt, self.f0_out, self.out_off = hm.var_to_const_rate_batch(
                 [plan.v_shift[u] for u in range(U)], [plan.v_f0[u] for u in range(U)], plan.frame_off[:U], fs, 5.0)
             rows = (row0, row1, rowt)
+            self._rows_host = rows   # (run_backward builds the adjoint's frame ranges from them)
         else:   # variable rate: output rows == frames (no row tables go to the device)
             self.f0_out = plan.v_f0 if isinstance(plan.v_f0, _FlatRows) else list(plan.v_f0)
             self.out_off = np.asarray(plan.frame_off, dtype=np.int64)
@@ -1496,6 +1497,59 @@ class CompressedAnalysisPlan:
             e.launch(self._warp_name, *warp)
         mark("k_mel_warp_mfma")
         return out
+
+    def run_backward(self, outs, grads, mark=None):
+        """The gradient of a loss with respect to the batch's samples, float32 [total_smpls] (utterance u at the offset of
+        its samples in self.lossless.sig), given outs = run()'s three matrices and grads = (dL/d m_mag_mel_log,
+        dL/d m_real_mel, dL/d m_imag_mel): contiguous float32 matrices of their shapes, or None for an output nobody
+        differentiated (not read, contributes zero).  DESIGN.md section 3.3j.
+        The lossless rows are RECOMPUTED (the fused forward never wrote them, and nothing of size F x H is kept between the
+        passes): self.lossless.run with the forward's precision and rows_in_use=None -- every row is written, also the phase
+        rows the constant-rate forward leaves out: the lossless backward multiplies real / imag into its result even where
+        the gradient is zero.  Then k_phase_grad_mask (the forward's voicing mask and clip, read from outs), at the
+        constant rate k_rows_lerp_adjoint at width phase_dim, k_mel_warp_bwd (the three jobs in one launch), at the
+        constant rate k_rows_lerp_adjoint on the magnitude gradients, and LosslessAnalysisPlan.run_backward."""
+        if self._warp_name == "mpx_mel_warp_fbank":
+            raise NotImplementedError("the filter-bank magnitudes (b_mag_fbank_mel) have no backward pass")
+        torch = _torch()
+        e, pl, N = self.engine, self.lossless, int(self.fft_len)
+        H = N // 2 + 1
+        Fo, n_var, total = self.total_out_frames, int(pl.total_frames), int(pl.total_smpls)
+        mark = mark or (lambda name: None)
+        mark("start")
+        shapes = ((Fo, self.mag_dim), (Fo, self.phase_dim), (Fo, self.phase_dim))
+        for g, shp in zip(grads, shapes):
+            if g is not None and (g.dtype != torch.float32 or tuple(g.shape) != shp or not g.is_contiguous()):
+                raise ValueError("run_backward: gradients must be contiguous float32 of the outputs' shapes")
+        g_m, g_r, g_i = grads
+        if Fo == 0 or n_var == 0 or total == 0 or all(g is None for g in grads):
+            return torch.zeros((total,), dtype=torch.float32, device=e.device)
+        precise = os.environ.get("MAGPHASE_COMP_ANALYSIS", "f64") != "f32"
+        rows = pl.run(precise=precise, rows_in_use=None)
+        mark("rows")
+        h_r, h_i = e.phase_grad_mask(outs[1], outs[2], self.voi, g_r, g_i)
+        tabs = live = None
+        if self.b_const_rate:
+            if getattr(self, "_adj", None) is None:
+                r0, r1, rt = self._rows_host
+                self._adj = e.to_device(hm.lerp_adjoint_table(r0, r1, rt, n_var).reshape(-1), np.int32)
+            tabs = (self.row0, self.row1, self.rowt)
+            # the masked phase gradients onto the variable-rate rows the forward interpolated from (width phase_dim)
+            _none, h_r, h_i = e.rows_lerp_adjoint((None, h_r, h_i), self._adj, self.rowt, n_var)
+            live = self.rows_in_use   # (None under MAGPHASE_WARP_PHASE_ROWS=0: no tile is skipped)
+        else:
+            live = self.voi
+        mark("k_phase_grad_mask")
+        have_ph = h_r is not None or h_i is not None
+        g_rows = e.mel_warp_backward(H, mag=(g_m, self.w_mag, rows[0], tabs) if g_m is not None else None,
+                                     phase=(h_r, h_i, self.w_ph, rows[1], rows[2], live) if have_ph else None)
+        mark("k_mel_warp_bwd")
+        if self.b_const_rate and g_rows[0] is not None:
+            g_rows = (e.rows_lerp_adjoint((g_rows[0], None, None), self._adj, self.rowt, n_var)[0],) + tuple(g_rows[1:])
+            mark("k_rows_lerp_adjoint")
+        gsig = pl.run_backward(rows[0], rows[1], rows[2], g_rows)
+        mark("k_analysis_lossless_bwd")
+        return gsig
 
 
 class Type2AnalysisPlan:
