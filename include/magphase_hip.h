@@ -269,6 +269,35 @@ int mpx_synthesis_lossless_backward(void* stream, int fft_len, const void* table
                                     int64_t ld_grad);
 
 /*
+ * Backward pass of mpx_synthesis_compressed_ola (synthesis_from_compressed, magphase.py:825-997; per_phase_type
+ * 'magphase', no post-filter): from grad_out = dL/d pcm_out BEFORE the output high-pass (float32 [total_out]) the gradients
+ * with respect to the frames' unwarped rows mag / real / imag (row pitch ld, one row per FRAME: what mpx_mel_unwarp_rows
+ * wrote).  grad_pos / grad_lo / grad_hi: as for mpx_synthesis_lossless_backward (hostmath.lossless_backward_table; reads are
+ * also clamped to [0, total_out) on the device).  noise .. noise_wtype, voiced, inv_gain, win_left / win_right, per_v / ap_v /
+ * ap_u and n_per are the forward's own arguments.  Per frame f and bin k, with N = fft_len:
+ *     Ns  = FFT_N of the frame's windowed, rotated noise (recomputed; not bit-identical to the forward's compact form),
+ *     u   = (real + j imag) / den, den = |real + j imag| (u = 0 where that is 0),
+ *     T   = P u + A inv_gain[f] Ns,  P = per_v (voiced, k < n_per) / 0,  A = ap_v (voiced) / ap_u,
+ *     gS  = (c_k / N) FFT_N(ifftshift(w_f g))_k, w_f the anti-ringing window (win_left, win_right), g the gradient samples
+ *           under the frame, c_k = 2 and 1 at bins 0 and N/2, where gS <- Re(gS) S / |S| with S = mag T (0 where S == 0),
+ *     grad_mag = Re(conj(T) gS),   grad_real + j grad_imag = (mag P / den) (gS - u Re(conj(u) gS))   (den == 0: mag P gS).
+ * grad_mag is written over all fft_len/2 + 1 bins of row f (pitch ld_grad); grad_real / grad_imag over the first
+ * min(64 ceil(n_per / 64), fft_len/2 + 1) bins -- zeros in unvoiced frames and from n_per on -- and nowhere else.  The phase
+ * rows of unvoiced frames and the bins from n_per on are not read (the forward does not produce them).  A null grad_X is not
+ * computed; all three null launches nothing.  Every element named above of a non-null grad_X is written exactly once: no
+ * atomics, deterministic.  Arguments are checked before the device is touched.
+ */
+int mpx_synthesis_compressed_backward(void* stream, int fft_len, const void* tables, const float* grad_out,
+                                      int64_t total_out, const int64_t* grad_pos, const int32_t* grad_lo,
+                                      const int32_t* grad_hi, int64_t n_frames, const float* mag, const float* real,
+                                      const float* imag, int64_t ld, const float* noise, const int64_t* noise_pos,
+                                      const int32_t* noise_left, const int32_t* noise_right, const int32_t* noise_wtype,
+                                      const int32_t* voiced, const float* inv_gain, const int32_t* win_left,
+                                      const int32_t* win_right, const float* per_v, const float* ap_v, const float* ap_u,
+                                      int32_t n_per, float* grad_mag, float* grad_real, float* grad_imag,
+                                      int64_t ld_grad);
+
+/*
  * Adjoint of the row interpolation out[f] = fma(x[row1[f]] - x[row0[f]], row_t[f], x[row0[f]]):
  *     dst_X[r] = sum over f with row0[f] == r of (1 - row_t[f]) src_X[f] + sum over f with row1[f] == r of row_t[f] src_X[f]
  * for r < n_rows (a frame with row0 == row1 == r weighs exactly 1).  ranges: int32 [n_rows x 4] = (a0, a1, b0, b1) per
@@ -653,6 +682,27 @@ int mpx_mel_warp_backward(void* stream, int32_t n_bins, const float* g_mag, cons
                           const float* w_phase, int32_t phase_dim, const float* real, const float* imag,
                           int64_t n_phase_rows, const float* live, float* grad_real, float* grad_imag, int64_t ld,
                           int64_t ld_grad);
+
+/*
+ * Backward of mpx_mel_unwarp / mpx_mel_unwarp_rows (la.sp_mel_unwarp, libaudio.py:663-690; the compressed synthesis): the
+ * gradients with respect to the coefficient rows, up to three products [rows x K] . [K x n_out] in one launch (float32
+ * matrix instructions, float32 accumulation).
+ *   magnitude job: grad_a_mag[r][c] = sum_{k < n_bins} u_mag[c][k] e_mag[r][k] g_mag[r][k] -- e_mag = exp(a_mag . u_mag),
+ *                  the forward's unwarped magnitudes at the ROWS' rate (row pitch ld_e), g_mag the gradient with respect
+ *                  to them (pitch ld_g), u_mag [mag_dim x n_bins] the forward's matrix; grad_a_mag [n_mag_rows x mag_dim].
+ *   phase jobs:    grad_a_real[r][c] = sum_{k < n_phase_bins} u_phase[c][k] g_real[r][k] (imag alike): g_real / g_imag
+ *                  [n_phase_rows x n_phase_bins] at pitch ld_phase, u_phase [phase_dim x n_bins]; outputs
+ *                  [n_phase_rows x phase_dim].
+ * Nothing beyond the named columns of an operand row is read.  A job whose output is null is skipped (its other pointers are
+ * not looked at); a job with zero rows launches nothing.  n_out (mag_dim / phase_dim of a job that runs) must be in 1..64.
+ * Every element of a non-null output is written exactly once: no atomics, deterministic.  Arguments are checked before the
+ * device is touched.
+ */
+int mpx_mel_unwarp_backward(void* stream, int32_t n_bins, const float* e_mag, int64_t ld_e, const float* g_mag,
+                            int64_t ld_g, const float* u_mag, int32_t mag_dim, int64_t n_mag_rows, float* grad_a_mag,
+                            const float* g_real, const float* g_imag, int64_t ld_phase, int32_t n_phase_bins,
+                            const float* u_phase, int32_t phase_dim, int64_t n_phase_rows, float* grad_a_real,
+                            float* grad_a_imag);
 
 /*
  * The upstream gradients of the two phase streams through the voicing mask and clip of mpx_mel_warp's epilogue

@@ -44,6 +44,8 @@ PROTOTYPES = {
     "mpx_synthesis_lossless_ola_lerp": (i32, [vp, i32] + [vp] * 8 + [i32, vp, vp, i32, vp, vp, vp, i64]),
     "mpx_rows_lerp": (i32, [vp, i32, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64]),
     "mpx_synthesis_lossless_backward": (i32, [vp, i32, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64] + [vp] * 6 + [i64]),
+    "mpx_synthesis_compressed_backward": (i32, [vp, i32, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64] + [vp] * 12
+                                          + [i32, vp, vp, vp, i64]),
     "mpx_rows_lerp_adjoint": (i32, [vp, i32, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, i64]),
     "mpx_analysis_lossless_backward": (i32, [vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, i64,
                                              vp, i64]),
@@ -97,6 +99,7 @@ PROTOTYPES = {
     "mpx_mel_warp_rows": (i32, [vp, i64, i32] + [vp] * 7 + [i32, vp, i32] + [vp] * 4 + [i64, i32, i64, vp, vp, vp]),
     "mpx_warp_phase_rows": (i32, [vp, i64, i32] + [vp] * 8),
     "mpx_mel_warp_backward": (i32, [vp, i32, vp, vp, i32, vp, i64] + [vp] * 7 + [i32, vp, vp, i64, vp, vp, vp, i64, i64]),
+    "mpx_mel_unwarp_backward": (i32, [vp, i32, vp, i64, vp, i64, vp, i32, i64, vp, vp, vp, i64, i32, vp, i32, i64, vp, vp]),
     "mpx_phase_grad_mask": (i32, [vp, i64, i32] + [vp] * 7),
     "mpx_min_phase": (i32, [vp, i32] + [vp] * 5 + [i64, vp, vp, vp, i64]),
     "mpx_true_envelope": (i32, [vp, i32, vp, vp, vp, i64, i64, i32, f64, i32, vp, i64, vp, vp, vp]),

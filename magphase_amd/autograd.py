@@ -1,6 +1,6 @@
 """
-Autograd for the lossless features, both directions, and for the compressed analysis.  Imported lazily by magphase.py, and
-only when a device tensor that requires grad goes in with return_device=True and grad mode on.
+Autograd for the lossless features, both directions, and for the compressed features, both directions.  Imported lazily by
+magphase.py, and only when a device tensor that requires grad goes in with return_device=True and grad mode on.
 
 Synthesis: a torch.autograd.Function around the unchanged forward launch of
 synthesis_from_lossless_batch / synthesis_from_lossless_const_rate_batch, with the gradients with respect to
@@ -23,8 +23,20 @@ clipped element (exactly +-1.0f) is defined as zero --, k_rows_lerp_adjoint thro
 the lossless analysis' backward kernels do the rest.  Not differentiable: v_pm_sec, v_voi and fs; v_lf0_smth and v_shift
 come from the host and carry no grad_fn.
 
-No double backward.  The compressed and type-2 synthesis, and the constant-rate lossless and type-2 analysis, have no
-backward pass.
+Compressed synthesis (section 3.3k): a fourth Function around the unchanged forward of synthesis_from_compressed_batch
+(the plan's packing of the coefficient rows, CompressedSynthesisPlan.run() and the output high-pass), type 1 with
+per_phase_type='magphase' and no post-filter, at the variable and the constant rate, with the gradients with respect to
+m_mag_mel_log / m_real_mel / m_imag_mel computed by CompressedSynthesisPlan.run_backward: the high-pass' adjoint (the same
+filter run backwards in time, per utterance), k_synth_comp_bwd (per frame: the noise spectrum recomputed, the gradient
+window through the anti-ringing window and one FFT, the epilogue against the forward's own unwarped rows),
+k_rows_lerp_adjoint through the constant-rate interpolation and k_mel_unwarp_bwd through the two mel unwarps.  Not
+differentiable: v_lf0 (it only produces integer pitch marks and the voicing flag), fs, and the noise with its two gains
+(they do not depend on the features).  Bins 0 and N/2 keep |S|: where S == 0 there the gradient is defined as zero; where
+a phase bin is a == b == 0 its gradient is m P gS (k_synth_lossless_bwd's convention).  A plan that stores its noise
+spectra (MAGPHASE_NOISE_SPECTRA=store) is differentiated the same way: the backward pass recomputes them.
+
+No double backward.  The type-2 synthesis, the compressed synthesis with per_phase_type 'min_phase' / 'linear', with a
+post-filter, with pcm16_norm or with prepared=, and the constant-rate lossless and type-2 analysis, have no backward pass.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -149,3 +161,53 @@ def analyze_compressed(plan, sigs):
     """plan.run() of a CompressedAnalysisPlan, differentiable with respect to the v_sig in sigs that are tensors requiring
     grad.  Returns the three float32 device matrices (with grad_fn)."""
     return _CompressedAnalysis.apply(plan, *sigs)
+
+
+class _CompressedSynthesis(torch.autograd.Function):
+    """forward(plan, b_out_hpf, n_utts, *mats): plan = a CompressedSynthesisPlan built from the utterances whose
+    coefficient matrices are mats, utterance-major (m_mag_mel_log_0, m_real_mel_0, m_imag_mel_0, m_mag_mel_log_1, ...:
+    tensors or host arrays; the plan holds them packed as float32 device rows already); plan.run() and Engine.output_hpf
+    are the forward, plan.adjoint_hpf and plan.run_backward the backward.  Output: the ONE [total_out] waveform buffer
+    (float64 after the high-pass, float32 without it); the per-utterance signals are views of it."""
+
+    @staticmethod
+    def forward(ctx, plan, b_out_hpf, n_utts, *mats):
+        pcm = plan.run()
+        if b_out_hpf:
+            pcm = plan.engine.output_hpf(pcm, plan.out_off_host, plan.fs)
+        ctx.plan, ctx.hpf = plan, bool(b_out_hpf)
+        ctx.rows = [int(mats[3 * u].shape[0]) for u in range(n_utts)]
+        ctx.like = [(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else None for m in mats]
+        return pcm
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        plan = ctx.plan
+        n_head = 3   # plan, b_out_hpf, n_utts
+        need_in = ctx.needs_input_grad[n_head:]
+        need = tuple(any(need_in[k::3]) for k in range(3))
+        with torch.cuda.device(grad_out.device):
+            if ctx.hpf:
+                g = plan.adjoint_hpf(grad_out)
+            else:
+                g = grad_out.to(torch.float32)
+            g = plan.run_backward(g.contiguous(), need=need)
+        out, a = [], 0
+        for u, n in enumerate(ctx.rows):
+            for k in range(3):
+                like = ctx.like[3 * u + k]
+                if like is None or not need_in[3 * u + k]:
+                    out.append(None)
+                else:
+                    out.append(g[k][a:a + n].to(like[0]).reshape(like[1]))
+            a += n
+        return (None,) * n_head + tuple(out)
+
+
+def synthesize_compressed(plan, b_out_hpf, utts):
+    """plan.run() of a CompressedSynthesisPlan (and the output high-pass), differentiable with respect to the coefficient
+    matrices in utts = [(m_mag_mel_log, m_real_mel, m_imag_mel, v_lf0)] that are tensors requiring grad.  Returns the
+    [total_out] waveform buffer (with grad_fn)."""
+    mats = [x for u in utts for x in u[:3]]
+    return _CompressedSynthesis.apply(plan, bool(b_out_hpf), len(utts), *mats)

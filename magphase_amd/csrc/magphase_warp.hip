@@ -1,6 +1,7 @@
 // magphase_warp.hip -- the mel warp / unwarp GEMMs of the compressed features on the f32 matrix instructions.
 //
 //   k_mel_warp_mfma, k_warp_phase_rows     mel warp of the compressed analysis as a GEMM on the f32 matrix instructions
+//   k_mel_unwarp_bwd                       backward of the mel unwarp (compressed synthesis): [rows x K] x [K x n_out]
 //   k_mel_unwarp_mfma / _tiled             [F x K] x [K x H] -> exp / identity: la.sp_mel_unwarp and
 //                                          phase_uncompress_type1_mcep as the linear maps they are, K <= 64
 #include "mpx_common.hpp"
@@ -466,6 +467,114 @@ __global__ __launch_bounds__(256) void k_phase_grad_mask(long long n_el, int nou
     const bool voiced = voi[idx / nout] != 0.0f;
     if (h_r) h_r[idx] = (voiced && fabsf(out_r[idx]) < 1.0f) ? g_r[idx] : 0.0f;
     if (h_i) h_i[idx] = (voiced && fabsf(out_i[idx]) < 1.0f) ? g_i[idx] : 0.0f;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Backward of the mel unwarp (compressed synthesis): out[rows x nout] = A[rows x K] . W^T, W the
+// forward's unwarp matrix as it lies ([nout x K'], pitch ldw, K <= K'), nout <= 64, on v_mfma_f32_16x16x4_f32 in the
+// shape of k_mel_warp_mfma above: one workgroup = 64 rows x up to 64 outputs, the reduction in chunks of 64 staged into
+// LDS as [row][k], wave w owns rows 16 w .. 16 w + 15 and every 16-wide column tile, lane group g takes
+// k = 16 g + 4 q + {0..3} of step q (one 16-byte fragment read per step), a fresh accumulator per chunk and the chunk
+// sums added up separately.  Up to three jobs per launch (blockIdx.y):
+//   magnitude job: A = E * gE elementwise, formed while staging (E = exp(U^T a), the forward's unwarped magnitudes at the
+//                  rows' rate; gE the gradient with respect to them), K = H;
+//   phase jobs:    A = grad a / grad b as k_synth_comp_bwd wrote them, K = the phase bins written.
+// Rows past the last, outputs past nout and bins past K are staged as zeros (nothing outside the matrices is read: the
+// operands carry row padding that nobody initialised).  Plain stores, one writer per element.
+// ---------------------------------------------------------------------------------------------
+struct UnwarpBwdJob {
+    const float* x;      // [rows x K], pitch ldx
+    const float* y;      // second factor of the operand, pitch ldy, or null
+    const float* W;      // [nout x K], pitch ldw
+    float* out;          // [rows x nout], dense
+    long long ldx, ldy, ldw;
+    long long rows;
+    int K;
+    int nout;
+};
+struct UnwarpBwdJobs {
+    UnwarpBwdJob j[3];
+};
+
+template <int NT>
+__device__ __forceinline__ void mel_unwarp_bwd_block(const UnwarpBwdJob& job, float (*As)[kWarpStride],
+                                                     float (*Ws)[kWarpStride]) {
+    const long long f0 = (long long)blockIdx.x * kWarpTile;
+    if (f0 >= job.rows) return;   // the jobs of a launch need not have the same row count
+    const int kk = threadIdx.x & 63, fq = threadIdx.x >> 6;   // staging roles: bin within the chunk, row quarter
+    const int wave = rfl((int)(threadIdx.x >> 6));
+    const int li = kk & 15, g = kk >> 4;                      // fragment roles
+    const int K = job.K, nout = job.nout;
+    f32x4 tot[NT];
+#pragma unroll
+    for (int jt = 0; jt < NT; ++jt) tot[jt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int k0 = 0; k0 < K; k0 += 64) {
+        const int k = k0 + kk;
+        const bool kin = k < K;
+        float av[16], wv[4 * NT];
+#pragma unroll
+        for (int p = 0; p < 16; ++p) {   // rows fq + 4 p: a wave's 64 lanes read 64 consecutive bins of one row
+            const long long f = f0 + fq + 4 * p;
+            const bool in = kin && f < job.rows;
+            float v = in ? job.x[f * job.ldx + k] : 0.0f;
+            if (job.y) v *= in ? job.y[f * job.ldy + k] : 0.0f;
+            av[p] = v;
+        }
+#pragma unroll
+        for (int p = 0; p < 4 * NT; ++p) {
+            const int i = fq + 4 * p;
+            wv[p] = (kin && i < nout) ? job.W[(long long)i * job.ldw + k] : 0.0f;
+        }
+#pragma unroll
+        for (int p = 0; p < 16; ++p) As[fq + 4 * p][kk] = av[p];
+#pragma unroll
+        for (int p = 0; p < 4 * NT; ++p) Ws[fq + 4 * p][kk] = wv[p];
+        __syncthreads();
+        f32x4 acc[NT];
+#pragma unroll
+        for (int jt = 0; jt < NT; ++jt) acc[jt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int col = 16 * g + 4 * q;
+            const float4 aq = *reinterpret_cast<const float4*>(&As[16 * wave + li][col]);
+            float4 bq[NT];
+#pragma unroll
+            for (int jt = 0; jt < NT; ++jt) bq[jt] = *reinterpret_cast<const float4*>(&Ws[16 * jt + li][col]);
+#pragma unroll
+            for (int jt = 0; jt < NT; ++jt) acc[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(aq.x, bq[jt].x, acc[jt], 0, 0, 0);
+#pragma unroll
+            for (int jt = 0; jt < NT; ++jt) acc[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(aq.y, bq[jt].y, acc[jt], 0, 0, 0);
+#pragma unroll
+            for (int jt = 0; jt < NT; ++jt) acc[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(aq.z, bq[jt].z, acc[jt], 0, 0, 0);
+#pragma unroll
+            for (int jt = 0; jt < NT; ++jt) acc[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(aq.w, bq[jt].w, acc[jt], 0, 0, 0);
+        }
+#pragma unroll
+        for (int jt = 0; jt < NT; ++jt) tot[jt] += acc[jt];
+        __syncthreads();
+    }
+    // C: column li of tile jt, row 4 g + r of this wave's 16 rows
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const long long f = f0 + 16 * wave + 4 * g + r;
+        if (f >= job.rows) continue;
+#pragma unroll
+        for (int jt = 0; jt < NT; ++jt) {
+            const int i = 16 * jt + li;
+            if (i < nout) job.out[f * nout + i] = tot[jt][r];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mel_unwarp_bwd(UnwarpBwdJobs jobs) {
+    __shared__ __attribute__((aligned(16))) float As[kWarpTile][kWarpStride];   // As[row][k]
+    __shared__ __attribute__((aligned(16))) float Ws[kWarpTile][kWarpStride];   // Ws[i][k]
+    const UnwarpBwdJob& job = jobs.j[blockIdx.y];
+    const int nt = (job.nout + 15) >> 4;   // wave-uniform (a kernel argument)
+    if (nt == 1) mel_unwarp_bwd_block<1>(job, As, Ws);
+    else if (nt == 2) mel_unwarp_bwd_block<2>(job, As, Ws);
+    else if (nt == 3) mel_unwarp_bwd_block<3>(job, As, Ws);
+    else mel_unwarp_bwd_block<4>(job, As, Ws);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1041,6 +1150,48 @@ int mpx_phase_grad_mask(void* stream, int64_t n_frames, int32_t phase_dim, const
     if ((n_el + 255) / 256 > 0x7fffffffLL) return fail(MPX_ERR_ARG, "mpx_phase_grad_mask: too many elements%s");
     hipLaunchKernelGGL(k_phase_grad_mask, dim3((unsigned)((n_el + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_el,
                        (int)phase_dim, voiced, out_real, out_imag, g_real, g_imag, h_real, h_imag);
+    MPX_HIP_CHECK(hipGetLastError());
+    return MPX_OK;
+}
+
+int mpx_mel_unwarp_backward(void* stream, int32_t n_bins, const float* e_mag, int64_t ld_e, const float* g_mag,
+                            int64_t ld_g, const float* u_mag, int32_t mag_dim, int64_t n_mag_rows, float* grad_a_mag,
+                            const float* g_real, const float* g_imag, int64_t ld_phase, int32_t n_phase_bins,
+                            const float* u_phase, int32_t phase_dim, int64_t n_phase_rows, float* grad_a_real,
+                            float* grad_a_imag) {
+    const bool do_mag = grad_a_mag != nullptr, do_ph = grad_a_real != nullptr || grad_a_imag != nullptr;
+    if (n_bins <= 0 || n_mag_rows < 0 || n_phase_rows < 0) return fail(MPX_ERR_ARG, "mpx_mel_unwarp_backward: bad size%s");
+    if (do_mag && (ld_e < n_bins || ld_g < n_bins)) return fail(MPX_ERR_ARG, "mpx_mel_unwarp_backward: row pitch < n_bins%s");
+    if (do_ph && (n_phase_bins < 0 || n_phase_bins > n_bins || ld_phase < n_phase_bins))
+        return fail(MPX_ERR_ARG, "mpx_mel_unwarp_backward: n_phase_bins outside [0, n_bins] or above the row pitch%s");
+    if ((do_mag && (mag_dim <= 0 || mag_dim > kWarpTile)) || (do_ph && (phase_dim <= 0 || phase_dim > kWarpTile)))
+        return fail(MPX_ERR_ARG, "mpx_mel_unwarp_backward: n_out must be in 1..64%s");
+    const long long max_rows = (long long)kWarpTile * 0x7fffffffLL;
+    if (n_mag_rows > max_rows || n_phase_rows > max_rows) return fail(MPX_ERR_ARG, "mpx_mel_unwarp_backward: too many rows%s");
+    UnwarpBwdJobs jobs;
+    int n_jobs = 0;
+    long long max_f = 0;
+    if (do_mag && n_mag_rows > 0) {
+        if (!e_mag || !g_mag || !u_mag) return fail(MPX_ERR_ARG, "mpx_mel_unwarp_backward: null pointer (magnitude job)%s");
+        jobs.j[n_jobs++] = {e_mag, g_mag, u_mag, grad_a_mag, (long long)ld_e, (long long)ld_g, (long long)n_bins,
+                            (long long)n_mag_rows, (int)n_bins, (int)mag_dim};
+        max_f = (long long)n_mag_rows;
+    }
+    if (do_ph && n_phase_rows > 0) {
+        if (!u_phase || (grad_a_real && !g_real) || (grad_a_imag && !g_imag))
+            return fail(MPX_ERR_ARG, "mpx_mel_unwarp_backward: null pointer (phase job)%s");
+        if (grad_a_real)
+            jobs.j[n_jobs++] = {g_real, nullptr, u_phase, grad_a_real, (long long)ld_phase, 0, (long long)n_bins,
+                                (long long)n_phase_rows, (int)n_phase_bins, (int)phase_dim};
+        if (grad_a_imag)
+            jobs.j[n_jobs++] = {g_imag, nullptr, u_phase, grad_a_imag, (long long)ld_phase, 0, (long long)n_bins,
+                                (long long)n_phase_rows, (int)n_phase_bins, (int)phase_dim};
+        max_f = max_f > (long long)n_phase_rows ? max_f : (long long)n_phase_rows;
+    }
+    if (n_jobs == 0) return MPX_OK;   // nothing asked for, or no rows: nothing launched
+    for (int k = n_jobs; k < 3; ++k) jobs.j[k] = jobs.j[0];   // (never indexed: the grid has n_jobs rows)
+    const dim3 grid((unsigned)((max_f + kWarpTile - 1) / kWarpTile), (unsigned)n_jobs);
+    hipLaunchKernelGGL(k_mel_unwarp_bwd, grid, dim3(256), 0, (hipStream_t)stream, jobs);
     MPX_HIP_CHECK(hipGetLastError());
     return MPX_OK;
 }

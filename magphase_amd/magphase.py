@@ -775,6 +775,16 @@ def _output_hpf(v_syn_sig, fs):
     return signal.lfilter(v_b, v_a, v_syn_sig)
 
 
+def _compressed_synthesis_wants_grad(utts, return_device):
+    """The result stays on the device, grad mode is on and one of the coefficient matrices is a device tensor that
+    requires grad (CPU tensors take the host path)."""
+    import sys
+
+    torch = sys.modules.get("torch")
+    return bool(return_device and torch is not None and torch.is_grad_enabled()
+                and any(torch.is_tensor(x) and x.requires_grad and x.device.type != "cpu" for u in utts for x in u[:3]))
+
+
 def synthesis_from_compressed_batch(utts, fs, fft_len=None, b_voi_ap_win=True, b_const_rate=False, alpha_phase=None,
                                     b_out_hpf=True, noise=None, engine=None, per_phase_type='magphase',
                                     b_post_filter=False, b_fbank_mel=False, noise_mode='reference', noise_seeds=None,
@@ -805,9 +815,28 @@ def synthesis_from_compressed_batch(utts, fs, fft_len=None, b_voi_ap_win=True, b
     the int16 samples la.write_audio_file(..., norm=pcm16_norm) would store, converted on the device (mpx_pcm16).
     prepared: the host side of THIS batch built ahead of time (engine.prepare_async("synthesis", utts, fs, fft_len=...,
     b_voi_ap_win=..., b_const_rate=...).result(): the planner thread prepares launch i + 1 while this thread enqueues
-    launch i; None: prepared here)."""
+    launch i; None: prepared here).
+    Autograd: with return_device, grad mode on and a device m_mag_mel_log / m_real_mel / m_imag_mel that requires grad,
+    the signals carry a grad_fn and tensor.backward() reaches the three coefficient matrices, in each one's own dtype and
+    shape (magphase_amd/autograd.py; the forward launches and their samples are the same).  At
+    both frame rates, with and without b_out_hpf / b_voi_ap_win / b_fbank_mel, for either noise_mode or an explicit noise.
+    Not differentiable: v_lf0 (integer pitch marks and the voicing flag), fs, the noise and its two gains.
+    NotImplementedError, naming the argument, for per_phase_type 'min_phase' / 'linear', a truthy b_post_filter,
+    pcm16_norm other than False and prepared=.  MAGPHASE_NOISE_SPECTRA=store is ignored by the backward pass (it
+    recomputes the noise spectra).  No double backward."""
     if return_device and async_out:
         raise ValueError("return_device and async_out exclude each other (async_out is a download)")
+    want_grad = _compressed_synthesis_wants_grad(utts, return_device)
+    if want_grad:   # what has no backward pass says so before anything is built
+        if per_phase_type in ('min_phase', 'linear'):
+            raise NotImplementedError("per_phase_type=%r has no backward pass: only 'magphase' is differentiable"
+                                      % (per_phase_type,))
+        if b_post_filter and b_post_filter != 'no':
+            raise NotImplementedError("b_post_filter=%r has no backward pass" % (b_post_filter,))
+        if pcm16_norm is not False:
+            raise NotImplementedError("pcm16_norm=%r (int16 output) has no backward pass" % (pcm16_norm,))
+        if prepared is not None:
+            raise NotImplementedError("prepared= (built from host arrays) has no backward pass")
     checked, _on_dev = _tensor_inputs(utts, _SYN_NAMES, lf0_at=3)
     if checked is not utts and prepared is not None:
         raise ValueError("prepared= was built from host arrays: it cannot be combined with tensor inputs")
@@ -817,6 +846,11 @@ def synthesis_from_compressed_batch(utts, fs, fft_len=None, b_voi_ap_win=True, b
                                    b_const_rate=b_const_rate, alpha_phase=alpha_phase, noise=noise,
                                    per_phase_type=per_phase_type, post_filter=b_post_filter, b_fbank_mel=b_fbank_mel,
                                    noise_mode=noise_mode, noise_seeds=noise_seeds, defer_rng=defer_rng, prepared=prepared)
+    if want_grad:   # the same launches inside a torch.autograd.Function (magphase_amd/autograd.py)
+        from .autograd import synthesize_compressed
+
+        pcm_dev = synthesize_compressed(plan, b_out_hpf, utts)
+        return [pcm_dev[int(plan.out_off_host[u]):int(plan.out_off_host[u + 1])] for u in range(len(utts))]
     pcm_dev = plan.run()
     if b_out_hpf:   # magphase.py:981-995, float64 on the device (engine.output_hpf); _output_hpf is the host form
         pcm_dev = engine.output_hpf(pcm_dev, plan.out_off_host, fs)

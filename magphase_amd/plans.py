@@ -1272,6 +1272,110 @@ class CompressedSynthesisPlan:
             self.debug = dict(mag=mag, real=real, imag=imag, sums=sums)
         return pcm
 
+    # ------------------------------------------------------------------ backward pass
+    def backward_tables(self):
+        """The device tables of run_backward, built and uploaded by the first backward pass: where every frame finds its
+        gradient samples in the [total_out] buffer (hostmath.lossless_backward_table, from the plan's own pm_rel /
+        out_start tables), the index that reverses every utterance in place (the adjoint high-pass; formed on the device
+        from the utterances' offsets) and, at the constant rate, the frame ranges of the row interpolation's adjoint
+        (hostmath.lerp_adjoint_table)."""
+        b = getattr(self, "_bwd", None)
+        if b is None:
+            e, torch = self.engine, _torch()
+            _wait_ready(self)
+            rel = self.pm_rel.cpu().numpy().astype(np.int64)
+            starts = self.out_start.cpu().numpy().astype(np.int64)
+            pos, lo, hi = hm.lossless_backward_table(rel, self.frame_off, starts, self.out_len, self.out_off_host,
+                                                     self.fft_len)
+            b = dict(e.to_device_packed([("pos", pos, np.int64), ("lo", lo, np.int32), ("hi", hi, np.int32),
+                                         ("off", self.out_off_host, np.int64)]))
+            # sample t of utterance u <-> sample off[u] + off[u + 1] - 1 - t: built on the device from the offsets
+            off = b["off"]
+            utt = torch.repeat_interleave(torch.arange(self.n_utts, device=e.device), off[1:] - off[:-1],
+                                          output_size=self.total_out)
+            b["rev"] = (off[:-1] + off[1:] - 1)[utt] - torch.arange(self.total_out, device=e.device)
+            if self.b_const_rate:
+                r0, r1 = self.row0.cpu().numpy(), self.row1.cpu().numpy()
+                b["adj"] = e.to_device(hm.lerp_adjoint_table(r0, r1, np.zeros(r0.size), self.n_rows).reshape(-1), np.int32)
+            self._bwd = b
+        return b
+
+    def _check_differentiable(self):
+        if type(self)._ola_entry != "mpx_synthesis_compressed_ola":
+            raise NotImplementedError("the type-2 synthesis has no backward pass")
+        if self.per_phase_type != "magphase":
+            raise NotImplementedError("per_phase_type=%r has no backward pass (only 'magphase')" % (self.per_phase_type,))
+        if self.apply_post_filter:
+            raise NotImplementedError("b_post_filter has no backward pass")
+
+    def adjoint_hpf(self, grad, fs=None):
+        """The adjoint of the output high-pass (Engine.output_hpf: a causal LTI filter per utterance, from a zero state) is
+        the same filter run backwards in time: grad [total_out] -> float32, every utterance reversed, filtered, reversed
+        again, float32."""
+        torch = _torch()
+        rev = self.backward_tables()["rev"]
+        g = grad.to(torch.float32).reshape(-1)
+        g = self.engine.output_hpf(g.index_select(0, rev).contiguous(), self.out_off_host, self.fs if fs is None else fs)
+        return g.index_select(0, rev).to(torch.float32)
+
+    def run_backward(self, grad_pcm, need=(True, True, True), mark=None):
+        """The gradients of run()'s waveform with respect to the coefficient rows (a_mag [n_rows x mag_dim], a_real and
+        a_imag [n_rows x phase_dim]), given grad_pcm = dL/d(run()'s result): contiguous float32 [total_out].  None where
+        need[k] is false.  After run(): the unwarped rows (spec) and the noise gains of the plan's work buffers are read,
+        not recomputed.  k_synth_comp_bwd (per-frame gradient rows; the noise spectra are recomputed -- a plan that
+        stores them, MAGPHASE_NOISE_SPECTRA=store, is differentiated the same way and the stored spectra are not read),
+        at the constant rate k_rows_lerp_adjoint at width H and the forward's unwarp again at the rows' rate (E),
+        k_mel_unwarp_bwd (up to three jobs in one launch), at the constant rate k_rows_lerp_adjoint at width phase_dim."""
+        self._check_differentiable()
+        torch = _torch()
+        e, N = self.engine, self.fft_len
+        H = N // 2 + 1
+        F, R = self.total_frames, self.n_rows
+        mark = mark or (lambda name: None)
+        if (grad_pcm.dtype != torch.float32 or int(grad_pcm.numel()) != self.total_out or not grad_pcm.is_contiguous()):
+            raise ValueError("run_backward: grad_pcm must be a contiguous float32 [%d]" % self.total_out)
+        need = tuple(bool(n) for n in need)
+        dims = (self.mag_dim, self.phase_dim, self.phase_dim)
+        if F == 0 or R == 0 or not any(need):
+            return tuple(torch.zeros((R, d), dtype=torch.float32, device=e.device) if n else None
+                         for n, d in zip(need, dims))
+        buf = getattr(self, "_buf", None)
+        if buf is None:
+            raise RuntimeError("run_backward: call run() first (the backward pass reads the forward's unwarped rows)")
+        t = self.backward_tables()
+        ld = buf["ld"]
+        mag, real, imag = buf["spec"]
+        n_per = int(self.n_per)
+        n_ph = min((n_per + 63) // 64 * 64, H)
+        mark("start")
+        # per-frame gradient rows, allocated apart from spec (whose rows the kernel reads)
+        g_m, g_a, g_b = (e.empty((F, ld))[:, :H] if n else None for n in need)
+        e.launch("mpx_synthesis_compressed_backward", N, e.tables(N), grad_pcm, self.total_out, t["pos"], t["lo"], t["hi"],
+                 F, mag, real, imag, ld, self.noise, self.npos, self.nleft, self.nright, self.wtype, self.voiced,
+                 buf["inv_gain"], self.win_l, self.win_r, self.per_v, self.ap_v, self.ap_u, n_per, g_m, g_a, g_b, ld)
+        mark("k_synth_comp_bwd")
+        e_mag, ld_e, g_e, ld_g = mag, ld, g_m, ld
+        if self.b_const_rate and need[0]:
+            g_e = e.rows_lerp_adjoint((g_m, None, None), t["adj"], self.rowt, R)[0]
+            ld_g = int(g_e.stride(0))
+            mark("k_rows_lerp_adjoint")
+            # E = exp(U_mag^T a_mag) at the rows' rate: the forward's unwarp again (its phase outputs are scratch)
+            e_mag, s_r, s_i = (e.empty((R, ld)) for _ in range(3))
+            e.launch("mpx_mel_unwarp", R, H, self.a_mag, self.mag_dim, self.u_mag, e_mag, self.a_real, self.a_imag,
+                     self.phase_dim, self.u_phase, s_r, s_i, ld)
+            del s_r, s_i
+            mark("k_mel_unwarp_mfma")
+        o_m = e.empty((R, self.mag_dim)) if need[0] else None
+        n_prow = F if self.b_const_rate else R      # (variable rate: rows == frames)
+        o_a, o_b = (e.empty((n_prow, self.phase_dim)) if n else None for n in need[1:])
+        e.launch("mpx_mel_unwarp_backward", H, e_mag, ld_e, g_e, ld_g, self.u_mag, self.mag_dim, R, o_m, g_a, g_b, ld, n_ph,
+                 self.u_phase, self.phase_dim, n_prow, o_a, o_b)
+        mark("k_mel_unwarp_bwd")
+        if self.b_const_rate and (need[1] or need[2]):
+            _none, o_a, o_b = e.rows_lerp_adjoint((None, o_a, o_b), t["adj"], self.rowt, R)
+            mark("k_rows_lerp_adjoint")
+        return o_m, o_a, o_b
+
 
 class Type2SynthesisPlan(CompressedSynthesisPlan):
     """
