@@ -375,6 +375,19 @@ int mpx_roundtrip_lossless_ola(void* stream, int fft_len, const void* tables, co
  * frame from its host tables (host function: no stream, no device); class_host: int32 [n_frames].
  */
 #define MPX_RT_FULL_SUPPORT 1u
+/*
+ * How the feature rows are stored (fft_len 4096 without MPX_RT_FULL_SUPPORT; every other instance ignores both bits and
+ * stores as under MPX_RT_STORE_ROWS).  Default: by line -- every interior store of a row covers two whole, aligned 128-byte
+ * lines of memory whatever the row's offset in its line (the phase, taken from each row pointer: any ld, any base).
+ * MPX_RT_STORE_ROWS: 256-byte blocks aligned to the row's first float.  MPX_RT_STORE_NT: by line, the interior stores
+ * non-temporal (not together with MPX_RT_STORE_ROWS).  The values written are the same under all three.
+ * mpx_roundtrip_store_map: the by-line shape for a row of phase 0 ... 31, out: int32 [34][64] -- per store of a plane in
+ * issue order the row float each lane writes, -1 where the lane is masked -- from the functions the kernel takes its
+ * addresses and predicates from; phase 0 is the MPX_RT_STORE_ROWS shape.  fft_len must be 4096.  Host function.
+ */
+#define MPX_RT_STORE_ROWS 4u
+#define MPX_RT_STORE_NT 8u
+int mpx_roundtrip_store_map(int fft_len, int phase, int32_t* out);
 int mpx_roundtrip_lossless_ola_flags(void* stream, int fft_len, const void* tables, const float* sig,
                                      const int64_t* frame_pos, const int32_t* frame_left, const int32_t* frame_right,
                                      int64_t n_frames, const mpx_ola_run* runs, int32_t n_runs, const int32_t* slot_off,

@@ -55,6 +55,7 @@ PROTOTYPES = {
     "mpx_roundtrip_lossless_ola_flags": (i32, [vp, i32] + [vp] * 5 + [i64, vp, i32, vp, vp, i32] + [vp] * 6 + [i64, u32]),
     "mpx_roundtrip_support_classes": (i32, [i32, vp, vp, i64, vp]),
     "mpx_roundtrip_frame_extents": (i32, [i32, vp, vp, i64, u32, vp]),
+    "mpx_roundtrip_store_map": (i32, [i32, i32, vp]),
     "mpx_roundtrip_slot_weights": (i32, [vp, i32]),
     "mpx_roundtrip_frame_terms": (i32, [i32, vp, vp, i64, vp]),
     "mpx_roundtrip_slot_costs": (i32, [vp, i32]),
@@ -120,6 +121,9 @@ PROTOTYPES = {
     "mpx_post_filter_merlin": (i32, [vp, vp, i64, i32] + [vp] * 4 + [i32, f64, vp, f64] + [vp] * 5),
 }
 SYMBOLS = tuple(PROTOTYPES)
+# mpx_roundtrip_lossless_ola_flags: how the feature rows are stored (MPX_RT_STORE_ROWS, by line, MPX_RT_STORE_NT), by the
+# names MAGPHASE_RT_STORES takes
+RT_STORE_FLAGS = {"rows": 4, "lines": 0, "lines_nt": 8}
 del vp, i32, i64, sz, f64
 
 _lib = None

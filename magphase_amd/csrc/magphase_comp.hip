@@ -1303,7 +1303,13 @@ __device__ unsigned long long g_rt_endprobe[4 * 8192];   // per wave: start, end
 // frames add to the ring (mpx_roundtrip_frame_extents) both read.
 template <int P>
 constexpr bool roundtrip_prunes(bool cls) { return cls && P == 32 && comp_compact<P>() && !MPX_COMP_DIT; }
-template <int P, bool CLS = false>
+// ST: how the feature rows are stored.  kStoreRows: 256-byte blocks aligned to the row (k_analysis' shape).  kStoreLines
+// (P = 32 with CLS only): blocks aligned to memory, two whole 128-byte lines each whatever the row's phase (mpx_common.hpp,
+// "Row stores by line").  kStoreLinesNT: those with the non-temporal bit on the interior (whole-line) stores; the clipped
+// edge blocks and the two parts of the middle block stay plain -- a sibling wave or the next store completes their lines,
+// so they need L2's merging.
+constexpr int kStoreRows = 0, kStoreLines = 1, kStoreLinesNT = 2;
+template <int P, bool CLS = false, int ST = kStoreRows>
 __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const float* __restrict__ sig,
                                                                        const long long* __restrict__ fpos,
                                                                        const int* __restrict__ fleft,
@@ -1317,6 +1323,7 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
                                                                        float* __restrict__ oimag, float* __restrict__ strips,
                                                                        float* __restrict__ pcm, long long ld) {
     constexpr int M = 64 * P, N = 2 * M, HP = P / 2;
+    static_assert(ST == kStoreRows || (P == 32 && CLS), "the line-aligned store forms exist for P = 32 with CLS only");
     constexpr bool kCls = roundtrip_prunes<P>(CLS);   // the forms that have pruned passes
     constexpr int NW = kCls ? kSupportNarrow : 0;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1371,33 +1378,91 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
             float* row_m = omag + (long long)fi * ld;
             float* row_r = oreal + (long long)fi * ld;
             float* row_i = oimag + (long long)fi * ld;
-            float* mlo = row_m + lane;
-            float* rlo = row_r + lane;
-            float* ilo = row_i + lane;
+            // ... or, by line (ST != kStoreRows), the same two streams in blocks aligned to memory: each plane's phase from
+            // its own row pointer (wave-uniform; any ld, any base), the six predicates as lane masks formed once per frame
+            int s_m = 0, s_r = 0, s_i = 0;
+            if constexpr (ST != kStoreRows) {
+                s_m = __builtin_amdgcn_readfirstlane(row_store_phase(row_m));
+                s_r = __builtin_amdgcn_readfirstlane(row_store_phase(row_r));
+                s_i = __builtin_amdgcn_readfirstlane(row_store_phase(row_i));
+            }
+            const bool pv_m = row_asc_prev(lane, s_m), pv_r = row_asc_prev(lane, s_r), pv_i = row_asc_prev(lane, s_i);
+            const bool cu_m = row_mir_cur(lane, s_m), cu_r = row_mir_cur(lane, s_r), cu_i = row_mir_cur(lane, s_i);
+            // (by line the per-lane offsets are formed per store from the lane and the store's predicate: offsets kept per plane
+            // would be four more live registers, and the form then needs scratch)
             const int hoff = lane0 ? M - 64 : M - lane;
-            float* mhi = row_m + hoff;
-            float* rhi = row_r + hoff;
-            float* ihi = row_i + hoff;
+            float* mlo = row_m + (ST != kStoreRows ? 0 : lane);
+            float* rlo = row_r + (ST != kStoreRows ? 0 : lane);
+            float* ilo = row_i + (ST != kStoreRows ? 0 : lane);
+            float* mhi = row_m + (ST != kStoreRows ? 0 : hoff);
+            float* rhi = row_r + (ST != kStoreRows ? 0 : hoff);
+            float* ihi = row_i + (ST != kStoreRows ? 0 : hoff);
+            auto st_line = [](float* dst, float v) {   // an interior block: two whole lines
+                if constexpr (ST == kStoreLinesNT) __builtin_nontemporal_store(v, dst);
+                else *dst = v;
+            };
+            // A clipped block: the store under a lane mask, without a branch.  An `if` around a store is a basic block of its
+            // own, and the compiler contracts products with sums block by block: the split's arithmetic, which it sinks past
+            // the first step's stores, would be cut differently from the row-relative form's and the rows would differ from
+            // that form's in their last bits.  So the by-line forms keep that form's control flow -- one conditional block in
+            // the first step, where it stores bin M -- and mask their other clipped stores here.
+            auto st_mask = [](float* dst, float v, unsigned long long mask) {
+                unsigned long long saved;
+                asm volatile("s_and_saveexec_b64 %0, %3\n\tglobal_store_dword %1, %2, off\n\ts_mov_b64 exec, %0"
+                             : "=&s"(saved)
+                             : "v"(dst), "v"(v), "s"(mask)
+                             : "memory", "scc");
+            };
+            unsigned long long k_pv_m = 0, k_pv_r = 0, k_pv_i = 0, k_cu_m = 0, k_cu_r = 0, k_cu_i = 0;
+            if constexpr (ST != kStoreRows) {
+                k_pv_m = __builtin_amdgcn_ballot_w64(pv_m), k_cu_m = __builtin_amdgcn_ballot_w64(cu_m);
+                k_pv_r = __builtin_amdgcn_ballot_w64(pv_r), k_cu_r = __builtin_amdgcn_ballot_w64(cu_r);
+                k_pv_i = __builtin_amdgcn_ballot_w64(pv_i), k_cu_i = __builtin_amdgcn_ballot_w64(cu_i);
+            }
             float zr[HP], zi[HP];   // Z[M - k]
             float hm = 0.0f, ha = 0.0f, hb = 0.0f;   // mirror features of the previous step
+            float pm = 0.0f, pa = 0.0f, pb = 0.0f;   // own features of the previous step (by line only)
 #pragma unroll
             for (int q = 0; q < HP; ++q) {
                 float m, a, b, mq, aq, bq;
                 feat(no_r[q], no_i[q], m, a, b);
                 feat(nm_r[q], nm_i[q], mq, aq, bq);
-                mlo[64 * q] = m;
-                rlo[64 * q] = a;
-                ilo[64 * q] = b;
-                if (q == 0) {
-                    if (lane0) {
-                        row_m[M] = mq;
-                        row_r[M] = aq;
-                        row_i[M] = bq;
+                if constexpr (ST == kStoreRows) {
+                    mlo[64 * q] = m;
+                    rlo[64 * q] = a;
+                    ilo[64 * q] = b;
+                    if (q == 0) {
+                        if (lane0) {
+                            row_m[M] = mq;
+                            row_r[M] = aq;
+                            row_i[M] = bq;
+                        }
+                    } else {
+                        mhi[-64 * (q - 1)] = lane0 ? mq : hm;
+                        rhi[-64 * (q - 1)] = lane0 ? aq : ha;
+                        ihi[-64 * (q - 1)] = lane0 ? bq : hb;
                     }
-                } else {
-                    mhi[-64 * (q - 1)] = lane0 ? mq : hm;
-                    rhi[-64 * (q - 1)] = lane0 ? aq : ha;
-                    ihi[-64 * (q - 1)] = lane0 ? bq : hb;
+                } else if (q == 0) {   // the clipped blocks B_0 and B_P
+                    st_mask(mlo + row_asc_base(lane, false) + row_asc_off(0), m, ~k_pv_m);
+                    st_mask(rlo + row_asc_base(lane, false) + row_asc_off(0), a, ~k_pv_r);
+                    st_mask(ilo + row_asc_base(lane, false) + row_asc_off(0), b, ~k_pv_i);
+                    if (cu_m || cu_r || cu_i) {
+                        st_mask(mhi + row_mir_base(lane, true, M) + row_mir_off(0), mq, k_cu_m);
+                        st_mask(rhi + row_mir_base(lane, true, M) + row_mir_off(0), aq, k_cu_r);
+                        st_mask(ihi + row_mir_base(lane, true, M) + row_mir_off(0), bq, k_cu_i);
+                    }
+                } else {               // B_q and B_{P - q}
+                    st_line(mlo + row_asc_base(lane, pv_m) + row_asc_off(q), pv_m ? pm : m);
+                    st_line(rlo + row_asc_base(lane, pv_r) + row_asc_off(q), pv_r ? pa : a);
+                    st_line(ilo + row_asc_base(lane, pv_i) + row_asc_off(q), pv_i ? pb : b);
+                    st_line(mhi + row_mir_base(lane, cu_m, M) + row_mir_off(q), cu_m ? mq : hm);
+                    st_line(rhi + row_mir_base(lane, cu_r, M) + row_mir_off(q), cu_r ? aq : ha);
+                    st_line(ihi + row_mir_base(lane, cu_i, M) + row_mir_off(q), cu_i ? bq : hb);
+                }
+                if constexpr (ST != kStoreRows) {
+                    pm = m;
+                    pa = a;
+                    pb = b;
                 }
                 hm = mq;
                 ha = aq;
@@ -1418,9 +1483,20 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
             }
             float mH, aH, bH;
             feat(nh_r, nh_i, mH, aH, bH);
-            mhi[-64 * (HP - 1)] = lane0 ? mH : hm;
-            rhi[-64 * (HP - 1)] = lane0 ? aH : ha;
-            ihi[-64 * (HP - 1)] = lane0 ? bH : hb;
+            if constexpr (ST == kStoreRows) {
+                mhi[-64 * (HP - 1)] = lane0 ? mH : hm;
+                rhi[-64 * (HP - 1)] = lane0 ? aH : ha;
+                ihi[-64 * (HP - 1)] = lane0 ? bH : hb;
+            } else {   // the middle block B_{P/2}: its low part from the ascending stream, its high part from the mirrors
+                st_mask(mlo + row_asc_base(lane, true) + row_asc_off(HP), pm, k_pv_m);
+                st_mask(rlo + row_asc_base(lane, true) + row_asc_off(HP), pa, k_pv_r);
+                st_mask(ilo + row_asc_base(lane, true) + row_asc_off(HP), pb, k_pv_i);
+                static_assert(row_mir_tail_live(0, true) && !row_mir_tail_live(1, true) && row_mir_tail_live(1, false),
+                              "the mirror tail's lanes: lane 0 and those that do not store this step's mirror");
+                st_mask(mhi + row_mir_base(lane, cu_m, M) + row_mir_off(HP), lane0 ? mH : hm, ~k_cu_m | 1ull);
+                st_mask(rhi + row_mir_base(lane, cu_r, M) + row_mir_off(HP), lane0 ? aH : ha, ~k_cu_r | 1ull);
+                st_mask(ihi + row_mir_base(lane, cu_i, M) + row_mir_off(HP), lane0 ? bH : hb, ~k_cu_i | 1ull);
+            }
             // bin M/2 (lane 0): Z = 2 conj(X)
             merge_handover<P>(zr, zi, 2.0f * nh_r, -2.0f * nh_i, xr, xi, lane);
         }
@@ -1873,12 +1949,27 @@ int mpx_roundtrip_support_classes(int fft_len, const int32_t* frame_left, const 
     return MPX_OK;
 }
 
+// The flags of mpx_roundtrip_lossless_ola_flags; the store bits change nothing about what a frame adds to the ring, so
+// mpx_roundtrip_frame_extents takes the same word and ignores them.
+static constexpr uint32_t kRtFlagsKnown = MPX_RT_FULL_SUPPORT | MPX_RT_STORE_ROWS | MPX_RT_STORE_NT;
+
+// The row float every lane writes in every store of one plane of one frame, for a row of phase `phase`, from the helpers
+// the kernel's line-aligned forms take their bases and predicates from (mpx_common.hpp, "Row stores by line").
+int mpx_roundtrip_store_map(int fft_len, int phase, int32_t* out) {
+    if (fft_len != 4096) return fail(MPX_ERR_ARG, "mpx_roundtrip_store_map: only fft_len 4096 has the line-aligned stores%s");
+    if (phase < 0 || phase > 31 || !out) return fail(MPX_ERR_ARG, "mpx_roundtrip_store_map: bad arguments%s");
+    const int P = p_of(fft_len);
+    for (int st = 0; st < row_store_count(P); ++st)
+        for (int lane = 0; lane < 64; ++lane) out[64 * st + lane] = row_store_index(st, lane, phase, P);
+    return MPX_OK;
+}
+
 // What the instance that mpx_roundtrip_lossless_ola_flags launches for (fft_len, flags) can add to the ring, per frame: the
 // samples of the rows support_row_live names for a frame the kernel takes as narrow, the whole frame otherwise -- and the
 // whole frame throughout where that instance has no pruned passes (the launch's own choice of CLS, roundtrip_prunes).
 int mpx_roundtrip_frame_extents(int fft_len, const int32_t* frame_left, const int32_t* frame_right, int64_t n_frames,
                                 uint32_t flags, int32_t* extents_host) {
-    if (flags & ~(uint32_t)MPX_RT_FULL_SUPPORT) return fail(MPX_ERR_ARG, "mpx_roundtrip_frame_extents: unknown flag%s");
+    if (flags & ~kRtFlagsKnown) return fail(MPX_ERR_ARG, "mpx_roundtrip_frame_extents: unknown flag%s");
     const int P = p_of(fft_len);
     if (!P) return fail(MPX_ERR_ARG, "mpx_roundtrip_frame_extents: fft_len must be 1024, 2048 or 4096%s");
     if (n_frames < 0 || (n_frames > 0 && (!frame_left || !frame_right || !extents_host)))
@@ -1916,7 +2007,9 @@ int mpx_roundtrip_lossless_ola_flags(void* stream, int fft_len, const void* tabl
                                      const int32_t* slot_runs, int32_t n_slots, const int32_t* pm_rel, float* out_mag,
                                      float* out_real, float* out_imag, float* strips, float* pcm_out, int64_t ld,
                                      uint32_t flags) {
-    if (flags & ~(uint32_t)MPX_RT_FULL_SUPPORT) return fail(MPX_ERR_ARG, "mpx_roundtrip_lossless_ola: unknown flag%s");
+    if (flags & ~kRtFlagsKnown) return fail(MPX_ERR_ARG, "mpx_roundtrip_lossless_ola: unknown flag%s");
+    if ((flags & MPX_RT_STORE_ROWS) && (flags & MPX_RT_STORE_NT))
+        return fail(MPX_ERR_ARG, "mpx_roundtrip_lossless_ola: MPX_RT_STORE_NT needs the line-aligned stores%s");
     const int P = p_of(fft_len);
     if (!P) return fail(MPX_ERR_ARG, "mpx_roundtrip_lossless_ola: fft_len must be 1024, 2048 or 4096%s");
     if (n_frames < 0 || n_runs < 0 || n_slots < 0) return fail(MPX_ERR_ARG, "mpx_roundtrip_lossless_ola: negative count%s");
@@ -1927,9 +2020,10 @@ int mpx_roundtrip_lossless_ola_flags(void* stream, int fft_len, const void* tabl
         return fail(MPX_ERR_ARG, "mpx_roundtrip_lossless_ola: null pointer%s");
     hipStream_t s = (hipStream_t)stream;
     const dim3 pgrid((n_slots + kCompPairs - 1) / kCompPairs), pblock(kCompPairWaves * 64);
-#define MPX_LAUNCH_RT(PP, CLS)                                                                                         \
+#define MPX_LAUNCH_RT(PP, CLS) MPX_LAUNCH_RT_K(PP, (k_roundtrip_pair<PP, CLS>))
+#define MPX_LAUNCH_RT_K(PP, KERNEL)                                                                                    \
     do {                                                                                                             \
-        auto KK = k_roundtrip_pair<PP, CLS>;                                                                         \
+        auto KK = KERNEL;                                                                                            \
         if (int rc = set_lds(KK, lds_bytes_comp_pair<PP>())) return rc;                                              \
         hipLaunchKernelGGL(KK, pgrid, pblock, lds_bytes_comp_pair<PP>(), s, sig,                                     \
                            (const long long*)frame_pos, frame_left, frame_right, (const RunDesc*)runs, slot_off,     \
@@ -1937,11 +2031,16 @@ int mpx_roundtrip_lossless_ola_flags(void* stream, int fft_len, const void* tabl
                            pcm_out, (long long)ld);                                                                  \
     } while (0)
     // support classes (k_roundtrip_pair's CLS): only N = 4096 has a narrow class
-    if (P == 32 && !(flags & MPX_RT_FULL_SUPPORT)) MPX_LAUNCH_RT(32, true);
-    else if (P == 32) MPX_LAUNCH_RT(32, false);
+    // store forms (k_roundtrip_pair's ST): only that instance has the line-aligned ones, every other ignores the bits
+    if (P == 32 && !(flags & MPX_RT_FULL_SUPPORT)) {
+        if (flags & MPX_RT_STORE_ROWS) MPX_LAUNCH_RT(32, true);
+        else if (flags & MPX_RT_STORE_NT) MPX_LAUNCH_RT_K(32, (k_roundtrip_pair<32, true, kStoreLinesNT>));
+        else MPX_LAUNCH_RT_K(32, (k_roundtrip_pair<32, true, kStoreLines>));
+    } else if (P == 32) MPX_LAUNCH_RT(32, false);
     else if (P == 16) MPX_LAUNCH_RT(16, false);
     else MPX_LAUNCH_RT(8, false);
 #undef MPX_LAUNCH_RT
+#undef MPX_LAUNCH_RT_K
     MPX_HIP_CHECK(hipGetLastError());
     return MPX_OK;
 }

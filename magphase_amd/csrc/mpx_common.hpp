@@ -200,6 +200,43 @@ __host__ __device__ constexpr unsigned support_zero_rows(int W) {
 // ... and whether row q of the rebuilt frame is in it
 __host__ __device__ constexpr bool support_row_live(int q, int W, int P) { return q >= P / 2 - W && q < P / 2 + W; }
 
+// Row stores by line (k_roundtrip_pair's `lines` forms).  A feature row of M + 1 = 64 P + 1 floats starts
+// s = (address of its float 0 / 4) mod 32 floats into a 128-byte line -- any s with a dense pitch -- so a 256-byte wave store
+// aligned to the ROW straddles three lines and leaves two of them partially written.  Here the stores are aligned to
+// MEMORY: block B_c = row floats [64 c - s, 64 c - s + 63], c = 0 ... P, two whole lines each (B_0 clipped below float 0,
+// B_P above float M).  A lane holds the own bin k = lane + 64 q and its mirror M - k at step q = 0 ... P/2 - 1, so
+//   ascending stream  B_q is complete at step q: lanes < 64 - s store this step's value, the others the previous step's,
+//                     64 floats lower; B_0 has the first group only, and the second group's values of the last step (floats
+//                     [M/2 - s, M/2 - 1], the low part of B_{P/2}) go out after the loop;
+//   mirror stream     B_{P - q} is complete at step q: lanes <= s store this step's mirror, the others the previous step's,
+//                     64 floats higher; step 0 stores the clipped B_P (bin M included) from the first group only, and the
+//                     high part of B_{P/2} -- bin M/2 from lane 0, the last step's mirrors from the lanes > s -- goes out
+//                     after the loop.
+// 2 (P/2) + 2 stores per plane in issue order: (ascending q, mirror q) for q = 0 ... P/2 - 1, the ascending tail, the mirror
+// tail.  With s == 0 the second ascending group is empty and the first mirror group is lane 0: the row-relative shape
+// (ascending 256-byte blocks, mirrors regrouped around lane 0, bin M alone), float for float.  The kernel takes its
+// per-lane bases, predicates and offsets from these functions, and so does mpx_roundtrip_store_map (the numpy twin:
+// hostmath.roundtrip_store_map), which the tests hold to "every float of the row exactly once, every interior store two
+// whole lines".
+__host__ __device__ inline int row_store_phase(const float* row) { return (int)(((unsigned long long)row >> 2) & 31u); }
+__host__ __device__ constexpr int row_store_count(int P) { return 2 * (P / 2) + 2; }
+__host__ __device__ constexpr bool row_asc_prev(int lane, int s) { return lane >= 64 - s; }   // stores the previous step's value
+__host__ __device__ constexpr int row_asc_base(int lane, bool prev) { return prev ? lane - 64 : lane; }
+__host__ __device__ constexpr int row_asc_off(int q) { return 64 * q; }                      // step q, and P/2: the tail
+__host__ __device__ constexpr bool row_mir_cur(int lane, int s) { return lane <= s; }         // stores this step's mirror
+__host__ __device__ constexpr int row_mir_base(int lane, bool cur, int M) { return cur ? M - 64 - lane : M - lane; }
+__host__ __device__ constexpr int row_mir_off(int q) { return -64 * (q - 1); }               // step q, and P/2: the tail
+__host__ __device__ constexpr bool row_mir_tail_live(int lane, bool cur) { return lane == 0 || !cur; }
+// the row float that `lane` writes in store `st` (issue order) of a plane whose row has phase s; -1: the lane is masked
+__host__ __device__ constexpr int row_store_index(int st, int lane, int s, int P) {
+    const int HP = P / 2, M = 64 * P, q = st >> 1;
+    const bool prev = row_asc_prev(lane, s), cur = row_mir_cur(lane, s);
+    if (st == 2 * HP) return prev ? row_asc_base(lane, true) + row_asc_off(HP) : -1;
+    if (st == 2 * HP + 1) return row_mir_tail_live(lane, cur) ? row_mir_base(lane, cur, M) + row_mir_off(HP) : -1;
+    if (!(st & 1)) return (q == 0 && prev) ? -1 : row_asc_base(lane, prev) + row_asc_off(q);
+    return (q == 0 && !cur) ? -1 : row_mir_base(lane, cur, M) + row_mir_off(q);
+}
+
 __device__ __forceinline__ FrameGeom frame_geom(const float* __restrict__ sig, long long pos, int L, int R, int N) {
     FrameGeom g;
     g.L = L;

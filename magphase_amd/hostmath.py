@@ -381,6 +381,36 @@ def roundtrip_frame_extents(left, right, fft_len, full_support=False):
     return np.stack([128 * (P // 2 - W), 128 * (P // 2 + W)], axis=1).astype(np.int32)
 
 
+def roundtrip_store_map(fft_len, phase):
+    """mpx_roundtrip_store_map in numpy (csrc/mpx_common.hpp, "Row stores by line"): how k_roundtrip_pair's line-aligned
+    forms store one feature row of M + 1 = fft_len / 2 + 1 floats whose float 0 lies `phase` (0 ... 31) floats into a
+    128-byte line.  Per store of a plane in issue order -- (ascending q, mirror q) for q = 0 ... P/2 - 1, the ascending tail,
+    the mirror tail: 2 (P/2) + 2 = 34 -- the row float each of the 64 lanes writes, -1 where the lane is masked.  Lane l
+    holds the own bin l + 64 q and its mirror M - l - 64 q at step q; block B_c = floats [64 c - phase, 64 c - phase + 63] is
+    two whole lines of memory.  Ascending: the lanes < 64 - phase store step q's value, the others step q - 1's 64 floats
+    lower (none at q = 0; their last values are the tail).  Mirrors: the lanes <= phase store step q's mirror, the others
+    step q - 1's 64 floats higher (none at q = 0); the tail is bin M/2 from lane 0 and the last step's mirrors from the
+    lanes > phase.  Only fft_len 4096 has these forms.  int32 [34, 64]."""
+    if int(fft_len) != 4096:
+        raise ValueError("roundtrip_store_map: only fft_len 4096 has the line-aligned stores")
+    s = int(phase)
+    if not 0 <= s <= 31:
+        raise ValueError("roundtrip_store_map: phase must be 0 ... 31")
+    P = int(fft_len) // 128
+    HP, M = P // 2, 64 * P
+    lane = np.arange(64, dtype=np.int64)
+    prev, cur = lane >= 64 - s, lane <= s
+    asc = lane - np.where(prev, 64, 0)
+    mir = np.where(cur, M - 64 - lane, M - lane)
+    out = np.full((2 * HP + 2, 64), -1, dtype=np.int64)
+    for q in range(HP):
+        out[2 * q] = np.where(prev & (q == 0), -1, asc + 64 * q)
+        out[2 * q + 1] = np.where(~cur & (q == 0), -1, mir - 64 * (q - 1))
+    out[2 * HP] = np.where(prev, asc + 64 * HP, -1)
+    out[2 * HP + 1] = np.where((lane == 0) | ~cur, mir - 64 * (HP - 1), -1)
+    return out.astype(np.int32)
+
+
 def ola_runs(pm_rel_list, starts, out_lens, out_offs, fft_len, n_slots, frames_per_run=None, weights=None, gcuts=None,
              extents=None):
     """

@@ -545,6 +545,8 @@ class LosslessRoundTripPlan:
     and the waveform synthesis_from_lossless builds from them.
     """
 
+    DEFAULT_STORES = "lines_nt"   # DESIGN.md 3.3a, "Row stores by line": the fastest form of the A/B
+
     def __init__(self, engine, utts, fft_len=None, frames_per_run=None, n_slots=None):
         # n_slots: overrides the engine's slot count (small tests)
         self.engine = engine
@@ -556,6 +558,13 @@ class LosslessRoundTripPlan:
         # sized as if every frame filled its N samples -- the A/B switch of the seams sized by what the frames really add
         # (_frame_extents, hostmath.ola_runs)
         self.full_seams = self.full_support or os.environ.get("MAGPHASE_RT_SEAMS", "") == "full"
+        # MAGPHASE_RT_STORES=rows|lines|lines_nt (read here, at plan build): how the N = 4096 compact-support instance stores
+        # the feature rows -- in 256-byte blocks aligned to the row, in blocks of two whole 128-byte lines of memory, or those
+        # with the interior stores non-temporal (csrc/mpx_common.hpp, "Row stores by line"); the rows are the same, every
+        # other instance ignores it
+        self.stores = os.environ.get("MAGPHASE_RT_STORES", "") or self.DEFAULT_STORES
+        if self.stores not in _lib.RT_STORE_FLAGS:
+            raise ValueError("MAGPHASE_RT_STORES must be rows, lines or lines_nt, not %r" % self.stores)
         if not utts:   # an empty batch: nothing to plan, run() returns empty tensors
             self.analysis = self.synthesis = self.seams = None
             self.seam_geometry = "dense" if self.full_seams else "extents"
@@ -642,7 +651,7 @@ class LosslessRoundTripPlan:
         if self.total_frames == 0:
             return feats, out
         _run_ola(e, lambda strips, out: e.roundtrip_lossless_ola(self.fft_len, a, s, feats, strips, out,
-                                                                 full_support=self.full_support),
+                                                                 full_support=self.full_support, stores=self.stores),
                  self.fft_len, s, strips, out, self.total_out)
         return feats, out
 
