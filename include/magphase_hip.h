@@ -387,6 +387,17 @@ int mpx_roundtrip_lossless_ola(void* stream, int fft_len, const void* tables, co
  */
 #define MPX_RT_STORE_ROWS 4u
 #define MPX_RT_STORE_NT 8u
+/*
+ * How the waveform is rebuilt at fft_len 4096.  The spectrum the synthesis half is given is the one the analysis half has
+ * just computed, so the frame it rebuilds, fftshift(IFFT(hermitian(FFT(y)))) of the windowed, rotated, zero-padded frame y,
+ * is fftshift(y) up to the two transforms' float32 error.  Default: direct -- the kernel overlap-adds the windowed frame
+ * itself, right after it has gathered it, and runs neither the Hermitian merge nor the inverse transform.
+ * MPX_RT_INVERSE_TRANSFORM: it runs them (the earlier behaviour; the A/B switch).  The feature rows are the same bit for
+ * bit; the waveforms differ by that float32 error (about 3e-7 of the peak).  fft_len 2048 and 1024 keep the transform
+ * and ignore the bit: their inverse leaves the samples in kappa(lane) order, the gather in lane order, so the ring
+ * address of the direct add would differ.  mpx_roundtrip_frame_extents accepts and ignores the bit.
+ */
+#define MPX_RT_INVERSE_TRANSFORM 32u
 int mpx_roundtrip_store_map(int fft_len, int phase, int32_t* out);
 int mpx_roundtrip_lossless_ola_flags(void* stream, int fft_len, const void* tables, const float* sig,
                                      const int64_t* frame_pos, const int32_t* frame_left, const int32_t* frame_right,

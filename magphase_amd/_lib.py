@@ -124,6 +124,9 @@ SYMBOLS = tuple(PROTOTYPES)
 # mpx_roundtrip_lossless_ola_flags: how the feature rows are stored (MPX_RT_STORE_ROWS, by line, MPX_RT_STORE_NT), by the
 # names MAGPHASE_RT_STORES takes
 RT_STORE_FLAGS = {"rows": 4, "lines": 0, "lines_nt": 8}
+# ... and how the waveform is rebuilt at N = 4096 (the windowed frame added directly, or MPX_RT_INVERSE_TRANSFORM), by the
+# names MAGPHASE_RT_INVERSE takes
+RT_INVERSE_FLAGS = {"direct": 0, "transform": 32}
 del vp, i32, i64, sz, f64
 
 _lib = None

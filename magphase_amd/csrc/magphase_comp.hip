@@ -84,6 +84,26 @@ __device__ __forceinline__ void noise_window_gather(const FrameGeom& g, int wtyp
     }
 }
 
+// What a caller may place inside noise_fft (k_roundtrip_pair's direct arm): gathered(re, im, narrow_c) runs right after the
+// gather, on the windowed, rotated frame in its registers (row j <-> samples 128 j + 2 lane, + 1; narrow_c: a
+// std::bool_constant, whether this is the class arm, whose other rows are not defined yet); exchanged() runs once the forward
+// transform has made its last use of the exchange buffer.  The default does nothing: every other caller's code is unchanged.
+struct NoiseFftNoHook {
+    template <int P, typename B>
+    __device__ __forceinline__ void gathered(float (&)[P], float (&)[P], B) const {}
+    __device__ __forceinline__ void exchanged() const {}
+};
+template <typename GFn, typename XFn>
+struct NoiseFftHook {
+    GFn on_gathered;
+    XFn on_exchanged;
+    template <int P, typename B>
+    __device__ __forceinline__ void gathered(float (&re)[P], float (&im)[P], B narrow_c) const { on_gathered(re, im, narrow_c); }
+    __device__ __forceinline__ void exchanged() const { on_exchanged(); }
+};
+template <typename GFn, typename XFn>
+__device__ __forceinline__ NoiseFftHook<GFn, XFn> noise_fft_hook(GFn g, XFn x) { return NoiseFftHook<GFn, XFn>{g, x}; }
+
 // Windowed noise frame (magphase.py:886-897: windowing() with per-frame window list, epoch moved to index 0 by
 // frm_list_to_matrix + fftshift) -> N-point real FFT -> Ns[k] for the bins kappa(lane) + 64 j, j = 0..P-1
 // (natural j), plus the Nyquist bin (real) on the lane with kappa == 0.  Synchronous staging (no prefetch).
@@ -93,10 +113,10 @@ __device__ __forceinline__ void noise_window_gather(const FrameGeom& g, int wtyp
 // (frame_support_class, mpx_common.hpp; the caller's promise) -- only the rows j < NW and j >= P - NW are gathered, the
 // others are constants 0, and the stages of the first in-register pass that meet those zeros are pruned for them.  Two
 // straight-line instances of the gather with those stages, one wave-uniform branch around them; everything else is shared.
-template <int P, bool PRESTAGED = false, bool COMPACT = false, int NW = 0>   // PRESTAGED: the caller already copied tile 0 into xbuf and waited for it
+template <int P, bool PRESTAGED = false, bool COMPACT = false, int NW = 0, typename Hook = NoiseFftNoHook>   // PRESTAGED: the caller already copied tile 0 into xbuf and waited for it
 __device__ __forceinline__ void noise_fft(const FrameGeom& g, int wtype, const float* tw, float* xbuf,
                                           unsigned xbuf_byte, int lane, float (&re)[P], float (&im)[P], float lc = 1.0f,
-                                          float ls = 0.0f, bool narrow = false) {
+                                          float ls = 0.0f, bool narrow = false, Hook hook = Hook()) {
     static_assert(NW == 0 || (COMPACT && !MPX_COMP_DIT), "support classes: the compact DIF form only");
     if constexpr (NW > 0) {
         // one wave-uniform choice per frame between two straight-line instances of the gather and of the stages of the
@@ -108,12 +128,14 @@ __device__ __forceinline__ void noise_fft(const FrameGeom& g, int wtype, const f
         if (narrow) {
             noise_window_gather<P, PRESTAGED, COMPACT, NW>(g, wtype, xbuf, xbuf_byte, lane, re, im);
             mpx_pin_live<~kZin>(re), mpx_pin_live<~kZin>(im);
+            hook.gathered(re, im, std::true_type());
             MPX_MARK("fft_forward");
             fft_inreg_pruned_stage<P, -1, P / 2, kZin, kAllRegs, 2 * S0>(re, im);
             MPX_ARM_END_CLASS();
         } else {
             noise_window_gather<P, PRESTAGED, COMPACT, P / 2>(g, wtype, xbuf, xbuf_byte, lane, re, im);
             mpx_pin(re), mpx_pin(im);
+            hook.gathered(re, im, std::false_type());
             MPX_MARK("fft_forward");
             fft_inreg_stages<P, -1, P / 2, 2 * S0>(re, im);
             MPX_ARM_END_FULL();
@@ -121,6 +143,7 @@ __device__ __forceinline__ void noise_fft(const FrameGeom& g, int wtype, const f
         const float4 pk = tw_half_pad<P>(tw, lane);
         fft_inreg_stages<P, -1, S0>(re, im);
         wave_fft_front_compact_rest<P, -1>(re, im, tw, xbuf, lane, pk.z, pk.w);
+        hook.exchanged();
         fft_inreg<P, -1>(re, im);
         (void)lc;
         (void)ls;
@@ -177,19 +200,24 @@ __device__ __forceinline__ void noise_fft(const FrameGeom& g, int wtype, const f
         wave_sync();
     }
     mpx_pin(re), mpx_pin(im);
+    hook.gathered(re, im, std::false_type());
     MPX_MARK("fft_forward");
     if constexpr (COMPACT) {   // (lc, ls) = W_128^lane from the pad of the lane's table row (k_synth_comp_pair keeps them there)
         const float4 pk = tw_half_pad<P>(tw, lane);
 #if MPX_COMP_DIT
         wave_fft_dit_compact<P, -1>(re, im, tw, xbuf, lane, pk.z, pk.w);   // output: register i <-> Z[lane + 64 i]
+        hook.exchanged();
 #else
         wave_fft_front_compact<P, -1>(re, im, tw, xbuf, lane, pk.z, pk.w);
+        hook.exchanged();
         fft_inreg<P, -1>(re, im);
 #endif
         (void)lc;
         (void)ls;
     } else {
-        wave_fft<P, -1>(re, im, tw, xbuf, lane);
+        wave_fft_front<P, -1>(re, im, tw, xbuf, lane);
+        hook.exchanged();
+        fft_inreg<P, -1>(re, im);
     }
 }
 
@@ -198,15 +226,15 @@ __device__ __forceinline__ void noise_fft(const FrameGeom& g, int wtype, const f
 // (X[k] = E + T, X[M-k] = conj(E - T)): P lane exchanges and P/2 split evaluations per lane instead of 2P and P of the
 // per-bin form.  The kappa == 0 lane's q == 0 pair is (DC, Nyquist); bin M/2 is its own mirror and comes out separately
 // (nh_*, meaningful on the kappa == 0 lane).
-template <int P, bool PRESTAGED = false, bool COMPACT = false, int NW = 0>   // NW, narrow: support class, see noise_fft
+template <int P, bool PRESTAGED = false, bool COMPACT = false, int NW = 0, typename Hook = NoiseFftNoHook>   // NW, narrow: support class; hook: see noise_fft
 __device__ __forceinline__ void noise_spectrum_paired(const FrameGeom& g, int wtype, const float* tw, float* xbuf,
                                                       unsigned xbuf_byte, int lane, float wl_c, float wl_s,
                                                       float (&no_r)[P / 2], float (&no_i)[P / 2], float (&nm_r)[P / 2],
                                                       float (&nm_i)[P / 2], float& nh_r, float& nh_i, float lc = 1.0f,
-                                                      float ls = 0.0f, bool narrow = false) {
+                                                      float ls = 0.0f, bool narrow = false, Hook hook = Hook()) {
     constexpr int LB = ilog2(P);
     float re[P], im[P];
-    noise_fft<P, PRESTAGED, COMPACT, NW>(g, wtype, tw, xbuf, xbuf_byte, lane, re, im, lc, ls, narrow);
+    noise_fft<P, PRESTAGED, COMPACT, NW>(g, wtype, tw, xbuf, xbuf_byte, lane, re, im, lc, ls, narrow, hook);
     mpx_pin(re), mpx_pin(im);
     MPX_MARK("split");
     if constexpr (COMPACT) {   // the split twiddle W_N^kappa from the table row's pad: not live across the transform
@@ -710,16 +738,16 @@ __device__ __forceinline__ void pair_frame_lane(const PairWave& w, int& lane, fl
 
 // Analysis of the staged frame g (Hann halves): X[k] of the own bins k = lane + 64 q (no_*) and of their mirrors M - k
 // (nm_*), bin M/2 on lane 0 (nh_*).  NW, narrow: the frame's support class (noise_fft).
-template <int P, int NW = 0>
+template <int P, int NW = 0, typename Hook = NoiseFftNoHook>
 __device__ __forceinline__ void pair_analysis_spectrum(const PairWave& w, const FrameGeom& g, int lane, float wa_c,
                                                        float wa_s, float (&no_r)[P / 2], float (&no_i)[P / 2],
                                                        float (&nm_r)[P / 2], float (&nm_i)[P / 2], float& nh_r, float& nh_i,
-                                                       bool narrow = false) {
+                                                       bool narrow = false, Hook hook = Hook()) {
     constexpr bool kCompact = comp_compact<P>();
     MPX_MARK("frame_setup");
     staged_wait<0>();
     noise_spectrum_paired<P, true, kCompact, NW>(g, 0, w.tw, w.xbuf, w.xbuf_byte, lane, wa_c, wa_s, no_r, no_i, nm_r, nm_i,
-                                                 nh_r, nh_i, 1.0f, 0.0f, narrow);
+                                                 nh_r, nh_i, 1.0f, 0.0f, narrow, hook);
     if (P != 32) {   // FFT output lanes hold bins kappa(lane) + 64 q; the rows and the merge want bins lane + 64 q
         const int src = kappa<P>(lane);
 #pragma unroll
@@ -804,14 +832,18 @@ __device__ __forceinline__ void pair_inverse_fft_back_class(float (&xr)[P], floa
 // ROT: the rows are taken half a transform apart (the fftshift, see ring_add_plane).
 // NW > 0 (k_roundtrip_pair): where `narrow` (wave-uniform) holds, only the rows of support class NW are added -- a second
 // straight-line instance of the ring add whose row set is a compile-time constant; xr / xi then hold only those rows.
-template <int P, bool ROT, int NW = 0, typename CFn, typename LFn>
+// NATIN (k_roundtrip_pair's direct arm): xr / xi are not a transform's output but the gathered frame itself, register j <->
+// samples 128 j + 2 lane (+ 1) -- natural register order whatever the transforms' form.
+template <int P, bool ROT, int NW = 0, bool NATIN = false, typename CFn, typename LFn>
 __device__ __forceinline__ void pair_ordered_ola(const PairWave& w, const PairCursor& cur, float* smem,
                                                  const RunDesc* __restrict__ runs, const int* __restrict__ pm_rel,
                                                  float* __restrict__ strips, float* __restrict__ pcm, float (&xr)[P],
                                                  float (&xi)[P], int lane, CFn combine, LFn live, bool narrow = false) {
     constexpr int R = ring_len<P>();
     constexpr bool kDit = comp_compact<P>() && MPX_COMP_DIT;
+    constexpr bool kNat = kDit || NATIN;   // natural register order (ring_add_plane's NAT)
     static_assert(NW == 0 || (ROT && !kDit && (kCompPairWaves > 8)), "class row sets: the rotated DIF form only");
+    static_assert(!NATIN || (ROT && P == 32), "the gathered frame's lanes are the ring's only where kappa(lane) == lane");
     if constexpr (NW == 0) mpx_pin(xr), mpx_pin(xi);
     MPX_MARK("ticket");
     const int fi = cur.fi;
@@ -836,21 +868,21 @@ __device__ __forceinline__ void pair_ordered_ola(const PairWave& w, const PairCu
         const RingAddr ra = ring_addr<P>(w.ring_byte, x, lane);
         if constexpr (NW > 0) {
             if (narrow) {
-                constexpr unsigned kOut = support_out_regs<P>(NW);
+                constexpr unsigned kOut = NATIN ? ~support_zero_rows<P>(NW) : support_out_regs<P>(NW);
                 mpx_pin_live<kOut>(xr), mpx_pin_live<kOut>(xi);
                 auto live_nw = [](int q) { return support_row_live(q, NW, P); };
-                ring_add_plane<P, 0, CH, kDit, ROT>(smem, ra, xr, lane, combine, live_nw);
-                ring_add_plane<P, 1, CH, kDit, ROT>(smem, ra, xi, lane, combine, live_nw);
+                ring_add_plane<P, 0, CH, kNat, ROT>(smem, ra, xr, lane, combine, live_nw);
+                ring_add_plane<P, 1, CH, kNat, ROT>(smem, ra, xi, lane, combine, live_nw);
                 MPX_ARM_END_CLASS();
             } else {
                 mpx_pin(xr), mpx_pin(xi);
-                ring_add_plane<P, 0, CH, kDit, ROT>(smem, ra, xr, lane, combine, live);
-                ring_add_plane<P, 1, CH, kDit, ROT>(smem, ra, xi, lane, combine, live);
+                ring_add_plane<P, 0, CH, kNat, ROT>(smem, ra, xr, lane, combine, live);
+                ring_add_plane<P, 1, CH, kNat, ROT>(smem, ra, xi, lane, combine, live);
                 MPX_ARM_END_FULL();
             }
         } else {
-            ring_add_plane<P, 0, CH, kDit, ROT>(smem, ra, xr, lane, combine, live);
-            ring_add_plane<P, 1, CH, kDit, ROT>(smem, ra, xi, lane, combine, live);
+            ring_add_plane<P, 0, CH, kNat, ROT>(smem, ra, xr, lane, combine, live);
+            ring_add_plane<P, 1, CH, kNat, ROT>(smem, ra, xi, lane, combine, live);
         }
     } else {
         ring_add<P>(smem, w.ring_byte, x, xr, xi, lane, combine, live);
@@ -1281,7 +1313,7 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_synth_comp_pair(const f
 // into the pair's LDS ring in frame order (runs / slots / tickets / head strips as k_synth_ola_pair; k_ola_fixup
 // afterwards).  The output samples are what k_synth_ola_pair gives on the features this kernel wrote up to float32
 // rounding (the same expressions; the compiler contracts their multiply-adds differently in the two kernels: measured
-// 3.6e-7 of the signal peak); the features differ from k_analysis' in the last bits (DIT instead of DIF forward
+// 3.6e-7 of the signal peak; the DIRECT arm, see below, adds the windowed frame itself and is closer to the oracle); the features differ from k_analysis' in the last bits (DIT instead of DIF forward
 // transform).  Both are held to the two-launch path's tolerances against the oracle.
 // Every frame index of [0, n_frames) must belong to exactly one run: a frame outside the runs is not analysed.
 // ---------------------------------------------------------------------------------------------
@@ -1309,7 +1341,18 @@ constexpr bool roundtrip_prunes(bool cls) { return cls && P == 32 && comp_compac
 // edge blocks and the two parts of the middle block stay plain -- a sibling wave or the next store completes their lines,
 // so they need L2's merging.
 constexpr int kStoreRows = 0, kStoreLines = 1, kStoreLinesNT = 2;
-template <int P, bool CLS = false, int ST = kStoreRows>
+// DIRECT (P = 32; the default of the launch, MPX_RT_INVERSE_TRANSFORM takes the other arm): the synthesis half is fed X
+// exactly as the split leaves it, so what the merge and the inverse transform rebuild is fftshift(IFFT(hermitian(FFT(y))))
+// of the windowed, rotated, zero-padded frame y that the gather has just put into registers -- whose exact value is
+// fftshift(y) (X == 0 gives 0 on both paths; the .real of the inverse drops what is exactly 0 for a real y).  The direct
+// arm overlap-adds y itself: row q of the shifted frame is gathered row (q + P/2) mod P on the same lane and plane, the
+// ring add's combine is a plain sum, and the ordered section runs right after the gather (a hook of noise_fft), on the
+// registers the forward transform then reads -- no copy of the frame is kept.  The next frame's staging moves behind the
+// forward transform's last use of the exchange buffer.  Merge, handover and inverse transform are not instantiated; the
+// feature rows are the other arm's bit for bit, the waveform loses the two transforms' float32 error (~3e-7 of the peak).
+// N = 2048 / 1024 keep the transform: there the ring's lanes hold samples in kappa(lane) order, the gather's in lane order.
+constexpr bool kRtDirectBuilt = !MPX_COMP_DIT;   // (the DIT form gathers into bit-reversed registers)
+template <int P, bool CLS = false, int ST = kStoreRows, bool DIRECT = false>
 __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const float* __restrict__ sig,
                                                                        const long long* __restrict__ fpos,
                                                                        const int* __restrict__ fleft,
@@ -1324,6 +1367,7 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
                                                                        float* __restrict__ pcm, long long ld) {
     constexpr int M = 64 * P, N = 2 * M, HP = P / 2;
     static_assert(ST == kStoreRows || (P == 32 && CLS), "the line-aligned store forms exist for P = 32 with CLS only");
+    static_assert(!DIRECT || (P == 32 && kRtDirectBuilt), "the direct arm: N = 4096, gather in natural register order");
     constexpr bool kCls = roundtrip_prunes<P>(CLS);   // the forms that have pruned passes
     constexpr int NW = kCls ? kSupportNarrow : 0;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1350,10 +1394,30 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
         bool narrow = false;
         if constexpr (kCls) narrow = MPX_RT_FORCE_NARROW || (frame_support_class(g.L, g.LR - g.L, N) == NW);
 
-        float xr[P], xi[P];
+        float xr[P], xi[P];   // the merged spectrum, then the rebuilt frame (not under DIRECT)
+        FrameGeom g_next = g;
         {
             float no_r[HP], no_i[HP], nm_r[HP], nm_i[HP], nh_r, nh_i;
-            pair_analysis_spectrum<P, NW>(w, g, lane, wa_c, wa_s, no_r, no_i, nm_r, nm_i, nh_r, nh_i, narrow);
+            if constexpr (DIRECT) {
+                // the ordered section on the gathered frame itself (ROT: rows half a transform apart, the fftshift; natural
+                // register order), then the transform; the next frame is staged once the exchange buffer is idle
+                auto on_gathered = [&](float (&re)[P], float (&im)[P], auto narrow_c) __attribute__((always_inline)) {
+                    auto plain_sum = [](float o, float v, int) { return o + v; };
+                    auto all_rows = [](int) { return true; };
+                    pair_ordered_ola<P, true, NW, true>(w, cur, smem, runs, pm_rel, strips, pcm, re, im, lane, plain_sum,
+                                                        all_rows, decltype(narrow_c)::value);
+                };
+                auto on_exchanged = [&]() __attribute__((always_inline)) {
+                    if (nxt.valid) {
+                        g_next = frame_geom(sig, fpos[nxt.fi], fleft[nxt.fi], fright[nxt.fi], N);
+                        pair_stage_next<P>(w, g_next, lane);
+                    }
+                };
+                pair_analysis_spectrum<P, NW>(w, g, lane, wa_c, wa_s, no_r, no_i, nm_r, nm_i, nh_r, nh_i, narrow,
+                                              noise_fft_hook(on_gathered, on_exchanged));
+            } else {
+                pair_analysis_spectrum<P, NW>(w, g, lane, wa_c, wa_s, no_r, no_i, nm_r, nm_i, nh_r, nh_i, narrow);
+            }
             // ---- per bin pair q: lossless features (magphase.py:466-474; as k_analysis: X == 0 -> all three 0), their
             // stores, and the pair's step of the Hermitian merge -- feat_merge_paired's arithmetic on the values just
             // stored (X = mag (R + jI) / |R + jI|, magphase.py:1761-1766), pair by pair so that a pair's four inputs die
@@ -1473,13 +1537,24 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
                 // that feat_merge_paired spends on rebuilding it are not spent here.  The (-1)^k of the fftshift is a rotation
                 // of the inverse transform's output by half its length -- a renaming of registers in the overlap-add below --
                 // and the 0.5 / M of the inverse transform rides on the overlap-add's multiply-add: both exact.
-                const float x_r = no_r[q], p_r = nm_r[q];
-                float x_i = no_i[q], p_i = nm_i[q];
-                if (q == 0) {   // DC and Nyquist: imaginary parts dropped (Q5)
-                    x_i = lane0 ? 0.0f : x_i;
-                    p_i = lane0 ? 0.0f : p_i;
+                // (DIRECT: none of it -- the frame is in the ring already.  What stays is the merge's twiddle, formed and
+                // thrown away: it is the conjugate of the split's W_N^k and shares that one's products, and which product of
+                // a sum of two the compiler fuses into the multiply-add depends on how many uses each has -- without the
+                // merge's uses the split's twiddles, and with them the rows, come out with other last bits than the other
+                // arm's.  One multiply-add per bin pair.)
+                if constexpr (DIRECT) {
+                    const float cq = cos2p<P>(q), sq = sin2p<P>(q);
+                    const float wr = ws_c * cq - ws_s * sq, wi = ws_c * sq + ws_s * cq;
+                    asm volatile("" ::"v"(wr), "v"(wi));
+                } else {
+                    const float x_r = no_r[q], p_r = nm_r[q];
+                    float x_i = no_i[q], p_i = nm_i[q];
+                    if (q == 0) {   // DC and Nyquist: imaginary parts dropped (Q5)
+                        x_i = lane0 ? 0.0f : x_i;
+                        p_i = lane0 ? 0.0f : p_i;
+                    }
+                    merge_pair_step<P>(q, x_r, x_i, p_r, p_i, ws_c, ws_s, xr[q], xi[q], zr[q], zi[q]);
                 }
-                merge_pair_step<P>(q, x_r, x_i, p_r, p_i, ws_c, ws_s, xr[q], xi[q], zr[q], zi[q]);
             }
             float mH, aH, bH;
             feat(nh_r, nh_i, mH, aH, bH);
@@ -1498,20 +1573,24 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
                 st_mask(ihi + row_mir_base(lane, cu_i, M) + row_mir_off(HP), lane0 ? bH : hb, ~k_cu_i | 1ull);
             }
             // bin M/2 (lane 0): Z = 2 conj(X)
-            merge_handover<P>(zr, zi, 2.0f * nh_r, -2.0f * nh_i, xr, xi, lane);
+            if constexpr (!DIRECT) merge_handover<P>(zr, zi, 2.0f * nh_r, -2.0f * nh_i, xr, xi, lane);
         }
-        pair_inverse_fft_front<P>(w, xr, xi, lane);
-        if (nxt.valid) {
-            g = frame_geom(sig, fpos[nxt.fi], fleft[nxt.fi], fright[nxt.fi], N);
-            pair_stage_next<P>(w, g, lane);
+        if constexpr (DIRECT) {
+            g = g_next;
+        } else {
+            pair_inverse_fft_front<P>(w, xr, xi, lane);
+            if (nxt.valid) {
+                g = frame_geom(sig, fpos[nxt.fi], fleft[nxt.fi], fright[nxt.fi], N);
+                pair_stage_next<P>(w, g, lane);
+            }
+            if constexpr (kCls) pair_inverse_fft_back_class<P, NW>(xr, xi, narrow);
+            else pair_inverse_fft_back<P>(xr, xi);
+            constexpr float kScale = 0.5f / (float)M;   // the inverse transform's scale, on the overlap-add's multiply-add
+            auto plain_add = [](float o, float v, int) { return fmaf(v, kScale, o); };
+            auto all_rows = [](int) { return true; };
+            // ROT: rows taken half a transform apart, the fftshift
+            pair_ordered_ola<P, true, NW>(w, cur, smem, runs, pm_rel, strips, pcm, xr, xi, lane, plain_add, all_rows, narrow);
         }
-        if constexpr (kCls) pair_inverse_fft_back_class<P, NW>(xr, xi, narrow);
-        else pair_inverse_fft_back<P>(xr, xi);
-        constexpr float kScale = 0.5f / (float)M;   // the inverse transform's scale, on the overlap-add's multiply-add
-        auto plain_add = [](float o, float v, int) { return fmaf(v, kScale, o); };
-        auto all_rows = [](int) { return true; };
-        // ROT: rows taken half a transform apart, the fftshift
-        pair_ordered_ola<P, true, NW>(w, cur, smem, runs, pm_rel, strips, pcm, xr, xi, lane, plain_add, all_rows, narrow);
         cur = nxt;
 #ifdef MPX_PROBE_ENDTIME
         ++probe_frames;
@@ -1951,7 +2030,8 @@ int mpx_roundtrip_support_classes(int fft_len, const int32_t* frame_left, const 
 
 // The flags of mpx_roundtrip_lossless_ola_flags; the store bits change nothing about what a frame adds to the ring, so
 // mpx_roundtrip_frame_extents takes the same word and ignores them.
-static constexpr uint32_t kRtFlagsKnown = MPX_RT_FULL_SUPPORT | MPX_RT_STORE_ROWS | MPX_RT_STORE_NT;
+// Neither does MPX_RT_INVERSE_TRANSFORM: both arms add the same rows of a frame.
+static constexpr uint32_t kRtFlagsKnown = MPX_RT_FULL_SUPPORT | MPX_RT_STORE_ROWS | MPX_RT_STORE_NT | MPX_RT_INVERSE_TRANSFORM;
 
 // The row float every lane writes in every store of one plane of one frame, for a row of phase `phase`, from the helpers
 // the kernel's line-aligned forms take their bases and predicates from (mpx_common.hpp, "Row stores by line").
@@ -2032,6 +2112,17 @@ int mpx_roundtrip_lossless_ola_flags(void* stream, int fft_len, const void* tabl
     } while (0)
     // support classes (k_roundtrip_pair's CLS): only N = 4096 has a narrow class
     // store forms (k_roundtrip_pair's ST): only that instance has the line-aligned ones, every other ignores the bits
+    // arms (k_roundtrip_pair's DIRECT): only N = 4096 has the direct one, every other N ignores the bit
+    if constexpr (kRtDirectBuilt) {
+        if (P == 32 && !(flags & MPX_RT_INVERSE_TRANSFORM)) {
+            if (flags & MPX_RT_FULL_SUPPORT) MPX_LAUNCH_RT_K(32, (k_roundtrip_pair<32, false, kStoreRows, true>));
+            else if (flags & MPX_RT_STORE_ROWS) MPX_LAUNCH_RT_K(32, (k_roundtrip_pair<32, true, kStoreRows, true>));
+            else if (flags & MPX_RT_STORE_NT) MPX_LAUNCH_RT_K(32, (k_roundtrip_pair<32, true, kStoreLinesNT, true>));
+            else MPX_LAUNCH_RT_K(32, (k_roundtrip_pair<32, true, kStoreLines, true>));
+            MPX_HIP_CHECK(hipGetLastError());
+            return MPX_OK;
+        }
+    }
     if (P == 32 && !(flags & MPX_RT_FULL_SUPPORT)) {
         if (flags & MPX_RT_STORE_ROWS) MPX_LAUNCH_RT(32, true);
         else if (flags & MPX_RT_STORE_NT) MPX_LAUNCH_RT_K(32, (k_roundtrip_pair<32, true, kStoreLinesNT>));

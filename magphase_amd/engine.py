@@ -1540,19 +1540,24 @@ class Engine:
                     self.feat_ld(*(xs * 3)[:3]), self.feat_ld(*(outs * 3)[:3]))
         return out
 
-    def roundtrip_lossless_ola(self, fft_len, plan_a, plan_s, feats, strips, pcm_out, full_support=False, stores="lines_nt"):
+    def roundtrip_lossless_ola(self, fft_len, plan_a, plan_s, feats, strips, pcm_out, full_support=False, stores="lines_nt",
+                               inverse="direct"):
         """Copy synthesis in one launch (mpx_roundtrip_lossless_ola_flags): plan_a's frames are analysed, their feature rows
         written to feats = (mag, real, imag) and overlap-added by plan_s' runs (a LosslessSynthesisPlan built for this
         kernel's slots from plan_a's v_f0); ola_fixup(plan_s, strips, pcm_out) completes the run boundaries.
         full_support: every frame takes the full support class (MPX_RT_FULL_SUPPORT).  stores: "rows", "lines" or
-        "lines_nt" -- how the N = 4096 compact-support instance stores the feature rows (MPX_RT_STORE_*; the same values)."""
+        "lines_nt" -- how the N = 4096 compact-support instance stores the feature rows (MPX_RT_STORE_*; the same values).
+        inverse: "direct" -- at N = 4096 the windowed frame itself is overlap-added, which is what the merge and the inverse
+        transform of its own spectrum rebuild -- or "transform" (MPX_RT_INVERSE_TRANSFORM); every other N transforms."""
         mag, real, imag = feats
         if stores not in _lib.RT_STORE_FLAGS:
             raise ValueError("roundtrip_lossless_ola: stores must be one of %s" % ", ".join(sorted(_lib.RT_STORE_FLAGS)))
+        if inverse not in _lib.RT_INVERSE_FLAGS:
+            raise ValueError("roundtrip_lossless_ola: inverse must be one of %s" % ", ".join(sorted(_lib.RT_INVERSE_FLAGS)))
         self.launch("mpx_roundtrip_lossless_ola_flags", int(fft_len), self.tables(fft_len), plan_a.sig, plan_a.pos, plan_a.left,
                     plan_a.right, int(plan_a.total_frames), plan_s.runs, int(plan_s.n_runs), plan_s.slot_off,
                     plan_s.slot_runs, int(plan_s.n_slots), plan_s.pm_rel, mag, real, imag, strips, pcm_out,
-                    self.feat_ld(mag, real, imag), (1 if full_support else 0) | _lib.RT_STORE_FLAGS[stores])
+                    self.feat_ld(mag, real, imag), (1 if full_support else 0) | _lib.RT_STORE_FLAGS[stores] | _lib.RT_INVERSE_FLAGS[inverse])
         return pcm_out
 
     def griffin_lim_ola(self, fft_len, plan, target, sig_in, sig_out, strips, phase_out=None):

@@ -546,6 +546,7 @@ class LosslessRoundTripPlan:
     """
 
     DEFAULT_STORES = "lines_nt"   # DESIGN.md 3.3a, "Row stores by line": the fastest form of the A/B
+    DEFAULT_INVERSE = "direct"    # DESIGN.md 3.3a, "The windowed frame, added directly"
 
     def __init__(self, engine, utts, fft_len=None, frames_per_run=None, n_slots=None):
         # n_slots: overrides the engine's slot count (small tests)
@@ -565,6 +566,12 @@ class LosslessRoundTripPlan:
         self.stores = os.environ.get("MAGPHASE_RT_STORES", "") or self.DEFAULT_STORES
         if self.stores not in _lib.RT_STORE_FLAGS:
             raise ValueError("MAGPHASE_RT_STORES must be rows, lines or lines_nt, not %r" % self.stores)
+        # MAGPHASE_RT_INVERSE=direct|transform (read here, at plan build): whether the N = 4096 instances overlap-add the
+        # windowed frame they have just gathered, or rebuild it by Hermitian merge and inverse transform from its own
+        # spectrum -- the A/B switch; the rows are the same, every other N transforms and ignores it
+        self.inverse = os.environ.get("MAGPHASE_RT_INVERSE", "") or self.DEFAULT_INVERSE
+        if self.inverse not in _lib.RT_INVERSE_FLAGS:
+            raise ValueError("MAGPHASE_RT_INVERSE must be direct or transform, not %r" % self.inverse)
         if not utts:   # an empty batch: nothing to plan, run() returns empty tensors
             self.analysis = self.synthesis = self.seams = None
             self.seam_geometry = "dense" if self.full_seams else "extents"
@@ -651,7 +658,8 @@ class LosslessRoundTripPlan:
         if self.total_frames == 0:
             return feats, out
         _run_ola(e, lambda strips, out: e.roundtrip_lossless_ola(self.fft_len, a, s, feats, strips, out,
-                                                                 full_support=self.full_support, stores=self.stores),
+                                                                 full_support=self.full_support, stores=self.stores,
+                                                                 inverse=self.inverse),
                  self.fft_len, s, strips, out, self.total_out)
         return feats, out
 
