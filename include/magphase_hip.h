@@ -298,6 +298,23 @@ int mpx_synthesis_compressed_backward(void* stream, int fft_len, const void* tab
                                       int64_t ld_grad);
 
 /*
+ * Backward pass of mpx_synthesis_compressed_type2_ola (synthesis_from_compressed_type2, magphase.py:1452-1597): the
+ * arguments, the argument checks and the results of mpx_synthesis_compressed_backward, with the type-2 assembly at bins 0
+ * and N/2: the forward keeps Re S there (not |S|), so gS <- (Re gS, 0) at those two bins and no projection on S / |S|.
+ * per_v / ap_v / ap_u are the type-2 curves, inv_gain[f] is 1 / rms_noise of the frame's utterance (mpx_noise_rms), n_per
+ * the first bin from which per_v is zero.  grad_imag at bins 0 and N/2 is -(mag P / den) u_i u_r Re gS: in general not zero.
+ */
+int mpx_synthesis_compressed_type2_backward(void* stream, int fft_len, const void* tables, const float* grad_out,
+                                            int64_t total_out, const int64_t* grad_pos, const int32_t* grad_lo,
+                                            const int32_t* grad_hi, int64_t n_frames, const float* mag, const float* real,
+                                            const float* imag, int64_t ld, const float* noise, const int64_t* noise_pos,
+                                            const int32_t* noise_left, const int32_t* noise_right,
+                                            const int32_t* noise_wtype, const int32_t* voiced, const float* inv_gain,
+                                            const int32_t* win_left, const int32_t* win_right, const float* per_v,
+                                            const float* ap_v, const float* ap_u, int32_t n_per, float* grad_mag,
+                                            float* grad_real, float* grad_imag, int64_t ld_grad);
+
+/*
  * Adjoint of the row interpolation out[f] = fma(x[row1[f]] - x[row0[f]], row_t[f], x[row0[f]]):
  *     dst_X[r] = sum over f with row0[f] == r of (1 - row_t[f]) src_X[f] + sum over f with row1[f] == r of row_t[f] src_X[f]
  * for r < n_rows (a frame with row0 == row1 == r weighs exactly 1).  ranges: int32 [n_rows x 4] = (a0, a1, b0, b1) per

@@ -46,6 +46,8 @@ PROTOTYPES = {
     "mpx_synthesis_lossless_backward": (i32, [vp, i32, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64] + [vp] * 6 + [i64]),
     "mpx_synthesis_compressed_backward": (i32, [vp, i32, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64] + [vp] * 12
                                           + [i32, vp, vp, vp, i64]),
+    "mpx_synthesis_compressed_type2_backward": (i32, [vp, i32, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64] + [vp] * 12
+                                                + [i32, vp, vp, vp, i64]),
     "mpx_rows_lerp_adjoint": (i32, [vp, i32, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, i64]),
     "mpx_analysis_lossless_backward": (i32, [vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, i64,
                                              vp, i64]),

@@ -35,7 +35,14 @@ differentiable: v_lf0 (it only produces integer pitch marks and the voicing flag
 a phase bin is a == b == 0 its gradient is m P gS (k_synth_lossless_bwd's convention).  A plan that stores its noise
 spectra (MAGPHASE_NOISE_SPECTRA=store) is differentiated the same way: the backward pass recomputes them.
 
-No double backward.  The type-2 synthesis, the compressed synthesis with per_phase_type 'min_phase' / 'linear', with a
+Type-2 synthesis (section 3.3l): a fifth Function around the unchanged forward of synthesis_from_compressed_type2_batch
+(Type2SynthesisPlan.run() and the elliptic output high-pass), at the variable rate and at any const_rate_ms, with the
+gradients computed by the same run_backward: the elliptic filter run backwards in time, k_synth_comp_bwd's type-2 arm
+(bins 0 and N/2 keep Re S, a linear map: the real end-bin gradient passes straight through), the type-2 phase unwarp
+matrix and curves as the plan holds them.  The one noise gain per utterance does not depend on the features: it is held
+constant and the backward pass is exact.  Not differentiable: v_lf0, fs, hf_slope_coeff, the noise and its gain.
+
+No double backward.  The compressed synthesis with per_phase_type 'min_phase' / 'linear', with a
 post-filter, with pcm16_norm or with prepared=, and the constant-rate lossless and type-2 analysis, have no backward pass.
 """
 import torch
@@ -211,3 +218,47 @@ def synthesize_compressed(plan, b_out_hpf, utts):
     [total_out] waveform buffer (with grad_fn)."""
     mats = [x for u in utts for x in u[:3]]
     return _CompressedSynthesis.apply(plan, bool(b_out_hpf), len(utts), *mats)
+
+
+class _Type2Synthesis(torch.autograd.Function):
+    """forward(plan, n_utts, *mats): plan = a Type2SynthesisPlan built from the utterances whose coefficient matrices are
+    mats, utterance-major as for _CompressedSynthesis; plan.run() and Engine.output_hpf(design='ellip60') are the forward,
+    plan.adjoint_hpf(design='ellip60') and plan.run_backward the backward.  Output: the ONE float64 [total_out] waveform
+    buffer; the per-utterance signals are views of it."""
+
+    @staticmethod
+    def forward(ctx, plan, n_utts, *mats):
+        pcm = plan.engine.output_hpf(plan.run(), plan.out_off_host, plan.fs, design="ellip60")
+        ctx.plan = plan
+        ctx.rows = [int(mats[3 * u].shape[0]) for u in range(n_utts)]
+        ctx.like = [(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else None for m in mats]
+        return pcm
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        plan = ctx.plan
+        n_head = 2   # plan, n_utts
+        need_in = ctx.needs_input_grad[n_head:]
+        need = tuple(any(need_in[k::3]) for k in range(3))
+        with torch.cuda.device(grad_out.device):
+            g = plan.run_backward(plan.adjoint_hpf(grad_out, design="ellip60").contiguous(), need=need)
+        out, a = [], 0
+        for u, n in enumerate(ctx.rows):
+            for k in range(3):
+                like = ctx.like[3 * u + k]
+                if like is None or not need_in[3 * u + k]:
+                    out.append(None)
+                else:
+                    out.append(g[k][a:a + n].to(like[0]).reshape(like[1]))
+            a += n
+        return (None,) * n_head + tuple(out)
+
+
+def synthesize_compressed_type2(plan, utts):
+    """plan.run() of a Type2SynthesisPlan and the elliptic output high-pass, differentiable with respect to the coefficient
+    matrices in utts = [(m_mag_mel_log, m_real_mel, m_imag_mel, v_lf0)] that are tensors requiring grad.  Returns the
+    float64 [total_out] waveform buffer (with grad_fn)."""
+    plan._check_differentiable()     # what has no backward pass says so before the forward is launched
+    mats = [x for u in utts for x in u[:3]]
+    return _Type2Synthesis.apply(plan, len(utts), *mats)

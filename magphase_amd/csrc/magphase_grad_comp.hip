@@ -1,6 +1,7 @@
 // magphase_grad_comp.hip -- backward pass of the compressed synthesis' frame kernel.
 //
-//   k_synth_comp_bwd<P>  one wavefront per frame, persistent waves (grid-stride over frames), the shape of
+//   k_synth_comp_bwd<P, T2>  (T2: the type-2 synthesis, section 3.3l -- below)
+//                        one wavefront per frame, persistent waves (grid-stride over frames), the shape of
 //                        k_synth_lossless_bwd (magphase_grad.hip).  Per frame, two real transforms of N points, each as one
 //                        64*P-point complex wave FFT plus the real split:
 //                          1. Ns, the spectrum of the frame's windowed, rotated noise -- the forward's own inputs (noise,
@@ -23,6 +24,9 @@
 // overlap-add are linear: gS_k = (c_k / N) FFT_N(ifftshift(w_f g))_k, c_k = 2 inside and 1 at the two ends; at the ends the
 // real gradient Re gS goes along S / |S| (0 where S == 0).  Then
 //   grad m = Re(conj(T) gS),   grad (a, b) = (m P / den) (gS - u Re(conj(u) gS))      (den == 0: u = 0, m P gS: bwd_bin)
+// T2 (the T2 arm of k_synth_comp_pair; mpx_synthesis_compressed_type2_backward): S_0 <- Re S_0, S_M <- Re S_M, a linear
+// map: the real end-bin gradient goes straight through, gS_end = (Re gS, 0), no projection on S / |S|; everything after it
+// is the same (at the ends grad b = -(m P / den) u_i u_r Re gS, in general not zero).
 #include "mpx_common.hpp"
 
 namespace mpx {
@@ -112,18 +116,22 @@ __device__ __forceinline__ void comp_bwd_noise_fft(const FrameGeom& g, int wtype
 // One bin of the epilogue.  (m, a, b): the frame's unwarped features, cpv = P_k (0 in unvoiced frames and from n_per on),
 // cap = A_k ig, (nr, ni) = Ns_k, (gr, gi) = gS_k; ends: bins 0 and N/2, where the forward keeps |S| and gi comes in as 0.
 // rsq(max(s, tiny)) multiplies a == b == 0 when s == 0: u = 0, and the phase gradient is m P gS (bwd_bin's convention).
+// T2: the forward keeps Re S at the ends -- (gr, 0) is the gradient with respect to S as it comes in.
+template <bool T2 = false>
 __device__ __forceinline__ void comp_bwd_bin(float m, float a, float b, float cpv, float cap, float nr, float ni, float gr,
                                              float gi, bool ends, float& om, float& oa, float& ob) {
     const float s = a * a + b * b;
     const float r = __builtin_amdgcn_rsqf(fmaxf(s, 1.0e-37f));
     const float ur = a * r, ui = b * r;
     const float tr = fmaf(nr, cap, cpv * ur), ti = fmaf(ni, cap, cpv * ui);
-    if (ends) {   // S = m T -> |S|: the (real) gradient goes along S / |S| = sign(m) T / |T|, 0 where S == 0
-        const float t2 = tr * tr + ti * ti;
-        const float sg = (m > 0.0f) ? 1.0f : ((m < 0.0f) ? -1.0f : 0.0f);
-        const float inv = (t2 >= 1.0e-37f) ? sg * __builtin_amdgcn_rsqf(t2) : 0.0f;
-        gi = gr * ti * inv;
-        gr = gr * tr * inv;
+    if constexpr (!T2) {
+        if (ends) {   // S = m T -> |S|: the (real) gradient goes along S / |S| = sign(m) T / |T|, 0 where S == 0
+            const float t2 = tr * tr + ti * ti;
+            const float sg = (m > 0.0f) ? 1.0f : ((m < 0.0f) ? -1.0f : 0.0f);
+            const float inv = (t2 >= 1.0e-37f) ? sg * __builtin_amdgcn_rsqf(t2) : 0.0f;
+            gi = gr * ti * inv;
+            gr = gr * tr * inv;
+        }
     }
     om = tr * gr + ti * gi;
     const float d = ur * gr + ui * gi;
@@ -172,7 +180,7 @@ constexpr int comp_bwd_waves() { return P == 32 ? 4 : kWavesPerBlock; }
 template <int P>
 constexpr size_t lds_bytes_comp_bwd() { return sizeof(float) * (size_t)(tw_floats<P>() + comp_bwd_waves<P>() * P * kXStride); }
 
-template <int P>
+template <int P, bool T2 = false>
 __global__ __launch_bounds__(64 * comp_bwd_waves<P>()) void k_synth_comp_bwd(CompBwdArgs A) {
     constexpr int M = 64 * P, N = 2 * M, LB = ilog2(P), HP = P / 2;
     constexpr int kWaves = comp_bwd_waves<P>(), kThr = 64 * kWaves;
@@ -340,7 +348,7 @@ __global__ __launch_bounds__(64 * comp_bwd_waves<P>()) void k_synth_comp_bwd(Com
                 feat(k_mir, fmq, faq, fbq, fpq, fcq);
                 {
                     float cm, cr, ci;
-                    comp_bwd_bin(fm, fa, fb, fp, fc, no_r[q], no_i[q], (er + tr) * sc, (ei + ti) * sci, edge, cm, cr, ci);
+                    comp_bwd_bin<T2>(fm, fa, fb, fp, fc, no_r[q], no_i[q], (er + tr) * sc, (ei + ti) * sci, edge, cm, cr, ci);
                     if (A.omag) row_m[k_own] = cm;
                     if (64 * q < n_phase) {   // wave-uniform: the whole 64-bin block lies below n_phase
                         if (A.oreal) row_r[k_own] = cr;
@@ -349,7 +357,7 @@ __global__ __launch_bounds__(64 * comp_bwd_waves<P>()) void k_synth_comp_bwd(Com
                 }
                 {
                     float cm, cr, ci;
-                    comp_bwd_bin(fmq, faq, fbq, fpq, fcq, nm_r[q], nm_i[q], (er - tr) * sc, (ti - ei) * sci, edge, cm, cr, ci);
+                    comp_bwd_bin<T2>(fmq, faq, fbq, fpq, fcq, nm_r[q], nm_i[q], (er - tr) * sc, (ti - ei) * sci, edge, cm, cr, ci);
                     if (q == 0) {
                         if (lane0) {                      // bin M
                             if (A.omag) row_m[M] = cm;
@@ -375,7 +383,7 @@ __global__ __launch_bounds__(64 * comp_bwd_waves<P>()) void k_synth_comp_bwd(Com
             // bin M/2 + kappa (in range; only lane 0's result is stored)
             float fm, fa, fb, fp, fc, cm, cr, ci;
             feat(M / 2 + kap, fm, fa, fb, fp, fc);
-            comp_bwd_bin(fm, fa, fb, fp, fc, nh_r, nh_i, re[1] * kS2, -im[1] * kS2, false, cm, cr, ci);
+            comp_bwd_bin<T2>(fm, fa, fb, fp, fc, nh_r, nh_i, re[1] * kS2, -im[1] * kS2, false, cm, cr, ci);
             if (A.omag) row_m[hoff - 64 * (HP - 1)] = lane0 ? cm : hm;
             if (M / 2 < n_phase) {
                 if (A.oreal) row_r[hoff - 64 * (HP - 1)] = lane0 ? cr : hr;
@@ -389,6 +397,52 @@ __global__ __launch_bounds__(64 * comp_bwd_waves<P>()) void k_synth_comp_bwd(Com
 
 using namespace mpx;
 
+// T2: the type-2 arm of k_synth_comp_bwd (mpx_synthesis_compressed_type2_backward); who: the entry's name for the messages
+template <bool T2>
+static int synthesis_compressed_backward_impl(const char* who, void* stream, int fft_len, const void* tables,
+                                              const float* grad_out, int64_t total_out, const int64_t* grad_pos,
+                                              const int32_t* grad_lo, const int32_t* grad_hi, int64_t n_frames,
+                                              const float* mag, const float* real, const float* imag, int64_t ld,
+                                              const float* noise, const int64_t* noise_pos, const int32_t* noise_left,
+                                              const int32_t* noise_right, const int32_t* noise_wtype, const int32_t* voiced,
+                                              const float* inv_gain, const int32_t* win_left, const int32_t* win_right,
+                                              const float* per_v, const float* ap_v, const float* ap_u, int32_t n_per,
+                                              float* grad_mag, float* grad_real, float* grad_imag, int64_t ld_grad) {
+    const int P = p_of(fft_len);
+    if (!P) return fail(MPX_ERR_ARG, "%s: fft_len must be 1024, 2048 or 4096", who);
+    const int H = fft_len / 2 + 1;
+    if (n_frames < 0 || total_out < 0) return fail(MPX_ERR_ARG, "%s: negative count", who);
+    if (ld < H || ld_grad < H) return fail(MPX_ERR_ARG, "%s: ld < fft_len/2 + 1", who);
+    if (n_per < 0 || n_per > H) return fail(MPX_ERR_ARG, "%s: n_per outside [0, fft_len/2 + 1]", who);
+    if (n_frames == 0) return MPX_OK;
+    if (!grad_mag && !grad_real && !grad_imag) return MPX_OK;   // nothing asked for
+    if (!tables || !grad_pos || !grad_lo || !grad_hi || !mag || !real || !imag || !noise || !noise_pos || !noise_left ||
+        !noise_right || !noise_wtype || !voiced || !inv_gain || !win_left || !win_right || !per_v || !ap_v || !ap_u ||
+        (total_out > 0 && !grad_out))
+        return fail(MPX_ERR_ARG, "%s: null pointer", who);
+    CompBwdArgs a;
+    a.gy = grad_out, a.total_out = (long long)total_out, a.gpos = (const long long*)grad_pos, a.glo = grad_lo, a.ghi = grad_hi;
+    a.nframes = (long long)n_frames, a.tw = (const float*)tables, a.mag = mag, a.real = real, a.imag = imag;
+    a.ld = (long long)ld, a.noise = noise, a.npos = (const long long*)noise_pos, a.nleft = noise_left, a.nright = noise_right;
+    a.wtype = noise_wtype, a.voiced = voiced, a.inv_gain = inv_gain, a.win_l = win_left, a.win_r = win_right;
+    a.per_v = per_v, a.ap_v = ap_v, a.ap_u = ap_u, a.n_per = n_per;
+    a.n_phase = min((n_per + 63) / 64 * 64, H);
+    a.omag = grad_mag, a.oreal = grad_real, a.oimag = grad_imag, a.ldg = (long long)ld_grad;
+    hipStream_t s = (hipStream_t)stream;
+#define MPX_LAUNCH_CBWD(PP)                                                                              \
+    do {                                                                                                 \
+        const dim3 grid(grid_for(n_frames, comp_bwd_waves<PP>())), block(64 * comp_bwd_waves<PP>());     \
+        if (int rc = set_lds((k_synth_comp_bwd<PP, T2>), lds_bytes_comp_bwd<PP>())) return rc;           \
+        hipLaunchKernelGGL((k_synth_comp_bwd<PP, T2>), grid, block, lds_bytes_comp_bwd<PP>(), s, a);     \
+    } while (0)
+    if (P == 32) MPX_LAUNCH_CBWD(32);
+    else if (P == 16) MPX_LAUNCH_CBWD(16);
+    else MPX_LAUNCH_CBWD(8);
+#undef MPX_LAUNCH_CBWD
+    MPX_HIP_CHECK(hipGetLastError());
+    return MPX_OK;
+}
+
 extern "C" {
 
 int mpx_synthesis_compressed_backward(void* stream, int fft_len, const void* tables, const float* grad_out,
@@ -400,39 +454,25 @@ int mpx_synthesis_compressed_backward(void* stream, int fft_len, const void* tab
                                       const int32_t* win_right, const float* per_v, const float* ap_v, const float* ap_u,
                                       int32_t n_per, float* grad_mag, float* grad_real, float* grad_imag,
                                       int64_t ld_grad) {
-    const int P = p_of(fft_len);
-    if (!P) return fail(MPX_ERR_ARG, "mpx_synthesis_compressed_backward: fft_len must be 1024, 2048 or 4096%s");
-    const int H = fft_len / 2 + 1;
-    if (n_frames < 0 || total_out < 0) return fail(MPX_ERR_ARG, "mpx_synthesis_compressed_backward: negative count%s");
-    if (ld < H || ld_grad < H) return fail(MPX_ERR_ARG, "mpx_synthesis_compressed_backward: ld < fft_len/2 + 1%s");
-    if (n_per < 0 || n_per > H) return fail(MPX_ERR_ARG, "mpx_synthesis_compressed_backward: n_per outside [0, fft_len/2 + 1]%s");
-    if (n_frames == 0) return MPX_OK;
-    if (!grad_mag && !grad_real && !grad_imag) return MPX_OK;   // nothing asked for
-    if (!tables || !grad_pos || !grad_lo || !grad_hi || !mag || !real || !imag || !noise || !noise_pos || !noise_left ||
-        !noise_right || !noise_wtype || !voiced || !inv_gain || !win_left || !win_right || !per_v || !ap_v || !ap_u ||
-        (total_out > 0 && !grad_out))
-        return fail(MPX_ERR_ARG, "mpx_synthesis_compressed_backward: null pointer%s");
-    CompBwdArgs a;
-    a.gy = grad_out, a.total_out = (long long)total_out, a.gpos = (const long long*)grad_pos, a.glo = grad_lo, a.ghi = grad_hi;
-    a.nframes = (long long)n_frames, a.tw = (const float*)tables, a.mag = mag, a.real = real, a.imag = imag;
-    a.ld = (long long)ld, a.noise = noise, a.npos = (const long long*)noise_pos, a.nleft = noise_left, a.nright = noise_right;
-    a.wtype = noise_wtype, a.voiced = voiced, a.inv_gain = inv_gain, a.win_l = win_left, a.win_r = win_right;
-    a.per_v = per_v, a.ap_v = ap_v, a.ap_u = ap_u, a.n_per = n_per;
-    a.n_phase = min((n_per + 63) / 64 * 64, H);
-    a.omag = grad_mag, a.oreal = grad_real, a.oimag = grad_imag, a.ldg = (long long)ld_grad;
-    hipStream_t s = (hipStream_t)stream;
-#define MPX_LAUNCH_CBWD(PP)                                                                            \
-    do {                                                                                               \
-        const dim3 grid(grid_for(n_frames, comp_bwd_waves<PP>())), block(64 * comp_bwd_waves<PP>());   \
-        if (int rc = set_lds((k_synth_comp_bwd<PP>), lds_bytes_comp_bwd<PP>())) return rc;             \
-        hipLaunchKernelGGL((k_synth_comp_bwd<PP>), grid, block, lds_bytes_comp_bwd<PP>(), s, a);       \
-    } while (0)
-    if (P == 32) MPX_LAUNCH_CBWD(32);
-    else if (P == 16) MPX_LAUNCH_CBWD(16);
-    else MPX_LAUNCH_CBWD(8);
-#undef MPX_LAUNCH_CBWD
-    MPX_HIP_CHECK(hipGetLastError());
-    return MPX_OK;
+    return synthesis_compressed_backward_impl<false>(
+        "mpx_synthesis_compressed_backward", stream, fft_len, tables, grad_out, total_out, grad_pos, grad_lo, grad_hi,
+        n_frames, mag, real, imag, ld, noise, noise_pos, noise_left, noise_right, noise_wtype, voiced, inv_gain, win_left,
+        win_right, per_v, ap_v, ap_u, n_per, grad_mag, grad_real, grad_imag, ld_grad);
+}
+
+int mpx_synthesis_compressed_type2_backward(void* stream, int fft_len, const void* tables, const float* grad_out,
+                                            int64_t total_out, const int64_t* grad_pos, const int32_t* grad_lo,
+                                            const int32_t* grad_hi, int64_t n_frames, const float* mag, const float* real,
+                                            const float* imag, int64_t ld, const float* noise, const int64_t* noise_pos,
+                                            const int32_t* noise_left, const int32_t* noise_right,
+                                            const int32_t* noise_wtype, const int32_t* voiced, const float* inv_gain,
+                                            const int32_t* win_left, const int32_t* win_right, const float* per_v,
+                                            const float* ap_v, const float* ap_u, int32_t n_per, float* grad_mag,
+                                            float* grad_real, float* grad_imag, int64_t ld_grad) {
+    return synthesis_compressed_backward_impl<true>(
+        "mpx_synthesis_compressed_type2_backward", stream, fft_len, tables, grad_out, total_out, grad_pos, grad_lo, grad_hi,
+        n_frames, mag, real, imag, ld, noise, noise_pos, noise_left, noise_right, noise_wtype, voiced, inv_gain, win_left,
+        win_right, per_v, ap_v, ap_u, n_per, grad_mag, grad_real, grad_imag, ld_grad);
 }
 
 }  // extern "C"

@@ -24,7 +24,8 @@ from .hostmath import check_const_rate_ms
 from .hostplan import plan_const_rate_synthesis
 from .plans import (CompressedAnalysisPlan, CompressedSynthesisPlan, GriffinLimPlan, LosslessAnalysisPlan,
                     LosslessConstRateAnalysisPlan, LosslessConstRateSynthesisPlan, LosslessRoundTripPlan,
-                    LosslessSynthesisPlan, Type2AnalysisPlan, Type2CompressedAnalysisPlan, Type2SynthesisPlan)
+                    LosslessSynthesisPlan, Type2AnalysisPlan, Type2CompressedAnalysisPlan, Type2SynthesisPlan,
+                    check_type2_grad_dims)
 
 _epoch_provider = None
 
@@ -1261,21 +1262,39 @@ def synthesis_from_compressed_type2_batch(utts, fs, fft_len=None, hf_slope_coeff
     the engine's device; with return_device the signals are float64 (int16 with pcm16_norm) views of the device PCM
     buffer.  Device lf0 vectors come to the host first (one copy), so every argument check, the finite-lf0 check
     included, still runs before the first kernel.  Launches go to torch's current stream of the engine's device.
+    Autograd: with return_device, grad mode on and a device m_mag_mel_log / m_real_mel / m_imag_mel that requires grad,
+    the float64 signals carry a grad_fn and tensor.backward() reaches the three coefficient matrices, in each one's own
+    dtype and shape (magphase_amd/autograd.py; the forward launches and their samples are the
+    same).  At the variable rate and at any const_rate_ms, for any hf_slope_coeff, either b_voi_ap_win, either noise_mode
+    or an explicit noise.  phase_dim > mag_dim: the gradient columns from mag_dim on are zeros (the forward does not read
+    them).  Not differentiable: v_lf0, fs, hf_slope_coeff, the noise and its gain (one per utterance, the rms of the noise
+    spectra alone: the backward pass is exact with it held constant).  NotImplementedError, naming the argument, for
+    pcm16_norm other than False and for more than 64 columns in a matrix.  No double backward.
     """
     const_rate_ms = _type2_rate(const_rate_ms)
     utts = list(utts)
     if not utts:
         return []
+    want_grad = _compressed_synthesis_wants_grad(utts, return_device)
+    if want_grad and pcm16_norm is not False:   # what has no backward pass says so before anything is built
+        raise NotImplementedError("pcm16_norm=%r (int16 output) has no backward pass" % (pcm16_norm,))
     utts, on_dev = _tensor_inputs(utts, _SYN_NAMES, lf0_at=3)
     if on_dev:
         engine = engine or get_engine()
         if all(len(u) == 4 for u in utts):   # (device lf0 comes down for the checks below; a malformed tuple raises there)
             utts = [tuple(u[:3]) + (l,) for u, l in zip(utts, engine.lf0_to_host([u[3] for u in utts]))]
     _type2_synthesis_check(utts, fs, fft_len, hf_slope_coeff)
+    if want_grad:
+        check_type2_grad_dims(np.shape(utts[0][0])[1], np.shape(utts[0][1])[1])
     engine = engine or get_engine()
     plan = Type2SynthesisPlan(engine, utts, fs, fft_len=fft_len, hf_slope_coeff=hf_slope_coeff,
                               b_voi_ap_win=b_voi_ap_win, const_rate_ms=const_rate_ms, noise=noise,
                               noise_mode=noise_mode, noise_seeds=noise_seeds, defer_rng=defer_rng)
+    if want_grad:   # the same launches inside a torch.autograd.Function (magphase_amd/autograd.py)
+        from .autograd import synthesize_compressed_type2
+
+        pcm_dev = synthesize_compressed_type2(plan, utts)
+        return [pcm_dev[int(plan.out_off_host[u]):int(plan.out_off_host[u + 1])] for u in range(len(utts))]
     pcm_dev = engine.output_hpf(plan.run(), plan.out_off_host, fs, design="ellip60")   # magphase.py:1599-1604
     if return_device:
         if pcm16_norm is not False:

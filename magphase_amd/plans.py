@@ -855,6 +855,7 @@ class CompressedSynthesisPlan:
     _native_planner = True      # Engine.prepare_synthesis / hostplan.plan_synthesis serve this plan's frame tables
     _n_per_key = "n_per"
     _ola_entry = "mpx_synthesis_compressed_ola"
+    _bwd_entry = "mpx_synthesis_compressed_backward"
 
     def __init__(self, engine, utts, fs, fft_len=None, b_voi_ap_win=True, b_const_rate=False, alpha_phase=None,
                  noise=None, frames_per_run=None, per_phase_type="magphase", post_filter=False, b_fbank_mel=False,
@@ -1318,21 +1319,22 @@ class CompressedSynthesisPlan:
         return b
 
     def _check_differentiable(self):
-        if type(self)._ola_entry != "mpx_synthesis_compressed_ola":
-            raise NotImplementedError("the type-2 synthesis has no backward pass")
+        if not self._bwd_entry:
+            raise NotImplementedError("%s has no backward pass" % type(self).__name__)
         if self.per_phase_type != "magphase":
             raise NotImplementedError("per_phase_type=%r has no backward pass (only 'magphase')" % (self.per_phase_type,))
         if self.apply_post_filter:
             raise NotImplementedError("b_post_filter has no backward pass")
 
-    def adjoint_hpf(self, grad, fs=None):
+    def adjoint_hpf(self, grad, fs=None, design="butter40"):
         """The adjoint of the output high-pass (Engine.output_hpf: a causal LTI filter per utterance, from a zero state) is
         the same filter run backwards in time: grad [total_out] -> float32, every utterance reversed, filtered, reversed
-        again, float32."""
+        again, float32.  design: Engine.output_hpf's ('ellip60': the type-2 synthesis' output filter)."""
         torch = _torch()
         rev = self.backward_tables()["rev"]
         g = grad.to(torch.float32).reshape(-1)
-        g = self.engine.output_hpf(g.index_select(0, rev).contiguous(), self.out_off_host, self.fs if fs is None else fs)
+        g = self.engine.output_hpf(g.index_select(0, rev).contiguous(), self.out_off_host, self.fs if fs is None else fs,
+                                   design=design)
         return g.index_select(0, rev).to(torch.float32)
 
     def run_backward(self, grad_pcm, need=(True, True, True), mark=None):
@@ -1367,7 +1369,7 @@ class CompressedSynthesisPlan:
         mark("start")
         # per-frame gradient rows, allocated apart from spec (whose rows the kernel reads)
         g_m, g_a, g_b = (e.empty((F, ld))[:, :H] if n else None for n in need)
-        e.launch("mpx_synthesis_compressed_backward", N, e.tables(N), grad_pcm, self.total_out, t["pos"], t["lo"], t["hi"],
+        e.launch(self._bwd_entry, N, e.tables(N), grad_pcm, self.total_out, t["pos"], t["lo"], t["hi"],
                  F, mag, real, imag, ld, self.noise, self.npos, self.nleft, self.nright, self.wtype, self.voiced,
                  buf["inv_gain"], self.win_l, self.win_r, self.per_v, self.ap_v, self.ap_u, n_per, g_m, g_a, g_b, ld)
         mark("k_synth_comp_bwd")
@@ -1394,6 +1396,15 @@ class CompressedSynthesisPlan:
         return o_m, o_a, o_b
 
 
+def check_type2_grad_dims(mag_dim, phase_dim):
+    """The backward pass of the type-2 synthesis goes through k_mel_unwarp_bwd, which produces at most 64 coefficient
+    columns per job."""
+    for name, d in (("m_mag_mel_log (mag_dim)", mag_dim), ("m_real_mel / m_imag_mel (phase_dim)", phase_dim)):
+        if int(d) > 64:
+            raise NotImplementedError("%s has %d columns: the backward pass of the type-2 synthesis takes at most 64"
+                                      % (name, int(d)))
+
+
 class Type2SynthesisPlan(CompressedSynthesisPlan):
     """
     synthesis_from_compressed_type2 (magphase.py:1452-1597, the output filter excluded) for a batch of utterances: the
@@ -1410,6 +1421,7 @@ class Type2SynthesisPlan(CompressedSynthesisPlan):
     """
     _n_per_key = "n_per_t2"
     _ola_entry = "mpx_synthesis_compressed_type2_ola"
+    _bwd_entry = "mpx_synthesis_compressed_type2_backward"
 
     def __init__(self, engine, utts, fs, fft_len=None, hf_slope_coeff=1.0, b_voi_ap_win=True, const_rate_ms=-1.0,
                  noise=None, frames_per_run=None, noise_mode="reference", noise_seeds=None, defer_rng=False):
@@ -1439,6 +1451,12 @@ class Type2SynthesisPlan(CompressedSynthesisPlan):
         self.per_v, self.ap_v, self.ap_u = (
             e.constant(("bin_curve_t2", k, int(fs), N, self.hf_slope_coeff), lambda k=k: self._bin_curves_host()[k])
             for k in range(3))
+
+    def _check_differentiable(self):
+        """run_backward serves this plan as it stands: u_phase and n_per are the type-2 ones, the
+        gain is constant.  What k_mel_unwarp_bwd cannot take is said here, before any launch."""
+        super()._check_differentiable()
+        check_type2_grad_dims(self.mag_dim, self.phase_dim)
 
     @property
     def gains(self):
