@@ -780,6 +780,24 @@ int mpx_true_envelope(void* stream, int fft_len, const void* tables, const float
                       int64_t ld_out, int32_t* iters, const int32_t* forced_iters, int32_t* ticket);
 
 /*
+ * Backward pass of the true envelope, one wavefront per frame: the exact adjoint of the forward pass as the device decides
+ * it.  in / in_type / weights as the forward call took them; iters (required): int32 [n_frames], the passes the forward
+ * made.  Per row the K = clamp(iters[f], 1, max_iters) passes are recomputed, the decisions of the max updates
+ * (m_k[b] = sm_k[b] > v_k[b], k < K; a tie keeps v) are kept on chip, and the K passes are run in reverse on grad_out
+ * ([n_frames x H], the gradient with respect to out): with S one smoothing pass, S^T g = D^-1 S (D g), D = diag(2, 1, ...,
+ * 1, 2).  grad_in ([n_frames x H]): the gradient with respect to in; every element is written exactly once, no atomics.
+ * The stop test is not differentiated.  A row the forward wrote as NaN gets an all-zero gradient row.  max_iters <= 100
+ * (the capacity of the on-chip decision history).  Optional outputs, for tests: decisions, int32 [n_frames x max_iters x
+ * ceil(H / 32)]: bit b % 32 of word b / 32 of pass k's words (k = 1 .. max_iters, pass-major) is m_k[b]; the words of the
+ * passes that decide nothing (k >= K) are 0.  env_out ([n_frames x H], row pitch ld_env_out): the recomputed out rows.
+ * ticket as in mpx_true_envelope.
+ */
+int mpx_true_envelope_backward(void* stream, int fft_len, const void* tables, const float* weights, const float* in,
+                               int64_t ld_in, int64_t n_frames, int32_t in_type, int32_t max_iters, const int32_t* iters,
+                               const float* grad_out, int64_t ld_grad_out, float* grad_in, int64_t ld_grad_in,
+                               int32_t* decisions, float* env_out, int64_t ld_env_out, int32_t* ticket);
+
+/*
  * Per-frame gain of the type-2 analysis (analysis_with_del_comp_from_pm_type2, magphase.py:236-242), one wavefront per
  * frame, float64.  Frames as mpx_analysis_frames takes them (frame_pos / frame_left / frame_right into sig).  voi: float32
  * [n_frames], the epoch's voicing.  gain[f] = (voi[f] == 1) ? max |x| over the first fft_len/2 + 1 samples of the

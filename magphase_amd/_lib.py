@@ -106,6 +106,7 @@ PROTOTYPES = {
     "mpx_phase_grad_mask": (i32, [vp, i64, i32] + [vp] * 7),
     "mpx_min_phase": (i32, [vp, i32] + [vp] * 5 + [i64, vp, vp, vp, i64]),
     "mpx_true_envelope": (i32, [vp, i32, vp, vp, vp, i64, i64, i32, f64, i32, vp, i64, vp, vp, vp]),
+    "mpx_true_envelope_backward": (i32, [vp, i32, vp, vp, vp, i64, i64, i32, i32, vp, vp, i64, vp, i64, vp, vp, i64, vp]),
     "mpx_frame_gain": (i32, [vp, i32] + [vp] * 5 + [i64, vp, i32]),
     "mpx_noise_gains": (i32, [vp] * 4 + [i32, i32, vp, vp]),
     "mpx_noise_power": (i32, [vp, i32] + [vp] * 5 + [i64, vp]),

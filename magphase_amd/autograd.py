@@ -1,5 +1,6 @@
 """
-Autograd for the lossless features, both directions, and for the compressed features, both directions.  Imported lazily by
+Autograd for the lossless features, both directions, for the compressed features, both directions, for the type-2 features,
+both directions, and for the true envelope.  Imported lazily by
 magphase.py, and only when a device tensor that requires grad goes in with return_device=True and grad mode on.
 
 Synthesis: a torch.autograd.Function around the unchanged forward launch of
@@ -42,8 +43,25 @@ gradients computed by the same run_backward: the elliptic filter run backwards i
 matrix and curves as the plan holds them.  The one noise gain per utterance does not depend on the features: it is held
 constant and the backward pass is exact.  Not differentiable: v_lf0, fs, hf_slope_coeff, the noise and its gain.
 
+True envelope (section 3.3m): a sixth Function around the unchanged launch of la.true_envelope_batch(return_device=True)
+(Engine.true_envelope), for the three in_types and any ncoeffs, with the gradient with respect to the input matrices
+computed by k_true_envelope_bwd (Engine.true_envelope_backward): the exact adjoint of the passes as the device ran them --
+the forward's pass counts and its packed input rows are kept, the decisions of the max updates are recomputed on chip.  The
+stop test is not differentiated (the pass count is a constant of the backward pass), so the gradient is that of the
+envelope with K passes; it jumps where a decision or the pass count flips.  A row with a non-finite dB value (all NaN
+in the forward) gets a zero gradient.  Not differentiable: thres_db.
+
+Type-2 analysis (section 3.3m): a seventh and an eighth Function around the unchanged forward launches of
+analysis_lossless_type2_batch (Type2AnalysisPlan.run) and analysis_compressed_type2_batch
+(Type2CompressedAnalysisPlan.run), with the gradient with respect to the samples v_sig computed by the plans' run_backward:
+both sets of rows are recomputed (only the envelope's pass counts and, for the compressed form, the three small matrices
+are kept), k_true_envelope_bwd takes the envelope's gradient to the two-period magnitudes, the lossless analysis' backward
+kernels run over the two-period and the one-period frame table and the two sample gradients are added; the compressed form
+first runs the tail of the type-1 compressed backward on the type-2 row tables.  Not differentiable: v_pm_sec, v_voi, fs,
+the per-frame gain.
+
 No double backward.  The compressed synthesis with per_phase_type 'min_phase' / 'linear', with a
-post-filter, with pcm16_norm or with prepared=, and the constant-rate lossless and type-2 analysis, have no backward pass.
+post-filter, with pcm16_norm or with prepared=, and the constant-rate lossless analysis, have no backward pass.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -262,3 +280,125 @@ def synthesize_compressed_type2(plan, utts):
     plan._check_differentiable()     # what has no backward pass says so before the forward is launched
     mats = [x for u in utts for x in u[:3]]
     return _Type2Synthesis.apply(plan, len(utts), *mats)
+
+
+class _TrueEnvelope(torch.autograd.Function):
+    """forward(engine, in_type, ncoeffs, thres_db, *mats): mats = the [F_i x H] matrices of la.true_envelope_batch (tensors
+    or host arrays); Engine.true_envelope is the forward launch, Engine.true_envelope_backward the backward one.  Outputs:
+    the ONE float32 [sum F_i x ld] buffer of envelope rows (the per-matrix results are views of it) and the int32 passes
+    per row (not differentiable).  Kept for the backward pass: the packed float32 input rows and the pass counts."""
+
+    @staticmethod
+    def forward(ctx, engine, in_type, ncoeffs, thres_db, *mats):
+        out, offs, iters, x = engine.true_envelope(list(mats), in_type, ncoeffs, thres_db, want_iters=True,
+                                                   return_input=True)
+        ctx.engine, ctx.in_type, ctx.ncoeffs = engine, in_type, ncoeffs
+        ctx.offs, ctx.n_bins = [int(o) for o in offs], int(mats[0].shape[1])
+        ctx.like = [(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else None for m in mats]
+        ctx.mark_non_differentiable(iters)
+        ctx.save_for_backward(x, iters)
+        return out, iters
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, _grad_iters):
+        x, iters = ctx.saved_tensors
+        n_head = 4   # engine, in_type, ncoeffs, thres_db
+        need_in = ctx.needs_input_grad[n_head:]
+        if grad_out.dtype != torch.float32 or grad_out.stride(1) != 1:
+            grad_out = grad_out.to(torch.float32).contiguous()
+        with torch.cuda.device(x.device):
+            g = ctx.engine.true_envelope_backward(x, iters, grad_out, ctx.n_bins, ctx.in_type, ctx.ncoeffs)
+        out = []
+        for like, need, a, b in zip(ctx.like, need_in, ctx.offs[:-1], ctx.offs[1:]):
+            out.append(g[a:b, :ctx.n_bins].to(like[0]).reshape(like[1]) if like is not None and need else None)
+        return (None,) * n_head + tuple(out)
+
+
+def true_envelope(engine, mats, in_type, ncoeffs, thres_db):
+    """Engine.true_envelope on mats, differentiable with respect to the matrices that are tensors requiring grad.  Returns
+    (the float32 [sum F_i x ld] envelope buffer with grad_fn, the row offsets, the int32 passes per row)."""
+    import numpy as np
+
+    out, iters = _TrueEnvelope.apply(engine, in_type, int(ncoeffs), float(thres_db), *mats)
+    offs = np.concatenate(([0], np.cumsum([int(m.shape[0]) for m in mats]))).astype(np.int64)
+    return out, offs, iters
+
+
+class _Type2Analysis(torch.autograd.Function):
+    """forward(plan, *sigs): plan = a Type2AnalysisPlan built from the utterances whose v_sig are sigs (tensors or host
+    arrays); plan.run(want_iters=True) is the forward launch sequence, plan.run_backward the backward one.  Outputs: the
+    three float32 [total_frames x H] matrices of the batch (envelope, real, imag; the per-utterance results are row views
+    that leave out row 0), the float64 per-frame gain and the int32 passes per envelope row (neither differentiable).
+    Kept for the backward pass: the pass counts only -- both sets of rows are recomputed."""
+
+    @staticmethod
+    def forward(ctx, plan, *sigs):
+        env, real, imag, gain, iters = plan.run(want_iters=True)
+        ctx.plan = plan
+        ctx.like = [(s.dtype, tuple(s.shape)) if torch.is_tensor(s) else None for s in sigs]
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(gain, iters)
+        ctx.save_for_backward(iters)
+        return env, real, imag, gain, iters
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_env, g_real, g_imag, _g_gain, _g_iters):
+        (iters,) = ctx.saved_tensors
+        need_in = ctx.needs_input_grad[1:]
+        grads = tuple(g if g is None or (g.dtype == torch.float32 and g.is_contiguous())
+                      else g.to(torch.float32).contiguous() for g in (g_env, g_real, g_imag))
+        with torch.cuda.device(iters.device):
+            gsig = ctx.plan.run_backward(grads, iters)
+        out, a = [], 0
+        for like, need, n in zip(ctx.like, need_in, ctx.plan.lossless.n_smpls):
+            out.append(gsig[a:a + n].to(like[0]).reshape(like[1]) if like is not None and need else None)
+            a += n
+        return (None,) + tuple(out)
+
+
+def analyze_type2(plan, sigs):
+    """plan.run(want_iters=True) of a Type2AnalysisPlan, differentiable with respect to the v_sig in sigs that are tensors
+    requiring grad.  Returns (env, real, imag, gain, iters) as plan.run does, the three matrices with grad_fn."""
+    return _Type2Analysis.apply(plan, *sigs)
+
+
+class _Type2CompressedAnalysis(torch.autograd.Function):
+    """forward(plan, *sigs): plan = a Type2CompressedAnalysisPlan built from the utterances whose v_sig are sigs;
+    plan.run(want_iters=True) is the forward, plan.run_backward the backward.  Outputs: the three float32 matrices of the
+    batch ([total_out_frames x mag_dim], [.. x phase_dim] twice), the float64 per-frame gain and the int32 passes per
+    envelope row (neither differentiable).  Kept for the backward pass: the three small matrices and the pass counts."""
+
+    @staticmethod
+    def forward(ctx, plan, *sigs):
+        (mag, real, imag), gain, iters = plan.run(want_iters=True)
+        ctx.plan = plan
+        ctx.like = [(s.dtype, tuple(s.shape)) if torch.is_tensor(s) else None for s in sigs]
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(gain, iters)
+        ctx.save_for_backward(mag, real, imag, iters)
+        return mag, real, imag, gain, iters
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_mag, g_real, g_imag, _g_gain, _g_iters):
+        mag, real, imag, iters = ctx.saved_tensors
+        need_in = ctx.needs_input_grad[1:]
+        grads = tuple(g if g is None or (g.dtype == torch.float32 and g.is_contiguous())
+                      else g.to(torch.float32).contiguous() for g in (g_mag, g_real, g_imag))
+        with torch.cuda.device(mag.device):
+            gsig = ctx.plan.run_backward((mag, real, imag), grads, iters)
+        out, a = [], 0
+        for like, need, n in zip(ctx.like, need_in, ctx.plan.t2.lossless.n_smpls):
+            out.append(gsig[a:a + n].to(like[0]).reshape(like[1]) if like is not None and need else None)
+            a += n
+        return (None,) + tuple(out)
+
+
+def analyze_compressed_type2(plan, sigs):
+    """plan.run(want_iters=True) of a Type2CompressedAnalysisPlan, differentiable with respect to the v_sig in sigs that are
+    tensors requiring grad.  Returns ((mag, real, imag) with grad_fn, gain)."""
+    plan.check_grad_dims()           # what has no backward pass says so before the forward is launched
+    mag, real, imag, gain, _iters = _Type2CompressedAnalysis.apply(plan, *sigs)
+    return (mag, real, imag), gain

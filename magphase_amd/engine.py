@@ -1324,13 +1324,14 @@ class Engine:
         return m * (self.to_host_f64(o_r[:, :H]) + 1j * self.to_host_f64(o_i[:, :H]))
 
     def true_envelope(self, mats, in_type="abs", ncoeffs=60, thres_db=0.1, fade=0.7, max_iters=hm.TRUE_ENV_MAX_ITERS,
-                      forced_iters=None, want_iters=False, ticket=True):
+                      forced_iters=None, want_iters=False, ticket=True, return_input=False):
         """
         la.true_envelope on a list of [F_i x H] matrices (numpy, or float32 device tensors) through ONE mpx_true_envelope
         launch: the rows are concatenated at mpx_spec_ld(H).  -> (device out [sum F_i x ld], row offsets, device int32
         passes per row or None).  max_iters = 1 with fade = fade_to_total is la.spectral_smoothing_rceps.
         forced_iters (tests): int per row, exactly that many passes.  ticket: frames handed out by a device counter (the
-        faster form); False: by grid stride.
+        faster form); False: by grid stride.  return_input: the packed float32 input rows [sum F_i x ld] as a
+        fourth result (what true_envelope_backward takes).
         """
         torch = _torch()
         H = int(mats[0].shape[1])
@@ -1354,7 +1355,38 @@ class Engine:
         tk = torch.empty(1, dtype=torch.int32, device=self.device) if ticket else None
         self.launch("mpx_true_envelope", N, self.tables(N), w, x, ld, F, hm.TRUE_ENV_IN_TYPES.index(in_type),
                     float(thres_db), int(max_iters), out, ld, iters, forced, tk)
-        return out, offs, iters
+        return (out, offs, iters, x) if return_input else (out, offs, iters)
+
+    def true_envelope_backward(self, x, iters, grad_out, n_bins, in_type="abs", ncoeffs=60, fade=0.7,
+                               max_iters=hm.TRUE_ENV_MAX_ITERS, want_decisions=False, want_env=False, ticket=True):
+        """
+        Gradient of true_envelope's output rows with respect to its input rows through ONE mpx_true_envelope_backward launch
+        (k_true_envelope_bwd).  x: the forward's float32 device input rows [F x >= H], H = n_bins (row pitch =
+        stride(0)); iters: device int32 [F], the forward's passes per row; grad_out: float32 device [F x >= H].  -> the gradient
+        [F x ld] (columns >= H are not written), or with want_decisions / want_env (tests) the tuple (gradient, decision
+        words int32 [F x max_iters x ceil(H / 32)] or None, recomputed envelope rows [F x ld] or None).
+        """
+        torch = _torch()
+        F, H = int(x.shape[0]), int(n_bins)
+        ld = int(x.stride(0)) if F > 1 else int(x.shape[1])
+        N = hm.true_envelope_check(H, in_type, ncoeffs)
+        if int(x.shape[1]) < H or int(grad_out.shape[1]) < H:
+            raise ValueError("true_envelope_backward: rows shorter than n_bins")
+        if x.dtype != torch.float32 or grad_out.dtype != torch.float32 or iters.dtype != torch.int32:
+            raise TypeError("true_envelope_backward: float32 rows and int32 pass counts expected")
+        if x.stride(1) != 1 or grad_out.stride(1) != 1 or int(grad_out.shape[0]) != F or int(iters.numel()) != F:
+            raise ValueError("true_envelope_backward: [F x H] rows with unit column stride and F pass counts expected")
+        ld_g = int(grad_out.stride(0)) if F > 1 else int(grad_out.shape[1])
+        old = int(self.lib.mpx_spec_ld(H))
+        gx = self.empty((F, old))
+        w = self.constant(("true_env_w", N, int(ncoeffs), float(fade)), lambda: hm.true_envelope_lifter(N, ncoeffs, fade))
+        dec = torch.empty((F, int(max_iters), (H + 31) // 32), dtype=torch.int32, device=self.device) \
+            if want_decisions else None
+        env = self.empty((F, old)) if want_env else None
+        tk = torch.empty(1, dtype=torch.int32, device=self.device) if ticket else None
+        self.launch("mpx_true_envelope_backward", N, self.tables(N), w, x, ld, F, hm.TRUE_ENV_IN_TYPES.index(in_type),
+                    int(max_iters), iters.contiguous(), grad_out, ld_g, gx, old, dec, env, old, tk)
+        return (gx, dec, env) if (want_decisions or want_env) else gx
 
     def warp_mag_matrix(self, mag_dim, H, alpha, b_mag_fbank_mel=False):
         """Device-resident [mag_dim x H] matrix of the magnitude compression and the name of the C entry point that goes
@@ -1439,7 +1471,8 @@ class Engine:
         return out
 
     def analysis_lossless_backward(self, fft_len, plan, mag, real, imag, grads):
-        """mpx_analysis_lossless_backward: plan: LosslessAnalysisPlan, mag / real / imag: the rows its run() returned,
+        """mpx_analysis_lossless_backward: plan: LosslessAnalysisPlan (or a plans.FrameTable: pos / left / right,
+        total_frames, total_smpls, backward_tables()), mag / real / imag: the rows its run() returned,
         grads = (g_mag, g_real, g_imag): float32 [plan.total_frames x H] rows with unit column stride and one row pitch, or
         None for an output nobody differentiated (not read, contributes zero) -> dL/d(samples), float32
         [plan.total_smpls] (zeros where no frame covers a sample, or when nothing is given)."""

@@ -486,6 +486,12 @@ def true_envelope_batch(list_of_matrices, in_type="abs", ncoeffs=60, thres_db=0.
     of k_true_envelope.  H - 1 must be 512, 1024 or 2048.  Returns a list of float64 arrays (return_device: float32
     device tensors [F_i x H], views of one buffer); return_iters: (that list, list of int32 passes per frame).
     A row with a zero or negative magnitude ('abs') comes back all NaN, as in the reference.
+
+    With return_device=True, a device tensor among the matrices that requires grad makes the returned envelopes carry a
+    grad_fn (magphase_amd/autograd.py, k_true_envelope_bwd): the exact adjoint of the passes the device ran, for every
+    in_type and ncoeffs; the input gets a gradient in its own dtype.  The stop test is not differentiated (the pass count is
+    held), thres_db is not differentiable, an all-NaN row gets a zero gradient, and there is no double backward.  The forward
+    values are the same bits either way.
     """
     mats = _te_inputs(list_of_matrices)
     if not mats:
@@ -493,8 +499,15 @@ def true_envelope_batch(list_of_matrices, in_type="abs", ncoeffs=60, thres_db=0.
     hm.true_envelope_check(int(mats[0].shape[1]), in_type, ncoeffs)
     from .engine import get_engine
 
+    import torch
+
     e = get_engine()
-    out, offs, iters = e.true_envelope(mats, in_type, int(ncoeffs), float(thres_db), want_iters=return_iters)
+    if return_device and torch.is_grad_enabled() and any(torch.is_tensor(m) and m.requires_grad for m in mats):
+        from . import autograd
+
+        out, offs, iters = autograd.true_envelope(e, mats, in_type, int(ncoeffs), float(thres_db))
+    else:
+        out, offs, iters = e.true_envelope(mats, in_type, int(ncoeffs), float(thres_db), want_iters=return_iters)
     H = int(mats[0].shape[1])
     rows = [out[int(a):int(b), :H] for a, b in zip(offs[:-1], offs[1:])]
     if return_device:

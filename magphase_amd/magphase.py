@@ -1061,6 +1061,23 @@ def _type2_rate(const_rate_ms):
     return v
 
 
+def _is_device_tensor(x):
+    import sys
+
+    torch = sys.modules.get("torch")
+    return torch is not None and torch.is_tensor(x) and x.device.type != "cpu"
+
+
+def _wants_grad(utts, return_device):
+    """A type-2 analysis call runs inside its torch.autograd.Function when the result stays on the device, grad mode is on
+    and some v_sig is a device tensor that requires grad (the rule of _run_lossless_analysis)."""
+    import sys
+
+    torch = sys.modules.get("torch")
+    return bool(return_device and torch is not None and torch.is_grad_enabled()
+                and any(_is_device_tensor(u[0]) and u[0].requires_grad for u in utts))
+
+
 def _type2_check(utts, fft_len):
     """Host argument checks of the type-2 analysis: (v_sig, fs, v_pm_sec, v_voi) tuples, one fft_len the device path
     takes (1024, 2048 or 4096) for the whole call, epochs and voicing of one length."""
@@ -1069,7 +1086,7 @@ def _type2_check(utts, fft_len):
         if len(u) != 4:
             raise ValueError("utts[%d]: expected (v_sig, fs, v_pm_sec, v_voi)" % i)
         v_sig, fs, v_pm_sec, v_voi = u
-        if np.ndim(v_sig) != 1:
+        if (v_sig.dim() if _is_device_tensor(v_sig) else np.ndim(v_sig)) != 1:   # (a device tensor is not staged for this)
             raise ValueError("utts[%d]: v_sig must be 1-D" % i)
         if np.ndim(v_pm_sec) != 1 or np.shape(v_pm_sec) != np.shape(v_voi) or np.size(v_pm_sec) == 0:
             raise ValueError("utts[%d]: v_pm_sec and v_voi must be non-empty 1-D vectors of one length" % i)
@@ -1094,6 +1111,15 @@ def analysis_lossless_type2_batch(utts, fft_len=None, engine=None, return_device
     Both transforms are float64 (k_analysis_f64), as analysis_compressed's.  A magnitude row with a zero bin gives an
     all-NaN envelope row, as in the reference.  return_iters: each tuple gets the envelope's passes per frame (int32)
     appended.  Engine: Type2AnalysisPlan.
+    v_sig may be a 1-D torch tensor on the engine's device (float32 / float16 / bfloat16 / float64, any element stride),
+    under the rules of analysis_lossless_batch: no sample is staged through the host, and the rows equal those of the
+    host-array call on the same float32 samples bit for bit.
+    Autograd: with return_device, grad mode on and a device v_sig that requires grad, m_mag_env / m_real / m_imag carry a
+    grad_fn and tensor.backward() reaches v_sig (magphase_amd/autograd.py, Type2AnalysisPlan.run_backward: the envelope's
+    backward kernel k_true_envelope_bwd, then the lossless analysis' backward kernels over the two frame tables; the
+    forward launches and their rows are the same).  The envelope's gradient is that of the passes as the device ran them:
+    the stop test is not differentiated.  Not differentiable: v_pm_sec, v_voi and fs; v_f0, v_shift and the per-frame
+    gain (float64, detached) carry no grad_fn; no double backward.
     """
     utts = list(utts)
     if not utts:
@@ -1104,11 +1130,16 @@ def analysis_lossless_type2_batch(utts, fft_len=None, engine=None, return_device
     for lens in plan.long_frame_lens:
         for n in lens:  # Q19: truncation warns, it does not raise (magphase.py:311-315)
             warnings.warn(_WARN_LONG % (plan.fft_len, n))
-    env, real, imag, gain, iters = plan.run(want_iters=return_iters)
+    if _wants_grad(utts, return_device):
+        from .autograd import analyze_type2
+
+        env, real, imag, gain, iters = analyze_type2(plan, [u[0] for u in utts])
+    else:
+        env, real, imag, gain, iters = plan.run(want_iters=return_iters)
     if not return_device:
         h = engine.to_host_f64_many([env, real, imag]) if plan.total_frames else [np.zeros((0, env.shape[1]))] * 3
         h_gain = gain.cpu().numpy()
-    h_iters = iters.cpu().numpy() if iters is not None else None
+    h_iters = iters.cpu().numpy() if return_iters else None   # (under autograd iters exists either way: no copy unasked)
     out = []
     for u in range(len(utts)):
         a, b = plan.out_rows(u)
@@ -1150,6 +1181,15 @@ def analysis_compressed_type2_batch(utts, fft_len=None, mag_dim=60, phase_dim=45
     rate); <= 0: the variable rate.  v_lgain = la.log(v_gain); b_norm_mag: the mean of columns 1.. of each log-mel row is
     subtracted, stored in column 0 and returned as v_lgain (magphase.py:3178-3182).  The three matrices are float64 numpy
     (return_device: float32 device rows); v_lf0_smth, v_shift and v_lgain are float64 numpy.
+    v_sig may be a 1-D torch tensor on the engine's device, under the rules of analysis_lossless_batch (no host staging,
+    rows bit-identical to the host-array call).
+    Autograd: with return_device, grad mode on and a device v_sig that requires grad, the three matrices carry a grad_fn
+    and tensor.backward() reaches v_sig, at the variable rate and at any const_rate_ms > 0, for mag_dim and phase_dim up
+    to 64 (more: NotImplementedError naming the argument); b_norm_mag is then applied with out-of-place torch operations,
+    so it is differentiated too (Type2CompressedAnalysisPlan.run_backward).  An unvoiced frame
+    contributes no phase gradient and a phase coefficient on the clip (exactly +-1) has a zero gradient, as in
+    analysis_compressed_batch.  Not differentiable: v_pm_sec, v_voi, fs; v_lf0_smth, v_shift and v_lgain (the gain stays
+    float64 and detached) carry no grad_fn; no double backward.
     """
     const_rate_ms = _type2_rate(const_rate_ms)
     utts = list(utts)
@@ -1166,10 +1206,23 @@ def analysis_compressed_type2_batch(utts, fft_len=None, mag_dim=60, phase_dim=45
     for lens in plan.t2.long_frame_lens:
         for n in lens:
             warnings.warn(_WARN_LONG % (plan.fft_len, n))
-    (mag, real, imag), gain = plan.run()
+    with_grad = _wants_grad(utts, return_device)
+    if with_grad:
+        from .autograd import analyze_compressed_type2
+
+        (mag, real, imag), gain = analyze_compressed_type2(plan, [u[0] for u in utts])
+    else:
+        (mag, real, imag), gain = plan.run()
     h_gain = gain.cpu().numpy()
     v_mean = None
-    if b_norm_mag:   # magphase.py:3178-3182, float64
+    if b_norm_mag and with_grad:   # the same arithmetic out of place, so that autograd sees it
+        import torch
+
+        md = mag.double()
+        v_mean = md[:, 1:].mean(dim=1)
+        mag = torch.cat((v_mean[:, None], md[:, 1:] - v_mean[:, None]), dim=1).to(torch.float32)
+        v_mean = v_mean.detach().cpu().numpy()
+    elif b_norm_mag:   # magphase.py:3178-3182, float64
         md = mag.double()
         v_mean = md[:, 1:].mean(dim=1)
         md -= v_mean[:, None]

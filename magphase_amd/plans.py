@@ -1691,6 +1691,25 @@ class CompressedAnalysisPlan:
         return gsig
 
 
+class FrameTable:
+    """A frame table over a batch's signal buffer, as Engine.analysis_lossless_backward reads one -- the part of a
+    LosslessAnalysisPlan that call uses, for a second table over the same samples: pos (int64) / left / right (int32) on the
+    device, total_frames, total_smpls and backward_tables() -> (scratch_off device int64 [F + 1], scratch floats) of
+    hostmath.analysis_backward_table, built from the host copies on the first call."""
+
+    def __init__(self, engine, fft_len, pos, left, right, total_frames, total_smpls, host_tabs):
+        self.engine, self.fft_len = engine, int(fft_len)
+        self.pos, self.left, self.right = pos, left, right
+        self.total_frames, self.total_smpls = int(total_frames), int(total_smpls)
+        self._host_tabs, self._bwd = host_tabs, None
+
+    def backward_tables(self):
+        if self._bwd is None:
+            _start, soff = hm.analysis_backward_table(*self._host_tabs, self.fft_len, self.total_smpls)
+            self._bwd = (self.engine.to_device(soff, np.int64), int(soff[-1]))
+        return self._bwd
+
+
 class Type2AnalysisPlan:
     """
     analysis_lossless_type2 (magphase.py:2793-2866) for a batch of utterances with epochs, (v_sig, fs, v_pm_sec, v_voi),
@@ -1732,6 +1751,7 @@ class Type2AnalysisPlan:
                                 ("voi", cat(voi, np.float32), np.float32),
                                 ("mag_only", np.zeros(F, dtype=np.float32), np.float32)])
         self.left2, self.right2, self.voi, self.mag_only = t["left2"], t["right2"], t["voi"], t["mag_only"]
+        self._host_lr2 = (cat(l2, np.int64), cat(r2, np.int64))   # (the backward pass' scratch table is built from them)
         self.ld = int(e.lib.mpx_spec_ld(N // 2 + 1))   # one row pitch for the analysis rows and the envelope
 
     def out_rows(self, u):
@@ -1759,14 +1779,65 @@ class Type2AnalysisPlan:
         w = e.constant(("true_env_w", N, TYPE2_ENV_NCOEFFS, 0.7),
                        lambda: hm.true_envelope_lifter(N, TYPE2_ENV_NCOEFFS, 0.7))
         forced = None
-        if forced_iters is not None:
-            forced = e.to_device(np.asarray(forced_iters, dtype=np.int32).reshape(F), np.int32)
+        if forced_iters is not None:   # (a device int32 tensor -- run(want_iters=True)'s own -- is taken as it is)
+            forced = forced_iters.reshape(F) if _is_tensor(forced_iters) else \
+                e.to_device(np.asarray(forced_iters, dtype=np.int32).reshape(F), np.int32)
         tk = torch.empty(1, dtype=torch.int32, device=e.device)
         e.launch("mpx_frame_gain", N, pl.sig, pl.pos, pl.left, pl.right, self.voi, F, gain, int(gain_blocks_per_cu))
         e.launch("mpx_true_envelope", N, e.tables(N), w, mag, self.ld, F, hm.TRUE_ENV_IN_TYPES.index("abs"),
                  TYPE2_ENV_THRES_DB, hm.TRUE_ENV_MAX_ITERS, env, self.ld, iters, forced, tk)
         del mag   # (stream-ordered: the allocator reuses the magnitude rows after the envelope)
         return env[:F, :H], feats[1], feats[2], gain[:F], iters
+
+    def two_period_table(self):
+        """The two-period frame table as a FrameTable for Engine.analysis_lossless_backward.  Truncated frames keep
+        starts and ends non-decreasing, so hostmath.analysis_backward_table accepts the table."""
+        if getattr(self, "_tab2", None) is None:
+            pl = self.lossless
+            _wait_ready(pl)
+            tabs = getattr(pl, "_host_tabs", None)
+            pos = tabs[0] if tabs is not None else pl.pos.cpu().numpy()
+            self._tab2 = FrameTable(self.engine, self.fft_len, pl.pos, self.left2, self.right2, self.total_frames,
+                                    pl.total_smpls, (pos,) + self._host_lr2)
+        return self._tab2
+
+    def run_backward(self, grads, iters, want_decisions=False):
+        """The gradient of a loss with respect to the batch's samples, float32 [total_smpls], given grads = (dL/d env,
+        dL/d real, dL/d imag) of run()'s three matrices -- float32 [total_frames x H] with unit column stride, or None for
+        an output nobody differentiated -- and iters, run(want_iters=True)'s passes per envelope row.  DESIGN.md section
+        3.3m.  Nothing of size F x H is kept between the passes: the two-period rows are recomputed into buffers of their
+        own (all three: the magnitude gradient needs the phase rows of the two-period frames, which the forward never
+        writes), k_true_envelope_bwd takes dL/d env to the two-period magnitudes, the lossless analysis' backward kernels
+        take those over the table (pos, left2, right2) to the samples; the one-period rows are recomputed with every row
+        written and the same kernels take (None, dL/d real, dL/d imag) over (pos, left, right); the two sample gradients
+        are added.  Row 0 of every utterance, which the outputs drop, arrives with zero gradients.  want_decisions
+        (tests): -> (gradient, the envelope kernel's decision words or None)."""
+        e, torch = self.engine, _torch()
+        pl, N, F = self.lossless, self.fft_len, self.total_frames
+        H, total = N // 2 + 1, int(pl.total_smpls)
+        for g in grads:
+            if g is not None and (g.dtype != torch.float32 or tuple(g.shape) != (F, H) or g.stride(1) != 1):
+                raise ValueError("run_backward: gradients must be float32 [%d x %d] with unit column stride" % (F, H))
+        g_env, g_real, g_imag = grads
+        gsig, dec = None, None
+        if F == 0 or total == 0 or all(g is None for g in grads):
+            return (torch.zeros((total,), dtype=torch.float32, device=e.device), None) if want_decisions else \
+                torch.zeros((total,), dtype=torch.float32, device=e.device)
+        if g_env is not None:
+            _wait_ready(pl)
+            rows2 = tuple(e.empty((F, self.ld))[:, :H] for _ in range(3))
+            e.analysis_frames(N, pl.sig, pl.pos, self.left2, self.right2, out=rows2, precise=True, rows_in_use=None)
+            r = e.true_envelope_backward(rows2[0], iters, g_env, H, "abs", TYPE2_ENV_NCOEFFS,
+                                         want_decisions=want_decisions)
+            g_mag2, dec = (r[0], r[1]) if want_decisions else (r, None)
+            gsig = e.analysis_lossless_backward(N, self.two_period_table(), rows2[0], rows2[1], rows2[2],
+                                                (g_mag2[:, :H], None, None))
+        if g_real is not None or g_imag is not None:
+            rows1 = tuple(e.empty((F, self.ld))[:, :H] for _ in range(3))
+            pl.run(out=rows1, precise=True, rows_in_use=None)
+            g1 = pl.run_backward(rows1[0], rows1[1], rows1[2], (None, g_real, g_imag))
+            gsig = g1 if gsig is None else gsig + g1
+        return (gsig, dec) if want_decisions else gsig
 
 
 class Type2CompressedAnalysisPlan:
@@ -1806,21 +1877,72 @@ class Type2CompressedAnalysisPlan:
             row1, rowt, self.f0_out = row0, np.zeros(row0.size), list(t2.v_f0)
             self.out_off = np.concatenate(([0], np.cumsum([f.size for f in self.f0_out]))).astype(np.int64)
         self.total_out_frames = int(self.out_off[-1])
+        self._rows_host = (np.asarray(row0), np.asarray(row1), np.asarray(rowt, dtype=np.float64))   # (backward pass)
         f0_cat = np.concatenate(self.f0_out) if self.f0_out else np.zeros(0)
         (self.row0, self.row1, self.rowt), d = _upload_rows(
             e, (row0, row1, rowt), head=[("voi", (f0_cat > 0).astype(np.float32), np.float32)])
         self.voi = d["voi"]
 
-    def run(self):
+    def run(self, want_iters=False):
         """-> ((mag [Fo x mag_dim], real, imag [Fo x phase_dim]) float32 device, gain float64 device [F]: the type-2
-        plan's rows, see Type2AnalysisPlan.out_rows)."""
+        plan's rows, see Type2AnalysisPlan.out_rows); want_iters: the envelope's int32 device passes per row as a third
+        result (what run_backward takes)."""
+        outs, gain, iters = self._run(want_iters)
+        return (outs, gain, iters) if want_iters else (outs, gain)
+
+    def check_grad_dims(self):
+        """k_mel_warp_bwd produces the gradient of at most 64 coefficient columns per job."""
+        for name, d in (("mag_dim", self.mag_dim), ("phase_dim", self.phase_dim)):
+            if int(d) > 64:
+                raise NotImplementedError("%s = %d: the backward pass of the type-2 analysis takes at most 64 coefficient "
+                                          "columns" % (name, int(d)))
+
+    def run_backward(self, outs, grads, iters):
+        """The gradient of a loss with respect to the batch's samples, float32 [total_smpls], given outs = run()'s three
+        matrices, grads = (dL/d m_mag_mel_log, dL/d m_real_mel, dL/d m_imag_mel) as contiguous float32 matrices of their
+        shapes or None, and iters = run(want_iters=True)'s pass counts.  The tail of CompressedAnalysisPlan.run_backward
+        on the type-2 row tables (which the forward reads at either rate): the type-2 rows are recomputed with the
+        forward's pass counts forced, k_phase_grad_mask, k_rows_lerp_adjoint at width phase_dim, k_mel_warp_bwd with the
+        magnitude job against the envelope rows, k_rows_lerp_adjoint on the magnitude gradients; then
+        Type2AnalysisPlan.run_backward.  DESIGN.md section 3.3m."""
+        self.check_grad_dims()
+        torch = _torch()
+        e, t2 = self.engine, self.t2
+        H = self.fft_len // 2 + 1
+        Fo, F, total = self.total_out_frames, int(t2.total_frames), int(t2.lossless.total_smpls)
+        shapes = ((Fo, self.mag_dim), (Fo, self.phase_dim), (Fo, self.phase_dim))
+        for g, shp in zip(grads, shapes):
+            if g is not None and (g.dtype != torch.float32 or tuple(g.shape) != shp or not g.is_contiguous()):
+                raise ValueError("run_backward: gradients must be contiguous float32 of the outputs' shapes")
+        g_m, g_r, g_i = grads
+        if Fo == 0 or F == 0 or total == 0 or all(g is None for g in grads):
+            return torch.zeros((total,), dtype=torch.float32, device=e.device)
+        env, real, imag, _gain, _it = t2.run(forced_iters=iters)
+        h_r, h_i = e.phase_grad_mask(outs[1], outs[2], self.voi, g_r, g_i)
+        if getattr(self, "_adj", None) is None:
+            r0, r1, rt = self._rows_host
+            self._adj = e.to_device(hm.lerp_adjoint_table(r0, r1, rt, F).reshape(-1), np.int32)
+        _none, h_r, h_i = e.rows_lerp_adjoint((None, h_r, h_i), self._adj, self.rowt, F)
+        have_ph = h_r is not None or h_i is not None
+        tabs = (self.row0, self.row1, self.rowt)
+        g_rows = e.mel_warp_backward(H, mag=(g_m, self.w_mag, env, tabs) if g_m is not None else None,
+                                     phase=(h_r, h_i, self.w_ph, real, imag, None) if have_ph else None)
+        if g_rows[0] is not None:
+            # An output frame whose log-mel row the forward wrote as NaN (an envelope row it reads has a zero bin: digital
+            # silence) has no gradient: zero -- not the kernel's NaN x 0, which the interpolation's adjoint would carry
+            # into the finite neighbouring row.  (k_true_envelope_bwd gives such an envelope row a zero gradient too.)
+            g_rows[0].masked_fill_((~torch.isfinite(outs[0]).all(dim=1))[:, None], 0.0)
+            g_rows = (e.rows_lerp_adjoint((g_rows[0], None, None), self._adj, self.rowt, F)[0],) + tuple(g_rows[1:])
+        return t2.run_backward(g_rows, iters)
+
+    def _run(self, want_iters):
         e = self.engine
         H = self.fft_len // 2 + 1
-        env, real, imag, gain, _ = self.t2.run()
+        env, real, imag, gain, iters = self.t2.run(want_iters=want_iters)
         Fo = self.total_out_frames
         out = (e.empty((max(Fo, 1), self.mag_dim)), e.empty((max(Fo, 1), self.phase_dim)),
                e.empty((max(Fo, 1), self.phase_dim)))
         if Fo:
             e.launch("mpx_mel_warp", Fo, H, env, real, imag, self.row0, self.row1, self.rowt, self.w_mag, self.mag_dim,
                      self.w_ph, self.phase_dim, self.voi, out[0], out[1], out[2], e.feat_ld(env, real, imag))
-        return tuple(o[:Fo] for o in out), gain
+        return tuple(o[:Fo] for o in out), gain, iters
