@@ -51,14 +51,14 @@ def test_unwarp_and_noise_gains_match_oracle(orc, golden_dir):
     mag = plan.debug["mag"].cpu().numpy().astype(np.float64)
     real = plan.debug["real"].cpu().numpy().astype(np.float64)
     imag = plan.debug["imag"].cpu().numpy().astype(np.float64)
-    assert np.max(np.abs(mag - dbg["m_mag"]) / dbg["m_mag"]) < 5e-6   # fp32 sum of 60 terms in the exponent
+    within(np.max(np.abs(mag - dbg["m_mag"]) / dbg["m_mag"]), 5e-6, "COMP_UNWARP_MAG_REL")   # fp32 sum of 60 terms in the exponent
     # the phase rows exist where the synthesis reads them (magphase.py:925-931: voiced frames, bins below the end of the
     # periodic / aperiodic crossfade); since round 5 that also holds for variable-rate input (mpx_mel_unwarp_rows with
     # identity row tables).  Voiced frames are checked; the plain form, all frames and bins, below.
     v, n_per = plan.voiced_host, int(plan.n_per)
     assert np.any(v) and 0 < n_per <= 512
-    assert np.max(np.abs(real[v, :n_per] - dbg["m_real"][v, :n_per])) < 2e-6
-    assert np.max(np.abs(imag[v, :n_per] - dbg["m_imag"][v, :n_per])) < 2e-6
+    within(np.max(np.abs(real[v, :n_per] - dbg["m_real"][v, :n_per])), 2e-6, "COMP_UNWARP_PHASE_ABS")
+    within(np.max(np.abs(imag[v, :n_per] - dbg["m_imag"][v, :n_per])), 2e-6, "COMP_UNWARP_PHASE_ABS")
     os.environ["MAGPHASE_UNWARP_ROWS_VAR"] = "0"
     try:
         np.random.seed(11)
@@ -68,12 +68,12 @@ def test_unwarp_and_noise_gains_match_oracle(orc, golden_dir):
         os.environ.pop("MAGPHASE_UNWARP_ROWS_VAR")
     assert not plain.unwarp_rows and plan.unwarp_rows
     assert np.array_equal(plain.debug["mag"].cpu().numpy(), plan.debug["mag"].cpu().numpy())   # the same values bit for bit
-    assert np.max(np.abs(plain.debug["real"].cpu().numpy().astype(np.float64) - dbg["m_real"])) < 2e-6
-    assert np.max(np.abs(plain.debug["imag"].cpu().numpy().astype(np.float64) - dbg["m_imag"])) < 2e-6
+    within(np.max(np.abs(plain.debug["real"].cpu().numpy().astype(np.float64) - dbg["m_real"])), 2e-6, "COMP_UNWARP_PHASE_ABS")
+    within(np.max(np.abs(plain.debug["imag"].cpu().numpy().astype(np.float64) - dbg["m_imag"])), 2e-6, "COMP_UNWARP_PHASE_ABS")
     assert np.array_equal(plain.debug["real"].cpu().numpy()[v, :n_per], plan.debug["real"].cpu().numpy()[v, :n_per])
     g_voi, g_unv = plan.gains[0]
-    assert abs(g_voi - dbg["g_voi"]) < 1e-6 * dbg["g_voi"]
-    assert abs(g_unv - dbg["g_unv"]) < 1e-6 * dbg["g_unv"]
+    within(abs(g_voi - dbg["g_voi"]) / dbg["g_voi"], 1e-6, "COMP_NOISE_GAIN_REL")
+    within(abs(g_unv - dbg["g_unv"]) / dbg["g_unv"], 1e-6, "COMP_NOISE_GAIN_REL")
 
 
 def test_unwarp_rows_equals_unwarp_then_interpolation(golden_dir):
@@ -124,9 +124,9 @@ def test_unwarp_rows_equals_unwarp_then_interpolation(golden_dir):
         if name != "mag":                      # phase rows: voiced frames, bins below the crossfade (the rest is never read)
             got, want = got[voi][:, :nc], want[voi][:, :nc]
         if name == "mag":
-            assert np.max(np.abs(got - want) / want) < 3e-7          # one fp32 rounding of the lerp
+            within(np.max(np.abs(got - want) / want), 3e-7, "COMP_UNWARP_ROWS_MAG_REL")   # one fp32 rounding of the lerp
         else:
-            assert np.max(np.abs(got - want)) < 2e-6                 # 45-term fp32 sums in a different association
+            within(np.max(np.abs(got - want)), 2e-6, "COMP_UNWARP_ROWS_PHASE_ABS")   # 45-term fp32 sums in a different association
 
 
 def test_row_table_form_of_the_synthesis_kernel(golden_dir):
