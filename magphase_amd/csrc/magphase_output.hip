@@ -254,7 +254,9 @@ __global__ __launch_bounds__(256) void k_pcm16(const T* __restrict__ y, const lo
     double v = (double)y[i];
     if (norm > 0.0) v = __ddiv_rn(__dmul_rn(norm, v), peak[u]);
     const double r = rint(__dmul_rn(v, 32767.0));
-    out[i] = (short)fmin(fmax(r, -32768.0), 32767.0);   // NaN (silent utterance: 0 / 0) -> fmax/fmin pick the bound
+    // NaN (a silent utterance: 0 / 0) is written as 0, as the host form stores it -- fmax / fmin alone would pick the
+    // bound, -32768: a full-scale DC file instead of silence
+    out[i] = (r != r) ? (short)0 : (short)fmin(fmax(r, -32768.0), 32767.0);
 }
 
 // int16 PCM -> float32 in [-1, 1): x * 2^-15, exact (what the host did with np.multiply before uploading float32 --

@@ -1105,14 +1105,19 @@ def hpf_tables(fs, block, design="butter40"):
     sos = np.ascontiguousarray(sos, dtype=np.float64)
     pm = np.zeros((2, 4))
     g = np.zeros((2, block, 2))
+    ld = np.longdouble
     for sec in range(2):
-        a1, a2 = sos[sec, 4] / sos[sec, 3], sos[sec, 5] / sos[sec, 3]
-        amat = np.array([[-a1, 1.0], [-a2, 0.0]])
-        row = np.array([1.0, 0.0])
+        # The powers of A are built in longdouble from the float64 a1, a2 the kernels use, and rounded once.  The poles of a
+        # section are a close pair (angle 0.004 at 48 kHz), A is nearly defective and a rounding of a low power is amplified
+        # ~1e5 times in A^256: np.linalg.matrix_power in float64 was 1.2e-9 off (1e-11 of the largest entry), which
+        # was half of the blocked scan's whole error (tests/test_output_stage_host.py).
+        a1, a2 = ld(sos[sec, 4] / sos[sec, 3]), ld(sos[sec, 5] / sos[sec, 3])
+        amat = np.array([[-a1, ld(1)], [-a2, ld(0)]], dtype=ld)
+        power = np.eye(2, dtype=ld)
         for n in range(block):
-            g[sec, n] = row
-            row = row @ amat
-        pm[sec] = np.linalg.matrix_power(amat, block).reshape(-1)
+            g[sec, n] = power[0].astype(np.float64)
+            power = power @ amat
+        pm[sec] = power.reshape(-1).astype(np.float64)
     return sos, pm, g
 
 

@@ -114,6 +114,7 @@ def write_audio_file(filepath, v_signal, fs, norm=0.98):
     except ImportError:
         pass
     pcm = np.rint(v_signal * 32767.0)
+    pcm[np.isnan(pcm)] = 0.0       # a silent signal (0 / 0) is written as silence; the cast alone leaves NaN -> int to the platform
     np.clip(pcm, -32768.0, 32767.0, out=pcm)
     write_pcm16_file(filepath, pcm.astype("<i2"), fs)
 

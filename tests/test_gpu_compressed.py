@@ -439,7 +439,9 @@ def test_device_post_filter_and_gains(mp, orc, golden_dir):
 
 
 def test_device_output_hpf_matches_lfilter(mp):
-    """mpx_output_hpf (cascade of biquads, blocked float64 scan) vs scipy.signal.lfilter on ragged utterances."""
+    """mpx_output_hpf (cascade of biquads, blocked float64 scan) vs scipy.signal.lfilter on ragged utterances.  The bound is
+    what lfilter's direct form allows: 7.6e-8 of these inputs is its own round-off (the device is 1e-10 from the longdouble
+    cascade: tests/test_gpu_output_stage.py holds the kernels to that)."""
     from scipy import signal
     from magphase_amd.engine import get_engine
     eng = get_engine()
@@ -454,7 +456,7 @@ def test_device_output_hpf_matches_lfilter(mp):
         b_, a_ = signal.butter(4, 40 / (fs / 2.0), btype="highpass")
         for u, x in enumerate(sigs):
             ref = signal.lfilter(b_, a_, x.astype(np.float64))
-            assert np.max(np.abs(y[off[u]:off[u + 1]] - ref)) <= 1e-6 * max(1.0, np.max(np.abs(ref)))
+            assert np.max(np.abs(y[off[u]:off[u + 1]] - ref)) <= 2e-7 * max(1.0, np.max(np.abs(ref)))
 
 
 @pytest.mark.parametrize("fs", [44100, 22050])
