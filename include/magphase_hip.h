@@ -833,6 +833,34 @@ int mpx_noise_rms(void* stream, int fft_len, const double* power, const int32_t*
                   float* inv_gain, double* rms);
 
 /*
+ * Maximum-likelihood parameter generation (MLPG): the smooth trajectory of an acoustic model's static / delta /
+ * acceleration means and variances.  NOT taken from Merlin or bandmat (neither is at hand): the mathematics is stated in
+ * DESIGN.md section 3.3n, parity with Merlin is unpinned.  Per utterance u (rows utt_frame_off[u] .. utt_frame_off[u + 1]
+ * - 1 of every operand; utt_frame_off: device int32 [n_utts + 1]) and dimension d < D, with K = 1 + n_win streams
+ * (stream 0 static, window (0, 1, 0); windows: HOST pointer to n_win x 3 float64 taps (w[-1], w[0], w[+1]); n_win 1 or 2):
+ * W_k[t, t + j] = w_k[j], taps outside the utterance dropped; P_k = diag(1 / var[., k D + d]); A = sum_k W_k^T P_k W_k;
+ * b = sum_k W_k^T P_k mean[., k D + d]; out[., d] = A^-1 b.
+ * mpx_mlpg_solve: one lane per system (u, d), LDL^T of bandwidth 2 in float64.  mean: float32 (mean_f64 == 0) or float64
+ * [total_frames x K D] at row pitch ld_mean (a column slice of a wider matrix: pass its first element and the matrix's
+ * pitch); var likewise (var_f64, ld_var), ld_var == 0: ONE row for all frames (the global variance); every variance must
+ * be finite and > 0 (not checked on the device).  out: float64 [total_frames x D] at ld_out.  work: float64
+ * [mpx_mlpg_work_doubles(total_frames, D)], the factor rows as two [total_frames x D] planes.  rhs_direct != 0: mean is
+ * the right-hand side itself, [total_frames x D] at ld_mean, and out = A^-1 mean (the backward pass: z = A^-1 g).
+ * No atomics; a system's result does not depend on the batch it is in; nothing outside an utterance's rows is read.
+ * mpx_mlpg_apply: y[t, k D + d] = [1 / var[t, k D + d]] (W_k x)[t, d], one thread per element; x: float32 / float64
+ * [total_frames x D] at ld_x; var as above, or null: no precision factor (the dynamic features of x); y: float64
+ * [total_frames x K D] at ld_y.  With var it is the tail of the backward pass: d L / d mean_k = P_k W_k z.
+ * Both return 0 without a launch when total_frames or n_utts is 0.
+ */
+int64_t mpx_mlpg_work_doubles(int64_t total_frames, int32_t D);
+int mpx_mlpg_solve(void* stream, const void* mean, int32_t mean_f64, int64_t ld_mean, const void* var, int32_t var_f64,
+                   int64_t ld_var, const int32_t* utt_frame_off, int32_t n_utts, int64_t total_frames, int32_t D,
+                   int32_t n_win, const double* windows, int32_t rhs_direct, double* out, int64_t ld_out, double* work);
+int mpx_mlpg_apply(void* stream, const void* x, int32_t x_f64, int64_t ld_x, const void* var, int32_t var_f64,
+                   int64_t ld_var, const int32_t* utt_frame_off, int32_t n_utts, int64_t total_frames, int32_t D,
+                   int32_t n_win, const double* windows, double* y, int64_t ld_y);
+
+/*
  * MagPhase post-filter (magphase.py:2300-2378, Q20) on [n_frames x dim] log-mel magnitudes.  half_len: int32
  * [nx_last - nx_first + 1] half lengths of the centred moving average of bins nx_first..nx_last (host table,
  * magphase.py:2342-2344); tilt: float32[dim] enhancement factors (np.linspace(boost_at_zero, boost_at_nyq, dim)).

@@ -122,6 +122,9 @@ PROTOTYPES = {
     "mpx_bw_probe_shapes": (i32, []),
     "mpx_rows_pack": (i32, [vp, vp, vp, i32, i32] + [vp, i32, i64, i64] * 3),
     "mpx_post_filter_merlin": (i32, [vp, vp, i64, i32] + [vp] * 4 + [i32, f64, vp, f64] + [vp] * 5),
+    "mpx_mlpg_work_doubles": (i64, [i64, i32]),
+    "mpx_mlpg_solve": (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, i64, i32, i32, vp, i32, vp, i64, vp]),
+    "mpx_mlpg_apply": (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i64]),
 }
 SYMBOLS = tuple(PROTOTYPES)
 # mpx_roundtrip_lossless_ola_flags: how the feature rows are stored (MPX_RT_STORE_ROWS, by line, MPX_RT_STORE_NT), by the

@@ -402,3 +402,46 @@ def analyze_compressed_type2(plan, sigs):
     plan.check_grad_dims()           # what has no backward pass says so before the forward is launched
     mag, real, imag, gain, _iters = _Type2CompressedAnalysis.apply(plan, *sigs)
     return (mag, real, imag), gain
+
+
+class _MLPG(torch.autograd.Function):
+    """forward(engine, var, streams, windows, width, *means): means = the [F_i x width] mean matrices of mp.mlpg_batch /
+    mp.mlpg_streams_batch (tensors or host arrays), var = the device variances ([width] or [sum F_i x width]), streams =
+    [(first column, D), ...].  Engine.mlpg_streams is the forward launch (one mpx_mlpg_solve per stream).  Output: the ONE
+    float64 [sum F_i x sum D] buffer of trajectories.  The backward pass keeps no factor: per stream it solves A z = g
+    again from the variances (mpx_mlpg_solve with the right-hand side given) and applies P_k W_k (mpx_mlpg_apply).  Kept:
+    the variances and the frame offsets -- MLPG is linear in the means, so the means themselves are not."""
+
+    @staticmethod
+    def forward(ctx, engine, var, streams, windows, width, *means):
+        import numpy as np
+
+        buf, offs = engine.mlpg_pack(list(means), width)
+        offs_dev = engine.to_device(offs.astype(np.int32), np.int32)
+        out = engine.mlpg_streams(buf, var, offs_dev, streams, windows)
+        ctx.engine, ctx.streams, ctx.windows, ctx.width = engine, streams, windows, width
+        ctx.offs = [int(o) for o in offs]
+        ctx.like = [(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else None for m in means]
+        ctx.save_for_backward(var, offs_dev)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        var, offs_dev = ctx.saved_tensors
+        n_head = 5   # engine, var, streams, windows, width
+        need_in = ctx.needs_input_grad[n_head:]
+        if grad_out.dtype != torch.float64 or grad_out.stride(1) != 1 or not grad_out.is_contiguous():
+            grad_out = grad_out.to(torch.float64).contiguous()
+        with torch.cuda.device(var.device):
+            g = ctx.engine.mlpg_streams_backward(grad_out, var, offs_dev, ctx.streams, ctx.windows, ctx.width)
+        out = []
+        for like, need, a, b in zip(ctx.like, need_in, ctx.offs[:-1], ctx.offs[1:]):
+            out.append(g[a:b].to(like[0]).reshape(like[1]) if like is not None and need else None)
+        return (None,) * n_head + tuple(out)
+
+
+def mlpg(engine, means, var, streams, windows, width):
+    """Engine.mlpg_streams on the packed means, differentiable with respect to the mean matrices that are tensors
+    requiring grad (the variances and the windows get no gradient).  -> the float64 [sum F_i x sum D] buffer with grad_fn."""
+    return _MLPG.apply(engine, var, streams, windows, int(width), *means)

@@ -1388,6 +1388,129 @@ class Engine:
                     int(max_iters), iters.contiguous(), grad_out, ld_g, gx, old, dec, env, old, tk)
         return (gx, dec, env) if (want_decisions or want_env) else gx
 
+    # ------------------------------------------------------------------ MLPG
+    def mlpg_pack(self, mats, width):
+        """List of [F_i x width] matrices (numpy, or device tensors; float32 / float64, any row stride) -> (ONE device
+        matrix [sum F_i x width], float64 if any of them is, else float32; row offsets int64 [n + 1]).  A batch of one
+        device tensor with unit column stride is not copied: the kernels read it where it lies.  Host matrices go up in
+        one copy; a mixed batch is gathered utterance by utterance."""
+        torch = _torch()
+        offs = np.concatenate(([0], np.cumsum([int(m.shape[0]) for m in mats]))).astype(np.int64)
+        total = int(offs[-1])
+        is_t = [torch.is_tensor(m) for m in mats]
+        f64 = any((m.dtype == torch.float64) if t else (np.asarray(m).dtype == np.float64) for m, t in zip(mats, is_t))
+        dt, ndt = (torch.float64, np.float64) if f64 else (torch.float32, np.float32)
+        if len(mats) == 1 and is_t[0] and mats[0].dtype == dt and (mats[0].shape[1] <= 1 or mats[0].stride(1) == 1) \
+                and (total <= 1 or mats[0].stride(0) >= width):
+            return mats[0].detach(), offs
+        if total == 0:
+            return torch.empty((0, width), dtype=dt, device=self.device), offs
+        if not any(is_t):
+            host = np.concatenate([np.asarray(m, dtype=ndt).reshape(-1, width) for m in mats], axis=0)
+            return self.to_device(host, ndt).view(total, width), offs
+        buf = torch.empty((total, width), dtype=dt, device=self.device)
+        for m, t, a, b in zip(mats, is_t, offs[:-1], offs[1:]):
+            if b > a:
+                src = m.detach() if t else torch.from_numpy(np.ascontiguousarray(m, dtype=ndt))
+                buf[int(a):int(b)].copy_(src, non_blocking=t)
+        return buf, offs
+
+    @staticmethod
+    def _mlpg_operand(t, width, what, total):
+        """(is_float64, row pitch) of a device operand of the MLPG entries: [total x >= width], unit column stride."""
+        torch = _torch()
+        if t.dtype not in (torch.float32, torch.float64):
+            raise TypeError("%s: float32 or float64 expected, got %s" % (what, t.dtype))
+        if t.dim() != 2 or int(t.shape[0]) != total or int(t.shape[1]) != width or (width > 1 and t.stride(1) != 1):
+            raise ValueError("%s: a [%d x %d] matrix with unit column stride expected, got %s"
+                             % (what, total, width, tuple(t.shape)))
+        return int(t.dtype == torch.float64), (int(t.stride(0)) if total > 1 else max(int(t.stride(0)), width))
+
+    def _mlpg_var(self, var, width, total):
+        torch = _torch()
+        if var.dim() == 1:   # the global variance: one row, pitch 0
+            if var.dtype not in (torch.float32, torch.float64) or int(var.numel()) != width or \
+                    (width > 1 and var.stride(0) != 1):
+                raise ValueError("mlpg: a global variance is one dense float32 / float64 row of %d values" % width)
+            return int(var.dtype == torch.float64), 0
+        return self._mlpg_operand(var, width, "mlpg: var", total)
+
+    def mlpg_solve(self, mean, var, offs_dev, D, windows, rhs=False, out=None, work=None):
+        """ONE mpx_mlpg_solve launch (k_mlpg_solve).  mean: device [total x K D] (a column slice of a wider
+        matrix is passed as the view it is; rhs: the right-hand side itself, [total x D]); var: device [K D] (global) or
+        [total x K D]; offs_dev: device int32 [n_utts + 1]; windows: hostmath.mlpg_windows(...).  -> out, float64 [total x D]
+        (given: a view with unit column stride, written in place).  work: float64 [>= mpx_mlpg_work_doubles]."""
+        torch = _torch()
+        total, K = int(mean.shape[0]), int(windows.shape[0]) + 1
+        m64, ld_m = self._mlpg_operand(mean, D if rhs else K * D, "mlpg: mean", total)
+        v64, ld_v = self._mlpg_var(var, K * D, total)
+        if out is None:
+            out = torch.empty((total, D), dtype=torch.float64, device=self.device)
+        o64, ld_o = self._mlpg_operand(out, D, "mlpg: out", total)
+        if not o64:
+            raise TypeError("mlpg: out must be float64")
+        need = int(self.lib.mpx_mlpg_work_doubles(total, D))
+        if work is None:
+            work = torch.empty(need, dtype=torch.float64, device=self.device)
+        if work.dtype != torch.float64 or int(work.numel()) < need or not work.is_contiguous():
+            raise ValueError("mlpg: work must be %d contiguous float64" % need)
+        wins = (ctypes.c_double * windows.size)(*[float(v) for v in windows.reshape(-1)])
+        self.launch("mpx_mlpg_solve", mean, m64, ld_m, var, v64, ld_v, offs_dev, int(offs_dev.numel()) - 1, total, int(D),
+                    K - 1, wins, int(bool(rhs)), out, ld_o, work)
+        return out
+
+    def mlpg_apply(self, x, var, offs_dev, D, windows, out=None):
+        """ONE mpx_mlpg_apply launch (k_mlpg_apply): y_k = [P_k] W_k x for every stream.  x: device [total x D]; var: None
+        (no precision factor: the dynamic features of x), or as mlpg_solve takes it.  -> out, float64 [total x K D]."""
+        torch = _torch()
+        total, K = int(x.shape[0]), int(windows.shape[0]) + 1
+        x64, ld_x = self._mlpg_operand(x, D, "mlpg: x", total)
+        v64, ld_v = (0, 0) if var is None else self._mlpg_var(var, K * D, total)
+        if out is None:
+            out = torch.empty((total, K * D), dtype=torch.float64, device=self.device)
+        o64, ld_o = self._mlpg_operand(out, K * D, "mlpg: y", total)
+        if not o64:
+            raise TypeError("mlpg: y must be float64")
+        wins = (ctypes.c_double * windows.size)(*[float(v) for v in windows.reshape(-1)])
+        self.launch("mpx_mlpg_apply", x, x64, ld_x, var, v64, ld_v, offs_dev, int(offs_dev.numel()) - 1, total, int(D),
+                    K - 1, wins, out, ld_o)
+        return out
+
+    def mlpg_streams(self, buf, var, offs_dev, streams, windows):
+        """MLPG of several streams of one packed matrix, one mpx_mlpg_solve launch per stream on column slices.  buf:
+        device [total x W]; var: device [W] or [total x W]; streams: [(first column, D), ...], stream s holding its K D
+        columns [static | delta | acc] from its first column.  -> float64 [total x sum D], the streams side by side."""
+        torch = _torch()
+        total, K = int(buf.shape[0]), int(windows.shape[0]) + 1
+        out = torch.empty((total, sum(d for _, d in streams)), dtype=torch.float64, device=self.device)
+        work = torch.empty(int(self.lib.mpx_mlpg_work_doubles(total, max(d for _, d in streams))), dtype=torch.float64,
+                           device=self.device)
+        o = 0
+        for c, d in streams:
+            v = var[c:c + K * d] if var.dim() == 1 else var[:, c:c + K * d]
+            self.mlpg_solve(buf[:, c:c + K * d], v, offs_dev, d, windows, out=out[:, o:o + d], work=work)
+            o += d
+        return out
+
+    def mlpg_streams_backward(self, grad_out, var, offs_dev, streams, windows, width):
+        """Gradient of mlpg_streams' output with respect to the packed means: per stream z = A^-1 g (the solve with the
+        right-hand side given, refactoring A from the variances) and P_k W_k z (mpx_mlpg_apply).  grad_out: float64
+        [total x sum D].  -> float64 [total x width]; columns of no stream are zero."""
+        torch = _torch()
+        total, K = int(grad_out.shape[0]), int(windows.shape[0]) + 1
+        covered = sum(K * d for _, d in streams) == width
+        g = (torch.empty if covered else torch.zeros)((total, width), dtype=torch.float64, device=self.device)
+        dmax = max(d for _, d in streams)
+        z = torch.empty((total, dmax), dtype=torch.float64, device=self.device)
+        work = torch.empty(int(self.lib.mpx_mlpg_work_doubles(total, dmax)), dtype=torch.float64, device=self.device)
+        o = 0
+        for c, d in streams:
+            v = var[c:c + K * d] if var.dim() == 1 else var[:, c:c + K * d]
+            self.mlpg_solve(grad_out[:, o:o + d], v, offs_dev, d, windows, rhs=True, out=z[:, :d], work=work)
+            self.mlpg_apply(z[:, :d], v, offs_dev, d, windows, out=g[:, c:c + K * d])
+            o += d
+        return g
+
     def warp_mag_matrix(self, mag_dim, H, alpha, b_mag_fbank_mel=False):
         """Device-resident [mag_dim x H] matrix of the magnitude compression and the name of the C entry point that goes
         with it: the cepstral mel warp (la.sp_mel_warp, mpx_mel_warp) or the mel filter bank (la.sp_mel_warp_fbank,

@@ -1364,3 +1364,125 @@ def true_envelope_check(H, in_type, ncoeffs):
     if int(ncoeffs) != ncoeffs or not 0 <= int(ncoeffs) <= N:
         raise ValueError("ncoeffs must be an integer in 0..%d (the FFT length), got %r" % (N, ncoeffs))
     return N
+
+
+# ---------------------------------------------------------------------------------------------
+# MLPG: argument checks of the public functions, all before any device call
+# ---------------------------------------------------------------------------------------------
+def mlpg_windows(windows):
+    """The dynamic windows of MLPG as a float64 [n_win x 3] array of taps (w[-1], w[0], w[+1]); n_win is 1 or 2."""
+    try:
+        w = np.array([[float(v) for v in row] for row in windows], dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("windows: one or two windows of three taps (w[-1], w[0], w[+1]) expected, got %r" % (windows,))
+    if w.ndim != 2 or w.shape[0] not in (1, 2) or w.shape[1] != 3:
+        raise ValueError("windows: one or two windows of three taps (w[-1], w[0], w[+1]) expected, got %r" % (windows,))
+    if not np.all(np.isfinite(w)):
+        raise ValueError("windows: every tap must be finite")
+    return w
+
+
+def _mlpg_matrix(m, name, width=None):
+    """One [F x width] operand of MLPG: a numpy array (any real dtype: float64 unless float32), or a torch tensor (float32 /
+    float64; a CPU tensor becomes a host array, a non-unit column stride is made contiguous)."""
+    import sys
+
+    torch = sys.modules.get("torch")
+    if torch is not None and torch.is_tensor(m):
+        if m.dtype not in (torch.float32, torch.float64):
+            raise ValueError("%s: dtype %s is not supported (float32 or float64)" % (name, m.dtype))
+        if m.dim() != 2:
+            raise ValueError("%s: must be 2-D [frames x width], got %d-D" % (name, m.dim()))
+        if m.device.type == "cpu":
+            m = m.detach().numpy()
+        elif m.shape[1] > 1 and m.stride(1) != 1:
+            m = m.contiguous()
+    else:
+        m = np.asarray(m)
+        if m.dtype.kind not in "fiu":
+            raise ValueError("%s: a real matrix expected, got dtype %s" % (name, m.dtype))
+        if m.dtype != np.float32:
+            m = m.astype(np.float64, copy=False)
+        if m.ndim != 2:
+            raise ValueError("%s: must be 2-D [frames x width], got %d-D" % (name, m.ndim))
+    if width is not None and int(m.shape[1]) != width:
+        raise ValueError("%s: %d columns expected, got %d" % (name, width, int(m.shape[1])))
+    return m
+
+
+def _mlpg_host_var_ok(v, name, cols=None):
+    if isinstance(v, np.ndarray):
+        x = v if cols is None else v[..., cols]
+        if not (np.all(np.isfinite(x)) and np.all(x > 0)):
+            raise ValueError("%s: every variance must be finite and > 0" % name)
+
+
+def mlpg_check(means, var, windows, what="mlpg_batch", width_of=None, var_cols=None):
+    """Checks of mlpg_batch / mlpg_streams_batch.  means: list of [F_i x width] matrices; var: one [width] vector or a
+    list of [F_i x width] matrices; width_of(width, K): checks the width and is what is returned as D (default: width / K).
+    Variances held in host arrays must be finite and > 0 (var_cols: in these columns only); those of device tensors are
+    NOT inspected.  -> (means, var, windows [n_win x 3], D, per_frame)."""
+    import sys
+
+    w = mlpg_windows(windows)
+    K = w.shape[0] + 1
+    if isinstance(means, np.ndarray) or not isinstance(means, (list, tuple)):
+        raise ValueError("%s: means must be a list of [frames x width] matrices" % what)
+    means = [_mlpg_matrix(m, "%s: means[%d]" % (what, i)) for i, m in enumerate(means)]
+    torch = sys.modules.get("torch")
+    is_t = torch is not None and torch.is_tensor(var)
+    per_frame = isinstance(var, (list, tuple)) and not (len(var) > 0 and np.isscalar(var[0]))
+    if not means:
+        return means, var, w, 0, per_frame
+    width = int(means[0].shape[1])
+    if any(int(m.shape[1]) != width for m in means):
+        raise ValueError("%s: every mean matrix must have the same number of columns" % what)
+    if width_of is None:
+        if width < K or width % K:
+            raise ValueError("%s: %d columns are not [static | delta | acc] blocks of %d streams" % (what, width, K))
+        D = width // K
+    else:
+        D = width_of(width, K)
+    if per_frame:
+        if len(var) != len(means):
+            raise ValueError("%s: var must be one vector or one matrix per utterance (%d given for %d utterances)"
+                             % (what, len(var), len(means)))
+        var = [_mlpg_matrix(v, "%s: var[%d]" % (what, i), width) for i, v in enumerate(var)]
+        for i, (v, m) in enumerate(zip(var, means)):
+            if int(v.shape[0]) != int(m.shape[0]):
+                raise ValueError("%s: var[%d] has %d rows, means[%d] has %d" % (what, i, v.shape[0], i, m.shape[0]))
+            _mlpg_host_var_ok(v, "%s: var[%d]" % (what, i), var_cols)
+    else:
+        if is_t:
+            if var.dtype not in (torch.float32, torch.float64) or var.dim() != 1 or int(var.numel()) != width:
+                raise ValueError("%s: var must be a float32 / float64 vector of %d values" % (what, width))
+            var = var.detach().numpy() if var.device.type == "cpu" else var.detach().contiguous()
+        else:
+            var = np.asarray(var)
+            if var.dtype.kind not in "fiu" or var.ndim != 1 or var.shape[0] != width:
+                raise ValueError("%s: var must be a vector of %d values (or a list of matrices)" % (what, width))
+            if var.dtype != np.float32:
+                var = var.astype(np.float64, copy=False)
+        _mlpg_host_var_ok(var, "%s: var" % what, var_cols)
+    return means, var, w, D, per_frame
+
+
+def mlpg_layout(layout, vuv, K, what="mlpg_streams_batch"):
+    """The streams of mlpg_streams_batch: layout = ((name, dim), ...), stream s in K dim_s columns [static | delta | acc]
+    one after the other, then one voicing column when vuv.  -> (layout as ((str, int), ...), [(first column, dim), ...],
+    the number of columns it asks for)."""
+    try:
+        layout = tuple((str(n), int(d)) for n, d in layout)
+    except (TypeError, ValueError):
+        raise ValueError("%s: layout must be ((name, dim), ...), got %r" % (what, layout))
+    if not layout or any(d < 1 for _, d in layout):
+        raise ValueError("%s: layout needs at least one stream and every dim >= 1" % what)
+    if len(set(n for n, _ in layout)) != len(layout):
+        raise ValueError("%s: stream names must differ" % what)
+    if any(n == "lf0" and d != 1 for n, d in layout) or (vuv and not any(n == "lf0" for n, _ in layout)):
+        raise ValueError("%s: the stream 'lf0' has dim 1, and vuv needs it in the layout" % what)
+    streams, c = [], 0
+    for _, d in layout:
+        streams.append((c, d))
+        c += K * d
+    return layout, streams, c + (1 if vuv else 0)

@@ -1400,3 +1400,169 @@ def get_num_of_frms_per_state(v_shift, lab_state_align_file, fs, b_prevent_zeros
     if b_prevent_zeros:
         v_n[v_n == 0] = 1
     return v_n
+
+
+# ---------------------------------------------------------------------------------------------
+# Maximum-likelihood parameter generation.  Stated here, not taken from Merlin / bandmat:
+# parity with Merlin's mlpg is UNPINNED.
+# ---------------------------------------------------------------------------------------------
+MLPG_WINDOWS = ((-0.5, 0.0, 0.5), (1.0, -2.0, 1.0))   # delta and acceleration, taps (w[-1], w[0], w[+1])
+
+
+def _mlpg_device_var(engine, var, per_frame, width):
+    return engine.mlpg_pack(var, width)[0] if per_frame else \
+        (var if not isinstance(var, np.ndarray) else engine.to_device(var, var.dtype))
+
+
+def _mlpg_run(engine, means, var, per_frame, w, streams, width, return_device):
+    """The launches of mlpg_batch / mlpg_streams_batch -> (float64 device buffer [sum F_i x sum D] (None when the batch has
+    no frames), packed means or None, row offsets)."""
+    import torch
+
+    offs = np.concatenate(([0], np.cumsum([int(m.shape[0]) for m in means]))).astype(np.int64)
+    if int(offs[-1]) == 0:
+        return None, None, offs
+    var_dev = _mlpg_device_var(engine, var, per_frame, width)
+    if return_device and torch.is_grad_enabled() and any(torch.is_tensor(m) and m.requires_grad for m in means):
+        from . import autograd
+
+        buf = None
+        out = autograd.mlpg(engine, means, var_dev, streams, w, width)
+    else:
+        buf, _ = engine.mlpg_pack(means, width)
+        out = engine.mlpg_streams(buf, var_dev, engine.to_device(offs.astype(np.int32), np.int32), streams, w)
+    return out, buf, offs
+
+
+def mlpg_batch(means, var, windows=MLPG_WINDOWS, engine=None, return_device=False):
+    """
+    Maximum-likelihood parameter generation on the device (k_mlpg_solve): the trajectory c = A^-1 b with
+    A = sum_k W_k^T P_k W_k and b = sum_k W_k^T P_k mu_k over the K = 1 + len(windows) streams (static, then one per
+    three-tap window (w[-1], w[0], w[+1])); window taps that fall outside an utterance are dropped.
+    means: list of [F_i x K D] matrices, columns [static D | delta D | acc D], each a numpy array or a device tensor
+    (float32 / float64, any row stride); one D per call.  var: ONE [K D] vector (the global variance), or a list of
+    [F_i x K D] matrices (per-frame variances; also the way to another boundary convention).  Variances in host arrays must
+    be finite and > 0 (ValueError, before any device call); variances in DEVICE tensors are not inspected.
+    Returns a list of [F_i x D] float64 arrays (return_device: float64 device tensors, views of one buffer); an utterance
+    without frames gives a (0, D) result.
+    Autograd: with return_device, grad mode on and a device mean matrix that requires grad, the results carry a grad_fn
+    and backward() gives each mean matrix a gradient in its own dtype and shape (dL/dmu_k = P_k W_k A^-1 dL/dc); the
+    forward values are the same bits either way.  Variances and windows get no gradient; no double backward.
+    Not Merlin's code: the mathematics is restated, parity with Merlin / bandmat is unpinned.
+    """
+    means, var, w, D, per_frame = hm.mlpg_check(means, var, windows, "mlpg_batch")
+    if not means:
+        return []
+    engine = engine or get_engine()
+    K = w.shape[0] + 1
+    out, _buf, offs = _mlpg_run(engine, means, var, per_frame, w, [(0, D)], K * D, return_device)
+    if out is None:
+        if return_device:
+            import torch
+
+            return [torch.zeros((0, D), dtype=torch.float64, device=engine.device) for _ in means]
+        return [np.zeros((0, D)) for _ in means]
+    rows = [out[int(a):int(b)] for a, b in zip(offs[:-1], offs[1:])]
+    if return_device:
+        return rows
+    host = out.cpu().numpy()
+    return [host[int(a):int(b)] for a, b in zip(offs[:-1], offs[1:])]
+
+
+def mlpg(m_mean, var, windows=MLPG_WINDOWS):
+    """mlpg_batch for one utterance: [F x K D] means, [K D] or [F x K D] variances -> [F x D] float64."""
+    per_frame = getattr(var, "ndim", None) == 2 or (hasattr(var, "dim") and var.dim() == 2)
+    return mlpg_batch([m_mean], [var] if per_frame else var, windows=windows)[0]
+
+
+def dynamic_features_batch(mats, windows=MLPG_WINDOWS, engine=None, return_device=False):
+    """
+    The static / delta / acceleration features of MLPG's own windows (k_mlpg_apply, no precision factor): every [F_i x D]
+    matrix (numpy or device tensor, float32 / float64) -> [F_i x K D] float64, columns [static | delta | acc], window taps
+    outside the utterance dropped -- what mlpg_batch inverts: mlpg_batch(dynamic_features_batch(x), any variances) == x.
+    """
+    w = hm.mlpg_windows(windows)
+    if isinstance(mats, np.ndarray) or not isinstance(mats, (list, tuple)):
+        raise ValueError("dynamic_features_batch: mats must be a list of [frames x D] matrices")
+    mats = [hm._mlpg_matrix(m, "dynamic_features_batch: mats[%d]" % i) for i, m in enumerate(mats)]
+    if not mats:
+        return []
+    D, K = int(mats[0].shape[1]), w.shape[0] + 1
+    if D < 1 or any(int(m.shape[1]) != D for m in mats):
+        raise ValueError("dynamic_features_batch: every matrix must have the same number (>= 1) of columns")
+    engine = engine or get_engine()
+    import torch
+
+    x, offs = engine.mlpg_pack(mats, D)
+    total = int(offs[-1])
+    if total == 0:
+        out = torch.zeros((0, K * D), dtype=torch.float64, device=engine.device)
+    else:
+        out = engine.mlpg_apply(x, None, engine.to_device(offs.astype(np.int32), np.int32), D, w)
+    if not return_device:
+        out = out.cpu().numpy()
+    return [out[int(a):int(b)] for a, b in zip(offs[:-1], offs[1:])]
+
+
+def dynamic_features(m, windows=MLPG_WINDOWS):
+    """dynamic_features_batch for one matrix."""
+    return dynamic_features_batch([m], windows=windows)[0]
+
+
+MLPG_LAYOUT = (("mag", 60), ("real", 10), ("imag", 10), ("lf0", 1))
+
+
+def mlpg_streams_batch(cmps, var, layout=MLPG_LAYOUT, vuv=True, vuv_thres=0.5, windows=MLPG_WINDOWS, engine=None,
+                       return_device=False):
+    """
+    MLPG of an acoustic model's whole output rows.  cmps: list of [F_i x W] matrices (numpy or device tensors, as
+    mlpg_batch takes them); stream s of layout = ((name, dim), ...) occupies K dim_s columns [static | delta | acc], the
+    streams in layout order, then ONE static voicing column when vuv is set.  var: one [W] vector or a list of [F_i x W]
+    matrices (the voicing column's entries are not used and not checked).  One mpx_mlpg_solve launch per stream, on column
+    slices of the same packed matrix.
+    Returns per utterance the tuple of trajectories in layout order -- with the default layout (m_mag_mel_log, m_real_mel,
+    m_imag_mel, v_lf0), exactly what synthesis_from_compressed_batch takes: [F_i x dim] float64 matrices, a stream named
+    'lf0' as a vector, set to the unvoiced value of la.f0_to_lf0 (-1e10) where the voicing column is <= vuv_thres.
+    return_device: device tensors (column slices of one float64 buffer; v_lf0 a float64 device vector), which the synthesis
+    reads where they lie.  Autograd as in mlpg_batch (the voicing decision is not differentiated; unvoiced frames send no
+    gradient to lf0).
+    """
+    import torch
+
+    K = hm.mlpg_windows(windows).shape[0] + 1
+    layout, streams, need = hm.mlpg_layout(layout, vuv, K)
+    if isinstance(vuv_thres, bool) or not isinstance(vuv_thres, (int, float)) or not np.isfinite(vuv_thres):
+        raise ValueError("mlpg_streams_batch: vuv_thres must be a finite number")
+
+    def width_of(width, _k):
+        if width != need:
+            raise ValueError("mlpg_streams_batch: the layout asks for %d columns, the matrices have %d" % (need, width))
+        return 0
+
+    means, var, w, _D, per_frame = hm.mlpg_check(cmps, var, windows, "mlpg_streams_batch", width_of=width_of,
+                                                 var_cols=slice(0, need - (1 if vuv else 0)))
+    if not means:
+        return []
+    width = int(means[0].shape[1])
+    engine = engine or get_engine()
+    out, buf, offs = _mlpg_run(engine, means, var, per_frame, w, streams, width, return_device)
+    if out is None:
+        z = [np.zeros(0) if n == "lf0" else np.zeros((0, d)) for n, d in layout]
+        if return_device:
+            z = [torch.from_numpy(a).to(engine.device) for a in z]
+        return [tuple(z) for _ in means]
+    cols, o = [], 0
+    for n, d in layout:
+        c = out[:, o:o + d]
+        if n == "lf0" and d == 1:
+            c = c[:, 0]
+            if vuv:
+                if buf is None:
+                    buf, _ = engine.mlpg_pack(means, width)
+                voiced = buf[:, width - 1].detach() > float(vuv_thres)
+                c = torch.where(voiced, c, torch.full((), la.MAGIC, dtype=torch.float64, device=engine.device))
+        cols.append(c)
+        o += d
+    if not return_device:
+        cols = [c.cpu().numpy() for c in cols]
+    return [tuple(c[int(a):int(b)] for c in cols) for a, b in zip(offs[:-1], offs[1:])]
