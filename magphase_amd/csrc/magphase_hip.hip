@@ -788,8 +788,8 @@ __global__ __launch_bounds__(256) void k_ola_gather(const float* __restrict__ fr
 // out[c] = (1 - t[c]) rows[r0[c]] + t[c] rows[r1[c]] for the three feature streams, one wavefront per output row.  A pure
 // stream: each lane moves whole 16-byte groups of the row (64 x 16 B = 1 KB contiguous per wave-instruction; the dense
 // feature pitch leaves rows only 4-byte aligned, which dwordx4 accesses allow), the last H mod 4 columns one float each.
-// Neighbouring output rows share source rows: those re-reads come from L2.  r0 == r1 reads the row once (t x 0 = 0: the
-// result is the row itself either way).
+// Neighbouring output rows share source rows: those re-reads come from L2.  r0 == r1 reads the row once and copies it: the
+// result is the row itself, bit for bit, in the 16-byte groups and in the last columns alike.
 // ---------------------------------------------------------------------------------------------
 typedef float f4a4 __attribute__((ext_vector_type(4), aligned(4)));
 constexpr int kLerpWaves = 4;
@@ -837,11 +837,17 @@ __global__ __launch_bounds__(kLerpWaves * 64) void k_rows_lerp(int H, const floa
             *reinterpret_cast<f4a4*>(di + od + 4 * v) = z;
         }
     }
-    const int k = 4 * nv + lane;   // the last H mod 4 columns
-    if (k < H) {
-        dm[od + k] = fmaf(sm[ob + k] - sm[oa + k], t, sm[oa + k]);
-        dr[od + k] = fmaf(sr[ob + k] - sr[oa + k], t, sr[oa + k]);
-        di[od + k] = fmaf(si[ob + k] - si[oa + k], t, si[oa + k]);
+    const int k = 4 * nv + lane;   // the last H mod 4 columns, by the same two arms (a == b: a copy, whatever the value --
+    if (k < H) {                   // fma(x - x, t, x) would turn -0.0 into +0.0 and an infinity into NaN)
+        if (a == b) {
+            dm[od + k] = sm[oa + k];
+            dr[od + k] = sr[oa + k];
+            di[od + k] = si[oa + k];
+        } else {
+            dm[od + k] = fmaf(sm[ob + k] - sm[oa + k], t, sm[oa + k]);
+            dr[od + k] = fmaf(sr[ob + k] - sr[oa + k], t, sr[oa + k]);
+            di[od + k] = fmaf(si[ob + k] - si[oa + k], t, si[oa + k]);
+        }
     }
 }
 

@@ -107,17 +107,23 @@ __device__ __forceinline__ void block_frame_range(long long nframes, long long& 
 // ---------------------------------------------------------------------------------------------
 // analysis
 // ---------------------------------------------------------------------------------------------
-// sin(pi t / 2)^2 = 0.5 + 0.5 sin(pi (t - 0.5)) for t in [0,1]: one odd degree-9 polynomial for sin(pi u) on
-// u in [-0.5, 0.5] (least squares on Chebyshev nodes, |err| < 4e-9; 1.2e-7 after fp32 evaluation), no range
-// reduction, no branches: 8 VALU per window sample.
+// sin(pi t / 2)^2 for t in [0,1] from one odd degree-9 polynomial for sin(pi u) on u in [-0.5, 0.5] (least squares on
+// Chebyshev nodes, |err| < 4e-9), evaluated at one of two arguments:
+//   t >= 0.375:  0.5 + 0.5 sin(pi (t - 0.5))   absolute error <= 1.2e-7 where the weight is >= 0.31
+//   t <  0.375:  sin(pi t / 2)^2               relative error of a few 2^-24 however small the weight, exactly 0 at t == 0
+// (the first form alone is good to 1.2e-7 of FULL SCALE: a weight of 1e-6 came out several per cent off and the weight at
+// t == 0 was 2^-25, not 0).  No range reduction, no branches: 8 VALU and 3 selects / compares per window sample; t == 1
+// gives exactly 1.
 __device__ __forceinline__ float sin2_halfpi(float t) {
-    const float u = t - 0.5f;
+    const bool low = t < 0.375f;
+    const float u = low ? 0.5f * t : t - 0.5f;
     const float u2 = u * u;
     float p = fmaf(u2, 7.721838616e-02f, -5.980441939e-01f);
     p = fmaf(u2, p, 2.550031194e+00f);
     p = fmaf(u2, p, -5.167706866e+00f);
     p = fmaf(u2, p, 3.141592580e+00f);
-    return fmaf(0.5f * u, p, 0.5f);
+    const float s = u * p;   // sin(pi u)
+    return low ? s * s : fmaf(0.5f, s, 0.5f);
 }
 
 // Half windows of libaudio.py:70-84 evaluated analytically.  t = k/L on the rising half (k <= L; t = 1 when L == 0:
