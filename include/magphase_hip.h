@@ -766,6 +766,23 @@ int mpx_min_phase(void* stream, int fft_len, const void* tables, const float* ma
                   float* out_imag, int64_t ld /* row pitch of mag and of the three outputs, floats */);
 
 /*
+ * Backward pass of mpx_min_phase with respect to the magnitude row it was computed from (the row interpolation is not
+ * part of it: mpx_rows_lerp_adjoint), one wavefront per frame.  mag / real / imag: mpx_min_phase's own outputs
+ * (m, cos phi, sin phi), [n_frames x H] at row pitch ld, H = fft_len / 2 + 1.  grad_m / grad_a / grad_b: the gradients with
+ * respect to those three rows, at row pitch ld_grad; columns of grad_a / grad_b at or beyond n_phase (0 <= n_phase <= H)
+ * are not read and count as zero (mpx_synthesis_compressed_backward writes min(n_per rounded up to 64, H) columns).
+ * A null grad_a or grad_b is zero -- both null: grad_mag = grad_m, no transform -- and so is a null grad_m.
+ * grad_mag[f][k] = grad_m[f][k] + (T^t g_phi)[k] / m[k] where m[k] > 0, grad_m[f][k] elsewhere, with
+ * g_phi = grad_b cos phi - grad_a sin phi (0 at bins 0 and fft_len / 2) and T the linear map ln m -> phi
+ * (DESIGN.md section 3.3o).  [n_frames x H] at row pitch ld_out; every element is written exactly once, no atomics,
+ * nothing outside columns 0 .. H - 1.  grad_mag may be grad_m itself (same pointer and ld_out == ld_grad), no other overlap.
+ * Returns 0 without a launch when n_frames is 0.
+ */
+int mpx_min_phase_backward(void* stream, int fft_len, const void* tables, const float* mag, const float* real,
+                           const float* imag, int64_t ld, const float* grad_m, const float* grad_a, const float* grad_b,
+                           int64_t ld_grad, int32_t n_phase, int64_t n_frames, float* grad_mag, int64_t ld_out);
+
+/*
  * True envelope (la.true_envelope, libaudio.py:295-340), one wavefront per frame.  For each row of in ([n_frames x H],
  * H = fft_len / 2 + 1, row pitch ld_in): v = the row in dB (in_type 0: 20 log10 x, 1: x, 2: (20 / ln 10) x); then up
  * to max_iters passes of sm = Re FFT(weights . IFFT(even extension of v))[0..H-1] (la.spectral_smoothing_rceps),

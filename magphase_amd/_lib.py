@@ -105,6 +105,7 @@ PROTOTYPES = {
     "mpx_mel_unwarp_backward": (i32, [vp, i32, vp, i64, vp, i64, vp, i32, i64, vp, vp, vp, i64, i32, vp, i32, i64, vp, vp]),
     "mpx_phase_grad_mask": (i32, [vp, i64, i32] + [vp] * 7),
     "mpx_min_phase": (i32, [vp, i32] + [vp] * 5 + [i64, vp, vp, vp, i64]),
+    "mpx_min_phase_backward": (i32, [vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, i32, i64, vp, i64]),
     "mpx_true_envelope": (i32, [vp, i32, vp, vp, vp, i64, i64, i32, f64, i32, vp, i64, vp, vp, vp]),
     "mpx_true_envelope_backward": (i32, [vp, i32, vp, vp, vp, i64, i64, i32, i32, vp, vp, i64, vp, i64, vp, vp, i64, vp]),
     "mpx_frame_gain": (i32, [vp, i32] + [vp] * 5 + [i64, vp, i32]),

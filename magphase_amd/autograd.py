@@ -60,8 +60,18 @@ kernels run over the two-period and the one-period frame table and the two sampl
 first runs the tail of the type-1 compressed backward on the type-2 row tables.  Not differentiable: v_pm_sec, v_voi, fs,
 the per-frame gain.
 
-No double backward.  The compressed synthesis with per_phase_type 'min_phase' / 'linear', with a
-post-filter, with pcm16_norm or with prepared=, and the constant-rate lossless analysis, have no backward pass.
+Magnitude-only synthesis (section 3.3o): a Function around the unchanged forward of synthesis_from_mag_batch
+(MagnitudeSynthesisPlan.run() -- the compressed plan with per_phase_type 'min_phase' / 'linear' -- and the output
+high-pass), with the gradient with respect to m_mag_mel_log computed by MagnitudeSynthesisPlan.run_backward:
+k_synth_comp_bwd against the rows the pair kernel read, k_min_phase_bwd (the adjoint of the minimum-phase stage, in
+place on the magnitude gradient rows; 'min_phase' only), k_rows_lerp_adjoint and k_mel_unwarp_bwd's magnitude job.  And a
+Function around la.build_min_phase_from_mag_spec_batch's one mpx_min_phase launch, magnitude rows -> unit phasor rows,
+with mpx_min_phase_backward as its backward.  Where m <= 0 the phase gets no gradient (the protected logarithm is a
+constant there).  Not differentiable: v_lf0, fs, the noise and its gains.
+
+No double backward.  synthesis_from_compressed_batch with per_phase_type 'min_phase' / 'linear' (synthesis_from_mag_batch
+is the differentiable form), any synthesis with a post-filter, with pcm16_norm or with prepared=, and the constant-rate
+lossless analysis, have no backward pass.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -445,3 +455,81 @@ def mlpg(engine, means, var, streams, windows, width):
     """Engine.mlpg_streams on the packed means, differentiable with respect to the mean matrices that are tensors
     requiring grad (the variances and the windows get no gradient).  -> the float64 [sum F_i x sum D] buffer with grad_fn."""
     return _MLPG.apply(engine, var, streams, windows, int(width), *means)
+
+
+class _MagnitudeSynthesis(torch.autograd.Function):
+    """forward(plan, b_out_hpf, n_utts, *mats): plan = a MagnitudeSynthesisPlan built from the utterances whose
+    m_mag_mel_log are mats (tensors or host arrays; the plan holds them packed as float32 device rows already); plan.run()
+    and Engine.output_hpf are the forward, plan.adjoint_hpf and plan.run_backward (k_synth_comp_bwd, k_min_phase_bwd,
+    k_rows_lerp_adjoint, k_mel_unwarp_bwd: DESIGN.md section 3.3o) the backward.  Output: the ONE [total_out] waveform
+    buffer (float64 after the high-pass, float32 without it); the per-utterance signals are views of it."""
+
+    @staticmethod
+    def forward(ctx, plan, b_out_hpf, n_utts, *mats):
+        pcm = plan.run()
+        if b_out_hpf:
+            pcm = plan.engine.output_hpf(pcm, plan.out_off_host, plan.fs)
+        ctx.plan, ctx.hpf = plan, bool(b_out_hpf)
+        ctx.rows = [int(m.shape[0]) for m in mats]
+        ctx.like = [(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else None for m in mats]
+        return pcm
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        plan = ctx.plan
+        n_head = 3   # plan, b_out_hpf, n_utts
+        need_in = ctx.needs_input_grad[n_head:]
+        with torch.cuda.device(grad_out.device):
+            g = plan.adjoint_hpf(grad_out) if ctx.hpf else grad_out.to(torch.float32)
+            g = plan.run_backward(g.contiguous())
+        out, a = [], 0
+        for like, need, n in zip(ctx.like, need_in, ctx.rows):
+            out.append(g[a:a + n].to(like[0]).reshape(like[1]) if like is not None and need else None)
+            a += n
+        return (None,) * n_head + tuple(out)
+
+
+def synthesize_from_mag(plan, b_out_hpf, utts):
+    """plan.run() of a MagnitudeSynthesisPlan (and the output high-pass), differentiable with respect to the
+    m_mag_mel_log in utts = [(m_mag_mel_log, v_lf0)] that are tensors requiring grad.  Returns the [total_out] waveform
+    buffer (with grad_fn)."""
+    plan.check_differentiable()      # what has no backward pass says so before the forward is launched
+    return _MagnitudeSynthesis.apply(plan, bool(b_out_hpf), len(utts), *[u[0] for u in utts])
+
+
+class _MinPhase(torch.autograd.Function):
+    """forward(engine, *mats): mats = the [F_i x H] magnitude matrices of la.build_min_phase_from_mag_spec_batch (tensors or
+    host arrays); Engine.min_phase_rows (ONE mpx_min_phase launch over all rows) is the forward, mpx_min_phase_backward the
+    backward.  Outputs: the unit phasor rows (cos phi, sin phi) of all matrices, float32 [sum F_i x H] views at the spectra's
+    row pitch; the product with the magnitudes is the caller's (plain torch).  Kept for the backward pass: the three rows
+    the forward wrote."""
+
+    @staticmethod
+    def forward(ctx, engine, *mats):
+        o_m, o_r, o_i = engine.min_phase_rows(list(mats))
+        ctx.engine = engine
+        ctx.rows = [int(m.shape[0]) for m in mats]
+        ctx.like = [(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else None for m in mats]
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(o_m, o_r, o_i)
+        return o_r, o_i
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_r, g_i):
+        o_m, o_r, o_i = ctx.saved_tensors
+        need_in = ctx.needs_input_grad[1:]
+        with torch.cuda.device(o_m.device):
+            g = ctx.engine.min_phase_backward(o_m, o_r, o_i, None, g_r, g_i)
+        out, a = [], 0
+        for like, need, n in zip(ctx.like, need_in, ctx.rows):
+            out.append(g[a:a + n].to(like[0]).reshape(like[1]) if like is not None and need else None)
+            a += n
+        return (None,) + tuple(out)
+
+
+def min_phase(engine, mats):
+    """Engine.min_phase_rows on mats, differentiable with respect to the matrices that are tensors requiring grad.
+    Returns the float32 (cos phi, sin phi) row matrices of the whole batch (with grad_fn)."""
+    return _MinPhase.apply(engine, *mats)

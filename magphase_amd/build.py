@@ -25,7 +25,7 @@ CSRC = os.path.join(HERE, "csrc")
 # Slowest first (single-job compile times, docs/LAB_NOTES.md: 47, 46, 36, 8, 7, 5 s, the rest 2-4 s each): the pool below
 # runs 8 compiles at a time, and a long unit started last would set the wall time of a clean build.
 UNITS = ["magphase_f64.hip", "magphase_warp.hip", "magphase_comp.hip", "magphase_hip.hip", "magphase_grad.hip",
-         "magphase_grad_comp.hip",
+         "magphase_grad_comp.hip", "magphase_grad_minphase.hip",
          "magphase_true_env.hip", "magphase_plan.cpp", "magphase_mtjump.cpp", "magphase_output.hip", "magphase_host.cpp",
          "magphase_epochs.hip", "magphase_noise.hip", "magphase_pack.hip", "magphase_probe.hip", "magphase_type2.hip",
          "magphase_merlin.hip", "magphase_mlpg.hip"]

@@ -1323,6 +1323,51 @@ class Engine:
         m = self.to_host_f64(o_m[:, :H])
         return m * (self.to_host_f64(o_r[:, :H]) + 1j * self.to_host_f64(o_i[:, :H]))
 
+    def min_phase_rows(self, mats):
+        """la.build_min_phase_from_mag_spec for a list of [F_i x H] magnitude matrices (host arrays or tensors on this
+        device, any of pack_rows' dtypes) through ONE mpx_min_phase launch -> (m, cos phi, sin phi), float32 [sum F_i x H]
+        views of rows at mpx_spec_ld(H)."""
+        torch = _torch()
+        H = int(mats[0].shape[1])
+        if any(m.ndim != 2 or int(m.shape[1]) != H for m in mats):
+            raise ValueError("min_phase_rows: every matrix must be [F x %d]" % H)
+        N = 2 * (H - 1)
+        F = int(sum(int(m.shape[0]) for m in mats))
+        ld = int(self.lib.mpx_spec_ld(H))
+        mag = self.empty((F, ld))[:, :H]
+        if any(torch.is_tensor(m) for m in mats):
+            self.pack_rows([list(mats)], [mag])
+        elif F:
+            mag.copy_(torch.from_numpy(np.concatenate([np.asarray(m, dtype=np.float32) for m in mats], axis=0)))
+        o_m, o_r, o_i = (self.empty((F, ld))[:, :H] for _ in range(3))
+        if F:
+            ident = torch.arange(F, dtype=torch.int32, device=self.device)
+            zeros_t = torch.zeros(F, dtype=torch.float32, device=self.device)
+            self.launch("mpx_min_phase", N, self.tables(N), mag, ident, ident, zeros_t, F, o_m, o_r, o_i, ld)
+        return o_m, o_r, o_i
+
+    def min_phase_backward(self, o_m, o_r, o_i, g_m, g_r, g_i, n_phase=None):
+        """mpx_min_phase_backward (k_min_phase_bwd): (o_m, o_r, o_i) = mpx_min_phase's own output rows ([F x H] views of one
+        pitch), (g_m, g_r, g_i) the gradients with respect to them ([F x H], None: zero) -> the gradient with respect to the
+        magnitude rows, float32 [F x H] (a view of rows at the outputs' pitch)."""
+        torch = _torch()
+        F, H = int(o_m.shape[0]), int(o_m.shape[1])
+        N = 2 * (H - 1)
+        ld = self.feat_ld(o_m, o_r, o_i)
+        gs = [None if g is None else g.to(torch.float32) for g in (g_m, g_r, g_i)]
+        have = [g for g in gs if g is not None]
+        if any(tuple(g.shape) != (F, H) for g in have):
+            raise ValueError("min_phase_backward: gradients must be [%d x %d]" % (F, H))
+        if have and (any(g.stride(1) != 1 for g in have) or len({int(g.stride(0)) for g in have}) > 1
+                     or int(have[0].stride(0)) < H):
+            gs = [None if g is None else g.contiguous() for g in gs]
+            have = [g for g in gs if g is not None]
+        out = self.empty((F, ld))[:, :H]
+        if F:
+            self.launch("mpx_min_phase_backward", N, self.tables(N), o_m, o_r, o_i, ld, gs[0], gs[1], gs[2],
+                        int(have[0].stride(0)) if have else H, H if n_phase is None else int(n_phase), F, out, ld)
+        return out
+
     def true_envelope(self, mats, in_type="abs", ncoeffs=60, thres_db=0.1, fade=0.7, max_iters=hm.TRUE_ENV_MAX_ITERS,
                       forced_iters=None, want_iters=False, ticket=True, return_input=False):
         """

@@ -387,6 +387,54 @@ def build_min_phase_from_mag_spec(m_mag):
     return get_engine().min_phase_single(np.asarray(m_mag, dtype=np.float64))
 
 
+def build_min_phase_from_mag_spec_batch(l_m_mag, return_device=False, engine=None):
+    """
+    build_min_phase_from_mag_spec for a list of [F_i x H] magnitude matrices in ONE mpx_min_phase launch (the single call
+    uploads and launches once per matrix).  Host arrays or tensors on the engine's device (float32 / float16 / bfloat16 /
+    float64, any row stride).  Returns per matrix the complex128 [F_i x H] spectrum the single call returns, or with
+    return_device=True the float32 device pair (real, imag) of m e^{j phi}.
+    Autograd: with return_device, grad mode on and a device matrix that requires grad, the pairs carry a grad_fn and
+    backward() reaches the magnitudes, in each one's own dtype and shape: the phasor rows through k_min_phase_bwd
+    (mpx_min_phase_backward), the product with m in plain torch.  Where m <= 0 the phase takes the
+    protected logarithm's constant and gets no gradient.  No double backward.
+    """
+    import sys
+
+    from .engine import get_engine
+    e = engine or get_engine()
+    mats = list(l_m_mag)
+    if not mats:
+        return []
+    torch = sys.modules.get("torch")
+    is_t = [torch is not None and torch.is_tensor(m) for m in mats]
+    for k, m in enumerate(mats):
+        if is_t[k]:
+            if m.device.type == "cpu":
+                m = m.detach()
+                mats[k], is_t[k] = (m.float() if m.element_size() == 2 else m).numpy(), False
+        else:
+            mats[k] = np.atleast_2d(np.asarray(m))
+    offs = np.concatenate(([0], np.cumsum([int(m.shape[0]) for m in mats]))).astype(np.int64)
+    want_grad = bool(return_device and torch is not None and torch.is_grad_enabled()
+                     and any(t and m.requires_grad for t, m in zip(is_t, mats)))
+    if want_grad:
+        from .autograd import min_phase
+
+        o_m, (o_r, o_i) = None, min_phase(e, mats)
+    else:
+        o_m, o_r, o_i = e.min_phase_rows(mats)
+    if not return_device:
+        m, c, s = (e.to_host_f64(x) for x in (o_m, o_r, o_i))
+        full = m * (c + 1j * s)
+        return [full[int(a):int(b)] for a, b in zip(offs[:-1], offs[1:])]
+    out = []
+    for k, (a, b) in enumerate(zip(offs[:-1], offs[1:])):
+        a, b = int(a), int(b)
+        m = mats[k].to(torch.float32) if is_t[k] else e.to_device(np.asarray(mats[k], dtype=np.float32), np.float32)
+        out.append((m * o_r[a:b], m * o_i[a:b]))
+    return out
+
+
 def gen_non_symmetric_win(left_len, right_len, win_func, b_norm=False):
     """libaudio.py:70-84: rising half of win_func(1 + 2 left) joined to the falling half of win_func(1 + 2 right)."""
     left_len, right_len = int(left_len), int(right_len)

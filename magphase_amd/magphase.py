@@ -24,7 +24,7 @@ from .hostmath import check_const_rate_ms
 from .hostplan import plan_const_rate_synthesis
 from .plans import (CompressedAnalysisPlan, CompressedSynthesisPlan, GriffinLimPlan, LosslessAnalysisPlan,
                     LosslessConstRateAnalysisPlan, LosslessConstRateSynthesisPlan, LosslessRoundTripPlan,
-                    LosslessSynthesisPlan, Type2AnalysisPlan, Type2CompressedAnalysisPlan, Type2SynthesisPlan,
+                    LosslessSynthesisPlan, MagnitudeSynthesisPlan, Type2AnalysisPlan, Type2CompressedAnalysisPlan, Type2SynthesisPlan,
                     check_type2_grad_dims)
 
 _epoch_provider = None
@@ -882,6 +882,78 @@ def synthesis_from_compressed(m_mag_mel_log, m_real_mel, m_imag_mel, v_lf0, fs, 
                                            b_voi_ap_win=b_voi_ap_win, b_const_rate=b_const_rate,
                                            alpha_phase=alpha_phase, b_out_hpf=b_out_hpf,
                                            per_phase_type=per_phase_type, b_fbank_mel=b_fbank_mel)[0]
+
+
+_MAG_NAMES = ("m_mag_mel_log", "v_lf0")
+
+
+def synthesis_from_mag_batch(utts, fs, fft_len=None, phase='min_phase', b_voi_ap_win=True, b_const_rate=False,
+                             b_out_hpf=True, noise=None, engine=None, b_post_filter=False, b_fbank_mel=False,
+                             noise_mode='reference', noise_seeds=None, pcm16_norm=False, return_device=False):
+    """Batched synthesis from the magnitudes alone; utts: list of (m_mag_mel_log, v_lf0).  phase: 'min_phase' -- the
+    periodic component takes the complex-cepstrum minimum phase of the unwarped magnitude (per_phase_type='min_phase',
+    magphase.py:937-938) -- or 'zero' (per_phase_type='linear', magphase.py:933-936); ValueError otherwise.  The samples
+    are those of synthesis_from_compressed_batch with that per_phase_type, whatever phase matrices it is given, bit for
+    bit.  Every other argument as synthesis_from_compressed_batch takes it: host arrays or device tensors (float32 /
+    float16 / bfloat16 / float64, any row stride; column slices are read where they lie), return_device, pcm16_norm,
+    noise / noise_mode / noise_seeds, b_post_filter, b_fbank_mel.
+    Autograd: with return_device, grad mode on and a device m_mag_mel_log that requires grad, the signals carry a grad_fn
+    and tensor.backward() reaches m_mag_mel_log, in its own dtype and shape (magphase_amd/autograd.py, DESIGN.md section
+    3.3o: k_synth_comp_bwd, k_min_phase_bwd, k_rows_lerp_adjoint, k_mel_unwarp_bwd; through the output high-pass'
+    adjoint with b_out_hpf).  The forward launches and their samples are the same.  Not differentiable: v_lf0, fs, the
+    noise and its gains.  NotImplementedError, naming the argument, for a truthy b_post_filter or pcm16_norm under grad
+    and for mag_dim > 64.  No double backward."""
+    if phase not in ('min_phase', 'zero'):
+        raise ValueError("phase must be 'min_phase' or 'zero', not %r" % (phase,))
+    utts = [tuple(u) for u in utts]
+    if any(len(u) != 2 for u in utts):
+        raise ValueError("utts: a list of (m_mag_mel_log, v_lf0)")
+    import sys
+
+    torch = sys.modules.get("torch")
+    want_grad = bool(return_device and torch is not None and torch.is_grad_enabled()
+                     and any(torch.is_tensor(u[0]) and u[0].requires_grad and u[0].device.type != "cpu" for u in utts))
+    if want_grad:   # what has no backward pass says so before anything is built
+        if b_post_filter and b_post_filter != 'no':
+            raise NotImplementedError("b_post_filter=%r has no backward pass" % (b_post_filter,))
+        if pcm16_norm is not False:
+            raise NotImplementedError("pcm16_norm=%r (int16 output) has no backward pass" % (pcm16_norm,))
+        for i, u in enumerate(utts):
+            if len(np.shape(u[0])) == 2 and int(np.shape(u[0])[1]) > 64:
+                raise NotImplementedError("utts[%d]: m_mag_mel_log (mag_dim) has %d columns: the backward pass takes at "
+                                          "most 64" % (i, int(np.shape(u[0])[1])))
+    utts, _on_dev = _tensor_inputs(utts, _MAG_NAMES, lf0_at=1)
+    engine = engine or get_engine()
+    plan = MagnitudeSynthesisPlan(engine, utts, fs, fft_len=fft_len, phase=phase, b_voi_ap_win=b_voi_ap_win,
+                                  b_const_rate=b_const_rate, noise=noise, post_filter=b_post_filter,
+                                  b_fbank_mel=b_fbank_mel, noise_mode=noise_mode, noise_seeds=noise_seeds)
+    cut = lambda x: [x[int(plan.out_off_host[u]):int(plan.out_off_host[u + 1])] for u in range(len(utts))]
+    if want_grad:   # the same launches inside a torch.autograd.Function (magphase_amd/autograd.py)
+        from .autograd import synthesize_from_mag
+
+        return cut(synthesize_from_mag(plan, b_out_hpf, utts))
+    pcm_dev = plan.run()
+    if b_out_hpf:
+        pcm_dev = engine.output_hpf(pcm_dev, plan.out_off_host, fs)
+    if return_device:
+        if pcm16_norm is not False:
+            pcm_dev = engine.output_pcm16(pcm_dev, plan.out_off_host, norm=pcm16_norm, return_device=True)
+        return cut(pcm_dev)
+    if pcm16_norm is not False:
+        pcm = engine.output_pcm16(pcm_dev, plan.out_off_host, norm=pcm16_norm)
+    elif b_out_hpf:
+        pcm = pcm_dev.cpu().numpy()
+    else:
+        pcm = engine.to_host_f64(pcm_dev)
+    return cut(pcm)
+
+
+def synthesis_from_mag(m_mag_mel_log, v_lf0, fs, fft_len=None, phase='min_phase', b_voi_ap_win=True, b_fbank_mel=False,
+                       b_const_rate=False, b_out_hpf=True):
+    """synthesis_from_compressed without transmitted phase: one utterance of synthesis_from_mag_batch."""
+    return synthesis_from_mag_batch([(m_mag_mel_log, v_lf0)], fs, fft_len=fft_len, phase=phase,
+                                    b_voi_ap_win=b_voi_ap_win, b_const_rate=b_const_rate, b_out_hpf=b_out_hpf,
+                                    b_fbank_mel=b_fbank_mel)[0]
 
 
 def synthesis_from_acoustic_modelling(in_feats_dir, filename_token, out_syn_dir, mag_dim, phase_dim, fs,

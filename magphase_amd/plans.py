@@ -1487,6 +1487,108 @@ class Type2SynthesisPlan(CompressedSynthesisPlan):
         return None
 
 
+class MagnitudeSynthesisPlan(CompressedSynthesisPlan):
+    """
+    Synthesis from the mel-log magnitudes and lf0 alone (magphase.py:922-938: per_phase_type 'min_phase' / 'linear'), with
+    a backward pass.  utts: list of (m_mag_mel_log [F x mag_dim], v_lf0 [F]); phase: 'min_phase'
+    (the complex-cepstrum minimum phase of the unwarped magnitude, k_min_phase) or 'zero' (the reference's 'linear').
+    The caller supplies no phase matrices: the plan feeds the unwarp one zero column per stream (its phase outputs are
+    overwritten before anything reads them).  run() is CompressedSynthesisPlan.run() with that per_phase_type -- the same
+    launches, the same samples.  run_backward(grad_pcm) -> float32 [n_rows x mag_dim]:
+      k_synth_comp_bwd against the rows the pair kernel read (g_m, and for 'min_phase' g_a / g_b),
+      k_min_phase_bwd ('min_phase': g_m += T^t g_phi / m, in place),
+      at the constant rate k_rows_lerp_adjoint at width H and the forward's unwarp again at the rows' rate (E),
+      k_mel_unwarp_bwd with the magnitude job only.
+    """
+    _PHASES = {"min_phase": "min_phase", "zero": "linear"}
+
+    def __init__(self, engine, utts, fs, fft_len=None, phase="min_phase", b_voi_ap_win=True, b_const_rate=False,
+                 noise=None, frames_per_run=None, post_filter=False, b_fbank_mel=False, noise_mode="reference",
+                 noise_seeds=None, defer_rng=False):
+        if phase not in self._PHASES:
+            raise ValueError("phase must be 'min_phase' or 'zero', not %r" % (phase,))
+        self.phase = phase
+        full = []
+        for ui, u in enumerate(utts):
+            if len(u) != 2:
+                raise ValueError("utterance %d: expected (m_mag_mel_log, v_lf0)" % ui)
+            mml, lf0 = u
+            if not _is_tensor(mml):
+                mml = np.asarray(mml)
+            if mml.ndim != 2:
+                raise ValueError("utterance %d: m_mag_mel_log must be 2-D" % ui)
+            if _is_tensor(mml):
+                z = _torch().zeros((int(mml.shape[0]), 1), dtype=_torch().float32, device=mml.device)
+            else:
+                z = np.zeros((int(mml.shape[0]), 1), dtype=np.float32)
+            full.append((mml, z, z, lf0))
+        super().__init__(engine, full, fs, fft_len=fft_len, b_voi_ap_win=b_voi_ap_win, b_const_rate=b_const_rate,
+                         noise=noise, frames_per_run=frames_per_run, per_phase_type=self._PHASES[phase],
+                         post_filter=post_filter, b_fbank_mel=b_fbank_mel, noise_mode=noise_mode, noise_seeds=noise_seeds,
+                         defer_rng=defer_rng)
+
+    def check_differentiable(self):
+        """What run_backward cannot take, said before any launch.  (CompressedSynthesisPlan._check_differentiable and its
+        refusal of these per_phase_types stand: this plan has a backward pass of its own.)"""
+        if self.apply_post_filter:
+            raise NotImplementedError("b_post_filter has no backward pass")
+        if int(self.mag_dim) > 64:
+            raise NotImplementedError("m_mag_mel_log (mag_dim) has %d columns: the backward pass takes at most 64"
+                                      % int(self.mag_dim))
+
+    def run_backward(self, grad_pcm, mark=None):
+        """The gradient of run()'s waveform with respect to the magnitude rows a_mag, float32 [n_rows x mag_dim], given
+        grad_pcm = dL/d(run()'s result): contiguous float32 [total_out].  After run(): the rows the pair kernel read and
+        the noise gains are taken from the plan's work buffers."""
+        self.check_differentiable()
+        torch = _torch()
+        e, N = self.engine, self.fft_len
+        H = N // 2 + 1
+        F, R = self.total_frames, self.n_rows
+        mark = mark or (lambda name: None)
+        if (grad_pcm.dtype != torch.float32 or int(grad_pcm.numel()) != self.total_out or not grad_pcm.is_contiguous()):
+            raise ValueError("run_backward: grad_pcm must be a contiguous float32 [%d]" % self.total_out)
+        if F == 0 or R == 0:
+            return torch.zeros((R, self.mag_dim), dtype=torch.float32, device=e.device)
+        buf = getattr(self, "_buf", None)
+        if buf is None:
+            raise RuntimeError("run_backward: call run() first (the backward pass reads the forward's unwarped rows)")
+        t = self.backward_tables()
+        ld = buf["ld"]
+        min_phase = self.phase == "min_phase"
+        # the rows k_synth_comp_pair read: k_min_phase's outputs, or the unwarped magnitude beside the constant phasor 1 + 0j
+        mag, real, imag = buf["spec_v"] if min_phase else buf["spec"]
+        n_per = int(self.n_per)
+        n_ph = min((n_per + 63) // 64 * 64, H)
+        tab = e.tables(N)
+        mark("start")
+        g_m = e.empty((F, ld))[:, :H]
+        g_a, g_b = (e.empty((F, ld))[:, :H] for _ in range(2)) if min_phase else (None, None)
+        e.launch(self._bwd_entry, N, tab, grad_pcm, self.total_out, t["pos"], t["lo"], t["hi"],
+                 F, mag, real, imag, ld, self.noise, self.npos, self.nleft, self.nright, self.wtype, self.voiced,
+                 buf["inv_gain"], self.win_l, self.win_r, self.per_v, self.ap_v, self.ap_u, n_per, g_m, g_a, g_b, ld)
+        mark("k_synth_comp_bwd")
+        if min_phase:   # in place: element k of a row is read and written by one lane
+            e.launch("mpx_min_phase_backward", N, tab, mag, real, imag, ld, g_m, g_a, g_b, ld, n_ph, F, g_m, ld)
+            mark("k_min_phase_bwd")
+        e_mag, g_e, ld_g = buf["spec"][0], g_m, ld
+        if self.b_const_rate:
+            g_e = e.rows_lerp_adjoint((g_m, None, None), t["adj"], self.rowt, R)[0]
+            ld_g = int(g_e.stride(0))
+            mark("k_rows_lerp_adjoint")
+            # E = exp(U_mag^T a_mag) at the rows' rate: the forward's unwarp again (its phase outputs are scratch)
+            e_mag, s_r, s_i = (e.empty((R, ld)) for _ in range(3))
+            e.launch("mpx_mel_unwarp", R, H, self.a_mag, self.mag_dim, self.u_mag, e_mag, self.a_real, self.a_imag,
+                     self.phase_dim, self.u_phase, s_r, s_i, ld)
+            del s_r, s_i
+            mark("k_mel_unwarp_mfma")
+        o_m = e.empty((R, self.mag_dim))
+        e.launch("mpx_mel_unwarp_backward", H, e_mag, ld, g_e, ld_g, self.u_mag, self.mag_dim, R, o_m, None, None, ld, 0,
+                 None, self.phase_dim, 0, None, None)
+        mark("k_mel_unwarp_bwd")
+        return o_m
+
+
 # ======================================================================================================
 # compressed-feature analysis (magphase.py:2947-2988, 2490-2544)
 # ======================================================================================================
