@@ -886,6 +886,16 @@ int mpx_post_filter(void* stream, const float* mag_mel_log, int64_t n_frames, in
                     int32_t nx_first, int32_t nx_last, const float* tilt, float* out);
 
 /*
+ * Backward of mpx_post_filter (k_post_filter_bwd).  The forward is linear per frame, y = x M^T; grad_in = grad_out M, as a
+ * gather: per input bin i the cover_cnt[i] output bins cover_idx[t * dim + i] whose window holds bin i (its own among them)
+ * and their weights cover_w[t * dim + i] = M[idx][i], t < fan -- hostmath.post_filter_backward_tables, built from the
+ * forward's half_len / tilt tables.  grad_out, grad_in: float32 [n_frames x dim] (3 <= dim <= 256, 1 <= fan <= dim).
+ * Deterministic (no atomics, every element written once); table entries outside the row are clamped into it.
+ */
+int mpx_post_filter_backward(void* stream, const float* grad_out, int64_t n_frames, int32_t dim, const int32_t* cover_cnt,
+                             const int32_t* cover_idx, const float* cover_w, int32_t fan, float* grad_in);
+
+/*
  * Output high-pass filter (magphase.py:981-995: scipy.signal.butter(4, 40 Hz) + lfilter) in float64 on the device,
  * as a cascade of the two second-order sections of the same Butterworth design (scipy output='sos'), each run as
  * a blocked scan: zero-state recurrence per block of mpx_hpf_block() samples, block end states chained per
@@ -964,6 +974,24 @@ int mpx_pcm16_to_f32(void* stream, const int16_t* pcm, int64_t n, float* out);
 int mpx_post_filter_merlin(void* stream, const float* mag_mel_log, int64_t n_frames, int32_t dim, const float* c1,
                            const float* lifter, const float* g, const float* wk, int32_t n_bins, double alpha,
                            const float* cf, double magic, float* mcep, float* mcep_w, float* r0, float* p_r0, float* out);
+
+/*
+ * Backward of mpx_post_filter_merlin: grad_in = the gradient with respect to mag_mel_log, given grad_out, the gradient
+ * with respect to the forward's output (the chain mc2b | b[0] += delta | b2mc taken as mcep_pf = mcep_w + delta e0, which
+ * it is in exact arithmetic):
+ *   mcep, mcep_w recomputed from mag_mel_log (k_rows_gemm);  grad_pf = grad_out . cf_t (k_rows_gemm);
+ *   grad_mcep = lifter * (grad_pf - g_d Q(mcep_w)) + g_d Q(mcep), g_d = grad_pf[0], Q(v) = S(v) / R(v),
+ *     R(v) = sum_k wk[k] exp(2 (v . g)[k]), S(v)[n] = sum_k wk[k] exp(2 (v . g)[k]) g[n][k]   (k_merlin_r0_bwd);
+ *   grad_in = grad_mcep . c1_t (k_rows_gemm).
+ * cf_t, c1_t: the forward's cf and c1 transposed, [dim x dim]; the other tables as the forward's.  mcep, mcep_w, grad_pf,
+ * grad_mcep: scratch [n_frames x dim] -- nothing of n_frames x n_bins is stored.  A frame whose R is not a positive finite
+ * number for either coefficient set (the forward wrote magic, or an infinity, there) gets an all-zero grad_in row.
+ * Deterministic (no atomics).
+ */
+int mpx_post_filter_merlin_backward(void* stream, const float* mag_mel_log, const float* grad_out, int64_t n_frames,
+                                    int32_t dim, const float* c1, const float* lifter, const float* g, const float* wk,
+                                    int32_t n_bins, const float* cf_t, const float* c1_t, float* mcep, float* mcep_w,
+                                    float* grad_pf, float* grad_mcep, float* grad_in);
 
 /*
  * Memory-rate probe (csrc/magphase_probe.hip; measurement only, not on the MagPhase path): one streaming float4 kernel

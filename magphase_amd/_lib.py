@@ -123,6 +123,8 @@ PROTOTYPES = {
     "mpx_bw_probe_shapes": (i32, []),
     "mpx_rows_pack": (i32, [vp, vp, vp, i32, i32] + [vp, i32, i64, i64] * 3),
     "mpx_post_filter_merlin": (i32, [vp, vp, i64, i32] + [vp] * 4 + [i32, f64, vp, f64] + [vp] * 5),
+    "mpx_post_filter_backward": (i32, [vp, vp, i64, i32, vp, vp, vp, i32, vp]),
+    "mpx_post_filter_merlin_backward": (i32, [vp, vp, vp, i64, i32] + [vp] * 4 + [i32] + [vp] * 7),
     "mpx_mlpg_work_doubles": (i64, [i64, i32]),
     "mpx_mlpg_solve": (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, i64, i32, i32, vp, i32, vp, i64, vp]),
     "mpx_mlpg_apply": (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i64]),

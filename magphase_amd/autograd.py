@@ -69,6 +69,14 @@ Function around la.build_min_phase_from_mag_spec_batch's one mpx_min_phase launc
 with mpx_min_phase_backward as its backward.  Where m <= 0 the phase gets no gradient (the protected logarithm is a
 constant there).  Not differentiable: v_lf0, fs, the noise and its gains.
 
+Post-filters (section 3.3p): a Function around the unchanged forward launches of Engine.post_filter (k_post_filter) and
+Engine.post_filter_merlin (mpx_post_filter_merlin's four launches) on the packed float32 rows of mp.post_filter_batch, with
+the gradient with respect to the log-mel magnitudes computed by k_post_filter_bwd (the MagPhase filter is linear per frame:
+g_x = g_y M as a gather over the inverse of the forward's own tables; nothing is kept) and by mpx_post_filter_merlin_backward (k_rows_gemm
+and k_merlin_r0_bwd: the cepstra and both frame energies are recomputed from the packed input rows, the only thing kept).
+A Merlin row for which the forward wrote la.MAGIC gets a zero gradient.  Not differentiable: fs, pf_coef and the four
+av_* / boost_* options.  The stage composes in front of the syntheses with b_post_filter=False.
+
 No double backward.  synthesis_from_compressed_batch with per_phase_type 'min_phase' / 'linear' (synthesis_from_mag_batch
 is the differentiable form), any synthesis with a post-filter, with pcm16_norm or with prepared=, and the constant-rate
 lossless analysis, have no backward pass.
@@ -533,3 +541,52 @@ def min_phase(engine, mats):
     """Engine.min_phase_rows on mats, differentiable with respect to the matrices that are tensors requiring grad.
     Returns the float32 (cos phi, sin phi) row matrices of the whole batch (with grad_fn)."""
     return _MinPhase.apply(engine, *mats)
+
+
+class _PostFilter(torch.autograd.Function):
+    """forward(engine, pf_type, fs, opts, *mats): mats = the [F_i x D] log-mel magnitude matrices of mp.post_filter_batch
+    (tensors or host arrays), opts = the filter's options as sorted (name, value) pairs; Engine.post_filter_pack (ONE
+    mpx_rows_pack launch) and Engine.post_filter / Engine.post_filter_merlin are the forward, Engine.post_filter_backward /
+    Engine.post_filter_merlin_backward the backward.  Output: the ONE float32 [sum F_i x D] buffer of filtered rows (the
+    per-utterance results are row views of it).  Kept for the backward pass: the packed input rows ('merlin' only)."""
+
+    @staticmethod
+    def forward(ctx, engine, pf_type, fs, opts, *mats):
+        x, offs = engine.post_filter_pack(list(mats))
+        kw = dict(opts)
+        out = engine.post_filter_merlin(x, fs, **kw) if pf_type == "merlin" else engine.post_filter(x, fs, **kw)
+        ctx.engine, ctx.pf_type, ctx.fs, ctx.kw = engine, pf_type, fs, kw
+        ctx.offs = [int(o) for o in offs]
+        ctx.like = [(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else None for m in mats]
+        if pf_type == "merlin":
+            ctx.save_for_backward(x)
+        else:
+            ctx.save_for_backward()
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        n_head = 4   # engine, pf_type, fs, opts
+        need_in = ctx.needs_input_grad[n_head:]
+        with torch.cuda.device(grad_out.device):
+            if ctx.pf_type == "merlin":
+                (x,) = ctx.saved_tensors
+                g = ctx.engine.post_filter_merlin_backward(x, grad_out, ctx.fs, **ctx.kw)
+            else:
+                ctx.saved_tensors   # (none kept; raises as torch does when the graph was freed)
+                g = ctx.engine.post_filter_backward(grad_out, ctx.fs, **ctx.kw)
+        out = []
+        for like, need, a, b in zip(ctx.like, need_in, ctx.offs[:-1], ctx.offs[1:]):
+            out.append(g[a:b].to(like[0]).reshape(like[1]) if like is not None and need else None)
+        return (None,) * n_head + tuple(out)
+
+
+def post_filter(engine, mats, pf_type, fs, opts):
+    """Engine.post_filter / Engine.post_filter_merlin on the packed rows of mats, differentiable with respect to the matrices
+    that are tensors requiring grad.  Returns (the float32 [sum F_i x D] buffer with grad_fn, the row offsets)."""
+    import numpy as np
+
+    out = _PostFilter.apply(engine, pf_type, fs, tuple(sorted(opts.items())), *mats)
+    offs = np.concatenate(([0], np.cumsum([int(m.shape[0]) for m in mats]))).astype(np.int64)
+    return out, offs

@@ -36,6 +36,33 @@ __global__ __launch_bounds__(256) void k_post_filter(const float* __restrict__ x
 }
 
 // ---------------------------------------------------------------------------------------------
+// Backward of k_post_filter.  The forward is linear per frame, y = x M^T with
+// M = diag(tilt) (I - A) + A, A the clamped moving average and the two end rows of M identity rows; the backward is
+// g_x = g_y M as a GATHER over column i of M: one thread per (frame, input bin i) sums w[t][i] * g_y[idx[t][i]] over the
+// cnt[i] output bins whose window covers bin i (the diagonal among them), in the table's order.  idx / w / cnt are
+// hostmath.post_filter_backward_tables' inverse of the forward's half_len / tilt tables, [fan x D] with the entry t of
+// bin i at t * D + i.  No atomics, every output written once.  Table entries are clamped into the row: a wrong table
+// gives wrong numbers, never a read outside the frame.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_post_filter_bwd(const float* __restrict__ gy, long long F, int D,
+                                                         const int* __restrict__ cnt, const int* __restrict__ idx,
+                                                         const float* __restrict__ w, int fan, float* __restrict__ gx) {
+    extern __shared__ float row[];   // rows_per_block x D
+    const int rows_per_block = blockDim.x / D;
+    const int rl = threadIdx.x / D, i = threadIdx.x - rl * D;
+    const long long f = (long long)blockIdx.x * rows_per_block + rl;
+    const bool live = (rl < rows_per_block) && (f < F);
+    if (live) row[rl * D + i] = gy[f * D + i];
+    __syncthreads();
+    if (!live) return;
+    const float* r = row + rl * D;
+    const int n = min(max(cnt[i], 0), fan);
+    float acc = 0.0f;
+    for (int t = 0; t < n; ++t) acc = fmaf(w[t * D + i], r[min(max(idx[t * D + i], 0), D - 1)], acc);
+    gx[f * D + i] = acc;
+}
+
+// ---------------------------------------------------------------------------------------------
 // output high-pass (magphase.py:981-995: butter(4, 40 Hz) + lfilter), float64, blocked scan over a CASCADE of two
 // second-order sections.  Each section's direct-form-II-transposed recurrence
 //   y = b0 x + z0 ; z0 = b1 x + z1 - a1 y ; z1 = b2 x - a2 y
@@ -288,6 +315,21 @@ int mpx_post_filter(void* stream, const float* mag_mel_log, int64_t n_frames, in
     const dim3 grid((unsigned)((n_frames + rows - 1) / rows)), block(256);
     hipLaunchKernelGGL(k_post_filter, grid, block, sizeof(float) * (size_t)rows * dim, (hipStream_t)stream,
                        mag_mel_log, (long long)n_frames, (int)dim, half_len, (int)nx_first, (int)nx_last, tilt, out);
+    MPX_HIP_CHECK(hipGetLastError());
+    return MPX_OK;
+}
+
+int mpx_post_filter_backward(void* stream, const float* grad_out, int64_t n_frames, int32_t dim, const int32_t* cover_cnt,
+                             const int32_t* cover_idx, const float* cover_w, int32_t fan, float* grad_in) {
+    if (n_frames < 0 || dim < 3 || dim > 256) return fail(MPX_ERR_ARG, "mpx_post_filter_backward: dim must be in 3..256%s");
+    if (fan < 1 || fan > dim) return fail(MPX_ERR_ARG, "mpx_post_filter_backward: fan must be in 1..dim%s");
+    if (n_frames == 0) return MPX_OK;
+    if (!grad_out || !cover_cnt || !cover_idx || !cover_w || !grad_in)
+        return fail(MPX_ERR_ARG, "mpx_post_filter_backward: null pointer%s");
+    const int rows = 256 / dim;
+    const dim3 grid((unsigned)((n_frames + rows - 1) / rows)), block(256);
+    hipLaunchKernelGGL(k_post_filter_bwd, grid, block, sizeof(float) * (size_t)rows * dim, (hipStream_t)stream, grad_out,
+                       (long long)n_frames, (int)dim, cover_cnt, cover_idx, cover_w, (int)fan, grad_in);
     MPX_HIP_CHECK(hipGetLastError());
     return MPX_OK;
 }

@@ -1249,6 +1249,65 @@ class Engine:
                     mcep_w, r0, p_r0, out)
         return out[:F]
 
+    def post_filter_pack(self, mats):
+        """The [F_i x D] matrices of mp.post_filter_batch (host arrays or tensors on this device, any of pack_rows' dtypes
+        and row strides) as ONE dense float32 device matrix [sum F_i x D] (one mpx_rows_pack launch) and the row offsets."""
+        D = int(mats[0].shape[1])
+        offs = np.concatenate(([0], np.cumsum([int(m.shape[0]) for m in mats]))).astype(np.int64)
+        x = self.empty((int(offs[-1]), D))
+        self.pack_rows([list(mats)], [x])
+        return x, offs
+
+    @staticmethod
+    def _grad_rows(grad_out, what):
+        """grad_out as the dense float32 [F x D] matrix the backward entries read."""
+        torch = _torch()
+        if grad_out.dim() != 2:
+            raise ValueError("%s: grad_out must be [frames x dim]" % what)
+        return grad_out.to(torch.float32).contiguous()
+
+    def post_filter_backward(self, grad_out, fs, **kw):
+        """mpx_post_filter_backward (k_post_filter_bwd): grad_out = the gradient with respect to Engine.post_filter's output,
+        [F x D] -> the gradient with respect to its input, float32 [F x D].  fs / kw as Engine.post_filter; the gather
+        tables (hostmath.post_filter_backward_tables of the forward's own tables) are resident per configuration."""
+        g = self._grad_rows(grad_out, "post_filter_backward")
+        F, D = int(g.shape[0]), int(g.shape[1])
+        key = ("post_filter_bwd", D, int(fs)) + tuple(sorted(kw.items()))
+        if key not in self._tables:
+            import warnings
+
+            with warnings.catch_warnings():   # (the forward gave the tables' warnings)
+                warnings.simplefilter("ignore")
+                fwd = hm.post_filter_tables(D, fs, **kw)
+            cnt, idx, w, fan = hm.post_filter_backward_tables(D, *fwd)
+            self._tables[key] = (fan, self.to_device(cnt, np.int32), self.to_device(idx, np.int32),
+                                 self.to_device(w, np.float32))
+        fan, d_cnt, d_idx, d_w = self._tables[key]
+        out = self.empty((F, D))
+        self.launch("mpx_post_filter_backward", g, F, D, d_cnt, d_idx, d_w, fan, out)
+        return out
+
+    def post_filter_merlin_backward(self, mag_mel_log, grad_out, fs, pf_coef=1.4):
+        """mpx_post_filter_merlin_backward (k_rows_gemm, k_merlin_r0_bwd): mag_mel_log = the float32 [F x D] rows
+        Engine.post_filter_merlin was given, grad_out = the gradient with respect to its output -> the gradient with respect
+        to mag_mel_log, float32 [F x D].  A row for which the forward wrote la.MAGIC (or an infinity) gets zeros.  Workspace:
+        four [F x D] matrices."""
+        g = self._grad_rows(grad_out, "post_filter_merlin_backward")
+        F, D = int(mag_mel_log.shape[0]), int(mag_mel_log.shape[1])
+        if tuple(g.shape) != (F, D):
+            raise ValueError("post_filter_merlin_backward: grad_out is %s, the input [%d x %d]" % (tuple(g.shape), F, D))
+        key = ("merlin_bwd", D, int(fs), float("%1.2f" % pf_coef))
+        if key not in self._tables:
+            t = hm.merlin_tables(D, fs, pf_coef)
+            self._tables[key] = (int(t["g"].shape[1]),) + tuple(self.to_device(a, np.float32) for a in (
+                t["c1"], t["lifter"], t["g"], t["wk"], np.ascontiguousarray(t["cf"].T), np.ascontiguousarray(t["c1"].T)))
+        nb, c1, lifter, gmat, wk, cf_t, c1_t = self._tables[key]
+        mcep, mcep_w, g_pf, g_c, out = (self.empty((max(F, 1), D)) for _ in range(5))
+        x = mag_mel_log.to(_torch().float32).contiguous()
+        self.launch("mpx_post_filter_merlin_backward", x, g, F, D, c1, lifter, gmat, wk, nb, cf_t, c1_t, mcep, mcep_w,
+                    g_pf, g_c, out)
+        return out[:F]
+
     def output_hpf(self, pcm, out_off_host, fs, design="butter40"):
         """
         magphase.py:981-995 on the device: float32 pcm [total] (utterances concatenated at out_off_host) ->

@@ -1081,6 +1081,52 @@ def post_filter_tables(mag_dim, fs, av_len_at_zero=None, av_len_at_nyq=None, boo
     return int(v_nx[0]), int(v_nx[-1]), (v_lens // 2).astype(np.int64), np.linspace(b0, bn, mag_dim)
 
 
+def post_filter_matrix(mag_dim, nx_first, nx_last, half_len, tilt):
+    """
+    The MagPhase post-filter as the [mag_dim x mag_dim] float64 matrix M it is per frame (y = x M^T), from
+    post_filter_tables' output: M = diag(tilt) (I - A) + A with A the moving average of half length
+    half_len[clamp(b, nx_first, nx_last) - nx_first] around the clamped bin, and the two end rows identity rows.
+    """
+    mag_dim, nx_first, nx_last = int(mag_dim), int(nx_first), int(nx_last)
+    half_len = np.asarray(half_len, dtype=np.int64)
+    tilt = np.asarray(tilt, dtype=np.float64)
+    if not (0 <= nx_first <= nx_last < mag_dim) or half_len.size != nx_last - nx_first + 1 or tilt.size != mag_dim:
+        raise ValueError("post_filter_matrix: tables do not fit mag_dim = %d" % mag_dim)
+    centre = np.clip(np.arange(mag_dim), nx_first, nx_last)
+    half = half_len[centre - nx_first]
+    if np.any(half < 0) or np.any(centre - half < 0) or np.any(centre + half >= mag_dim):
+        raise ValueError("post_filter_matrix: an averaging window leaves the row (half lengths %d .. %d)"
+                         % (half.min(), half.max()))
+    m_ave = np.zeros((mag_dim, mag_dim))
+    for b in range(mag_dim):
+        m_ave[b, centre[b] - half[b]:centre[b] + half[b] + 1] = 1.0 / (2 * half[b] + 1)
+    m = tilt[:, None] * (np.eye(mag_dim) - m_ave) + m_ave
+    m[0] = 0.0
+    m[0, 0] = 1.0
+    m[-1] = 0.0
+    m[-1, -1] = 1.0
+    return m
+
+
+def post_filter_backward_tables(mag_dim, nx_first, nx_last, half_len, tilt):
+    """
+    Inverse tables of the MagPhase post-filter for mpx_post_filter_backward's gather (g_x = g_y M, column by column): per
+    input bin i the output bins j with M[j][i] != 0 in ascending order and their weights M[j][i].
+    Returns (cnt int32 [mag_dim], idx int32 [fan x mag_dim], w float64 [fan x mag_dim], fan); entry t of bin i is at
+    [t][i], unused entries are (idx i, w 0).
+    """
+    m = post_filter_matrix(mag_dim, nx_first, nx_last, half_len, tilt)
+    cover = [np.flatnonzero(m[:, i]) for i in range(int(mag_dim))]
+    cnt = np.array([c.size for c in cover], dtype=np.int32)
+    fan = max(1, int(cnt.max()))
+    idx = np.tile(np.arange(int(mag_dim), dtype=np.int32), (fan, 1))
+    w = np.zeros((fan, int(mag_dim)))
+    for i, c in enumerate(cover):
+        idx[:c.size, i] = c
+        w[:c.size, i] = m[c, i]
+    return cnt, idx, w, fan
+
+
 HPF_DESIGNS = ("butter40", "ellip60")
 
 

@@ -768,6 +768,88 @@ def post_filter_merlin_device(m_mag_mel_log, fs, pf_coef=1.4, engine=None):
     return engine.to_host_f64(engine.post_filter_merlin(x, fs, pf_coef=pf_coef))
 
 
+def post_filter_batch(mats, fs, pf_type='magphase', pf_coef=1.4, av_len_at_zero=None, av_len_at_nyq=None,
+                      boost_at_zero=None, boost_at_nyq=None, engine=None, return_device=False):
+    """
+    The post-filter as a stage of its own on the device, for a whole batch: pf_type 'magphase' = post_filter
+    (k_post_filter), 'merlin' = post_filter_merlin (mpx_post_filter_merlin), one forward launch sequence over all frames.
+    mats: list of [F_i x D] log-mel magnitude matrices, each a host array or a tensor on the engine's device (float16 /
+    bfloat16 / float32 / float64, any row stride -- column slices of a wider tensor are read where they lie: one
+    mpx_rows_pack launch gathers them into float32 rows).  F_i = 0 and an empty list are legal.
+    Returns a list of [F_i x D] float64 arrays (return_device: float32 device tensors, row views of one buffer); the
+    values are Engine.post_filter's / Engine.post_filter_merlin's on the packed float32 rows, bit for bit -- what
+    synthesis_from_compressed_batch(b_post_filter=True / 'merlin') filters its magnitudes with.
+    ValueError: a pf_type other than 'magphase' / 'merlin'; av_len_at_zero / av_len_at_nyq / boost_at_zero / boost_at_nyq
+    given with 'merlin' or a pf_coef other than 1.4 with 'magphase' (each option belongs to one filter); D outside 3..64
+    ('merlin') or 3..256 ('magphase'); matrices that are not 2-D or differ in D -- all before any launch.  The sample-rate
+    defaults, the warnings and the ValueError of 'magphase' are hostmath.post_filter_tables'.
+    Autograd: with return_device, grad mode on and a device matrix that requires grad, the results carry a grad_fn
+    (autograd._PostFilter) and backward() gives each matrix a gradient in its own dtype and shape, computed by
+    k_post_filter_bwd / mpx_post_filter_merlin_backward; the forward values are the same bits
+    either way.  A 'merlin' row whose output is la.MAGIC gets a zero gradient.  Not differentiable: fs, pf_coef and the
+    four av_* / boost_* options; no double backward.  Under grad the 'magphase' tables must hold no negative half length
+    (D = 3 with the 48 kHz defaults does: ValueError).
+    Composition: mlpg_streams_batch -> post_filter_batch -> synthesis_from_compressed_batch / synthesis_from_mag_batch with
+    b_post_filter=False carries a waveform loss through the filter to the acoustic model's means.
+    """
+    if pf_type not in ('magphase', 'merlin'):
+        raise ValueError("post_filter_batch: pf_type must be 'magphase' or 'merlin', not %r" % (pf_type,))
+    if isinstance(mats, np.ndarray) or not isinstance(mats, (list, tuple)):
+        raise ValueError("post_filter_batch: mats must be a list of [frames x D] matrices")
+    opts = dict(av_len_at_zero=av_len_at_zero, av_len_at_nyq=av_len_at_nyq, boost_at_zero=boost_at_zero,
+                boost_at_nyq=boost_at_nyq)
+    opts = {k: v for k, v in opts.items() if v is not None}
+    if pf_type == 'merlin':
+        if opts:
+            raise ValueError("post_filter_batch: %s belong to pf_type='magphase'" % ", ".join(sorted(opts)))
+        opts = dict(pf_coef=float(pf_coef))
+    elif float(pf_coef) != 1.4:
+        raise ValueError("post_filter_batch: pf_coef belongs to pf_type='merlin'")
+    mats = list(mats)
+    if not mats:
+        return []
+    for i, m in enumerate(mats):
+        if not hasattr(m, "shape"):
+            mats[i] = m = np.asarray(m)
+        if len(m.shape) != 2:
+            raise ValueError("post_filter_batch: mats[%d] must be a 2-D [frames x D] matrix" % i)
+    D = int(mats[0].shape[1])
+    if any(int(m.shape[1]) != D for m in mats):
+        raise ValueError("post_filter_batch: every matrix must have the same number of columns")
+    d_max = 64 if pf_type == 'merlin' else 256
+    if not 3 <= D <= d_max:
+        raise ValueError("post_filter_batch: pf_type=%r needs 3 <= D <= %d, not %d" % (pf_type, d_max, D))
+    if pf_type == 'magphase':
+        hm.post_filter_tables(D, fs, **opts)   # the reference's warnings and its ValueError, before any launch
+    engine = engine or get_engine()
+    import torch
+
+    wants_grad = bool(return_device and torch.is_grad_enabled()
+                      and any(_is_device_tensor(m) and m.requires_grad for m in mats))
+    total = int(sum(int(m.shape[0]) for m in mats))
+    if total == 0:
+        out = torch.zeros((0, D), dtype=torch.float32, device=engine.device)
+        offs = np.zeros(len(mats) + 1, dtype=np.int64)
+    else:
+        with warnings.catch_warnings():   # (the tables' warnings were given above)
+            warnings.simplefilter("ignore")
+            if wants_grad:
+                from . import autograd
+
+                out, offs = autograd.post_filter(engine, mats, pf_type, fs, opts)
+            else:
+                x, offs = engine.post_filter_pack(mats)
+                out = engine.post_filter_merlin(x, fs, **opts) if pf_type == 'merlin' else engine.post_filter(x, fs, **opts)
+    if not return_device:
+        out = engine.to_host_f64(out) if total else np.zeros((0, D))
+    return [out[int(a):int(b)] for a, b in zip(offs[:-1], offs[1:])]
+
+
+def post_filter_device(m_mag_mel_log, fs, **kw):
+    """post_filter_batch for one matrix ([F x D] in, [F x D] out; kw as post_filter_batch's)."""
+    return post_filter_batch([m_mag_mel_log], fs, **kw)[0]
+
+
 def _output_hpf(v_syn_sig, fs):
     """magphase.py:981-995: 4th-order Butterworth high-pass at 40 Hz, float64 on the host (poles at |z|~0.997)."""
     from scipy import signal
