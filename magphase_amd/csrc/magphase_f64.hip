@@ -31,7 +31,8 @@ constexpr size_t lds_bytes_ana64() {
            sizeof(float) * (size_t)(kAna64Waves * P * kXStride + 4 + kAna64Waves * f64_win_floats<P>());   // + frame queue + window regions
 }
 
-// sin(x), |x| <= pi/2: Taylor polynomial to x^17 (remainder (pi/2)^19 / 19! = 4e-14)
+// sin(x) by its Taylor polynomial to x^17: the remainder x^19 / 19! is 4e-14 at |x| = pi/2, but 8e-20 -- far below 2^-53 of
+// sin(x) -- for |x| <= pi/4, the only range hann_half_f64 uses; near 0 the error is RELATIVE (the last step is x + x^3 p)
 __device__ __forceinline__ double sin_halfpi_range(double x) {
     const double x2 = x * x;
     double p = 1.0 / 355687428096000.0;
@@ -46,12 +47,20 @@ __device__ __forceinline__ double sin_halfpi_range(double x) {
 }
 
 // np.hanning(1 + 2L)[k] on the rising half (t = k/L; L == 0: weight 1) and np.hanning(1 + 2R) on the falling half
-// (t = (L + R - k)/R): 0.5 - 0.5 cos(pi t) = 0.5 + 0.5 sin(pi (t - 0.5))      (libaudio.py:70-84)
+// (t = (L + R - k)/R): 0.5 - 0.5 cos(pi t) = sin(pi t / 2)^2                   (libaudio.py:70-84)
+// One polynomial at one of two arguments, as the float32 sin2_halfpi (mpx_common.hpp):
+//   t <  0.5:  sin(pi t / 2)^2             a few 2^-53 of the WEIGHT however small it is, exactly 0 at t == 0
+//   t >= 0.5:  1 - sin(pi (1 - t) / 2)^2   a few 2^-53 absolute (1 - t is exact there), exactly 1 at t == 1
+// (0.5 + 0.5 sin(pi (t - 0.5)) at every t was good to the polynomial's remainder at pi/2, 2.2e-14 of FULL SCALE: the weight at
+// k == 1 of a half of 9600 samples, 2.7e-8, came out 8e-7 off -- more than a float32 rounding of the feature -- and the
+// weight at t == 0 was -2.2e-14, not 0: a sample there gave unit phasors where the reference's row is (0, 0, 0).)
 __device__ __forceinline__ double hann_half_f64(int k, int L, int LR, int kadd, double invL, double invR) {
     const bool rising = k <= L;
     const int num = rising ? k + kadd : LR - k;
     const double t = (double)num * (rising ? invL : invR);
-    return fma(0.5, sin_halfpi_range(3.14159265358979323846 * (t - 0.5)), 0.5);
+    const bool low = t < 0.5;
+    const double s = sin_halfpi_range(1.57079632679489661923 * (low ? t : 1.0 - t));
+    return low ? s * s : fma(-s, s, 1.0);
 }
 
 // 1/sqrt(s) from the fp32 hardware estimate (relative error e0 <= 1.2e-7) and ONE Newton step in double: the error
