@@ -1,90 +1,83 @@
 """
-Autograd for the lossless features, both directions, for the compressed features, both directions, for the type-2 features,
-both directions, and for the true envelope.  Imported lazily by
-magphase.py, and only when a device tensor that requires grad goes in with return_device=True and grad mode on.
+Autograd for the batch API: every path is a torch.autograd.Function around the UNCHANGED forward launches, with the
+backward pass in hand-written kernels.  Imported lazily by magphase.py and libaudio.py, and only under hostmath.wants_grad's
+rule (return_device, grad mode on, a device tensor that requires grad).  Every gradient comes back in its input's own dtype
+and shape; host arrays and inputs that need no gradient get None.
 
-Synthesis: a torch.autograd.Function around the unchanged forward launch of
-synthesis_from_lossless_batch / synthesis_from_lossless_const_rate_batch, with the gradients with respect to
-m_mag / m_real / m_imag computed by k_synth_lossless_bwd (and k_rows_lerp_adjoint for constant-rate rows).
-Not differentiable: v_f0 (the pitch marks are integers) and fs.
-
-Analysis (section 3.3i): a second Function around the unchanged forward launch of analysis_lossless_batch, with the
-gradient with respect to the samples v_sig computed by k_analysis_lossless_bwd and k_analysis_bwd_gather from the
-forward's own output rows (X = mag (real + j imag): nothing else is kept).  Not differentiable: v_pm_sec, v_voi and fs
-(the epochs are rounded to samples); v_f0 and v_shift come from the host and carry no grad_fn.  Where mag^2 < 1e-37 --
-the clamp region of the forward's 1 / |X|, which holds X == 0 -- the gradient with respect to X is defined as zero: a
-silent frame gives zeros, never Inf or NaN.
-
-Compressed analysis (section 3.3j): a third Function around the unchanged forward launch of analysis_compressed_batch
-(CompressedAnalysisPlan.run(), whichever of its paths it takes), at the variable and the constant rate, with the gradient
-with respect to the samples v_sig computed by CompressedAnalysisPlan.run_backward: the lossless rows are recomputed (only
-the three small output matrices are kept), k_phase_grad_mask and k_mel_warp_bwd take the gradients back through the two
-mel warps -- the phase streams' voicing mask and clip are read from the forward's own outputs, and the gradient at a
-clipped element (exactly +-1.0f) is defined as zero --, k_rows_lerp_adjoint through the constant-rate interpolation, and
-the lossless analysis' backward kernels do the rest.  Not differentiable: v_pm_sec, v_voi and fs; v_lf0_smth and v_shift
-come from the host and carry no grad_fn.
-
-Compressed synthesis (section 3.3k): a fourth Function around the unchanged forward of synthesis_from_compressed_batch
-(the plan's packing of the coefficient rows, CompressedSynthesisPlan.run() and the output high-pass), type 1 with
-per_phase_type='magphase' and no post-filter, at the variable and the constant rate, with the gradients with respect to
-m_mag_mel_log / m_real_mel / m_imag_mel computed by CompressedSynthesisPlan.run_backward: the high-pass' adjoint (the same
-filter run backwards in time, per utterance), k_synth_comp_bwd (per frame: the noise spectrum recomputed, the gradient
-window through the anti-ringing window and one FFT, the epilogue against the forward's own unwarped rows),
-k_rows_lerp_adjoint through the constant-rate interpolation and k_mel_unwarp_bwd through the two mel unwarps.  Not
-differentiable: v_lf0 (it only produces integer pitch marks and the voicing flag), fs, and the noise with its two gains
-(they do not depend on the features).  Bins 0 and N/2 keep |S|: where S == 0 there the gradient is defined as zero; where
-a phase bin is a == b == 0 its gradient is m P gS (k_synth_lossless_bwd's convention).  A plan that stores its noise
-spectra (MAGPHASE_NOISE_SPECTRA=store) is differentiated the same way: the backward pass recomputes them.
-
-Type-2 synthesis (section 3.3l): a fifth Function around the unchanged forward of synthesis_from_compressed_type2_batch
-(Type2SynthesisPlan.run() and the elliptic output high-pass), at the variable rate and at any const_rate_ms, with the
-gradients computed by the same run_backward: the elliptic filter run backwards in time, k_synth_comp_bwd's type-2 arm
-(bins 0 and N/2 keep Re S, a linear map: the real end-bin gradient passes straight through), the type-2 phase unwarp
-matrix and curves as the plan holds them.  The one noise gain per utterance does not depend on the features: it is held
-constant and the backward pass is exact.  Not differentiable: v_lf0, fs, hf_slope_coeff, the noise and its gain.
-
-True envelope (section 3.3m): a sixth Function around the unchanged launch of la.true_envelope_batch(return_device=True)
-(Engine.true_envelope), for the three in_types and any ncoeffs, with the gradient with respect to the input matrices
-computed by k_true_envelope_bwd (Engine.true_envelope_backward): the exact adjoint of the passes as the device ran them --
-the forward's pass counts and its packed input rows are kept, the decisions of the max updates are recomputed on chip.  The
-stop test is not differentiated (the pass count is a constant of the backward pass), so the gradient is that of the
-envelope with K passes; it jumps where a decision or the pass count flips.  A row with a non-finite dB value (all NaN
-in the forward) gets a zero gradient.  Not differentiable: thres_db.
-
-Type-2 analysis (section 3.3m): a seventh and an eighth Function around the unchanged forward launches of
-analysis_lossless_type2_batch (Type2AnalysisPlan.run) and analysis_compressed_type2_batch
-(Type2CompressedAnalysisPlan.run), with the gradient with respect to the samples v_sig computed by the plans' run_backward:
-both sets of rows are recomputed (only the envelope's pass counts and, for the compressed form, the three small matrices
-are kept), k_true_envelope_bwd takes the envelope's gradient to the two-period magnitudes, the lossless analysis' backward
-kernels run over the two-period and the one-period frame table and the two sample gradients are added; the compressed form
-first runs the tail of the type-1 compressed backward on the type-2 row tables.  Not differentiable: v_pm_sec, v_voi, fs,
-the per-frame gain.
-
-Magnitude-only synthesis (section 3.3o): a Function around the unchanged forward of synthesis_from_mag_batch
-(MagnitudeSynthesisPlan.run() -- the compressed plan with per_phase_type 'min_phase' / 'linear' -- and the output
-high-pass), with the gradient with respect to m_mag_mel_log computed by MagnitudeSynthesisPlan.run_backward:
-k_synth_comp_bwd against the rows the pair kernel read, k_min_phase_bwd (the adjoint of the minimum-phase stage, in
-place on the magnitude gradient rows; 'min_phase' only), k_rows_lerp_adjoint and k_mel_unwarp_bwd's magnitude job.  And a
-Function around la.build_min_phase_from_mag_spec_batch's one mpx_min_phase launch, magnitude rows -> unit phasor rows,
-with mpx_min_phase_backward as its backward.  Where m <= 0 the phase gets no gradient (the protected logarithm is a
-constant there).  Not differentiable: v_lf0, fs, the noise and its gains.
-
-Post-filters (section 3.3p): a Function around the unchanged forward launches of Engine.post_filter (k_post_filter) and
-Engine.post_filter_merlin (mpx_post_filter_merlin's four launches) on the packed float32 rows of mp.post_filter_batch, with
-the gradient with respect to the log-mel magnitudes computed by k_post_filter_bwd (the MagPhase filter is linear per frame:
-g_x = g_y M as a gather over the inverse of the forward's own tables; nothing is kept) and by mpx_post_filter_merlin_backward (k_rows_gemm
-and k_merlin_r0_bwd: the cepstra and both frame energies are recomputed from the packed input rows, the only thing kept).
-A Merlin row for which the forward wrote la.MAGIC gets a zero gradient.  Not differentiable: fs, pf_coef and the four
-av_* / boost_* options.  The stage composes in front of the syntheses with b_post_filter=False.
+entry function                forward -> backward                                 differentiable | not             DESIGN.md
+synthesize                    Lossless[ConstRate]SynthesisPlan.run                m_mag, m_real, m_imag            3.3h
+                                -> .run_backward                                    | v_f0, fs
+analyze                       LosslessAnalysisPlan.run -> .run_backward           v_sig | v_pm_sec, v_voi, fs      3.3i
+analyze_compressed            CompressedAnalysisPlan.run -> .run_backward         v_sig | v_pm_sec, v_voi, fs      3.3j
+synthesize_compressed         CompressedSynthesisPlan.run, Engine.output_hpf      m_mag_mel_log, m_real_mel,       3.3k
+                                -> .adjoint_hpf, .run_backward                      m_imag_mel | v_lf0, fs, noise
+synthesize_compressed_type2   Type2SynthesisPlan.run, output_hpf('ellip60')       the same three | v_lf0, fs,      3.3l
+                                -> .adjoint_hpf('ellip60'), .run_backward           hf_slope_coeff, noise, its gain
+true_envelope                 Engine.true_envelope                                the matrices | thres_db, the     3.3m
+                                -> Engine.true_envelope_backward                    stop test (pass counts held)
+analyze_type2                 Type2AnalysisPlan.run -> .run_backward              v_sig | v_pm_sec, v_voi, fs,     3.3m
+analyze_compressed_type2      Type2CompressedAnalysisPlan.run -> .run_backward      the per-frame gain             3.3m
+mlpg                          Engine.mlpg_streams -> .mlpg_streams_backward       the means | variances, windows   3.3n
+synthesize_from_mag           MagnitudeSynthesisPlan.run, Engine.output_hpf       m_mag_mel_log | v_lf0, fs,       3.3o
+                                -> .adjoint_hpf, .run_backward                      noise and its gains
+min_phase                     Engine.min_phase_rows -> .min_phase_backward        the magnitudes (not where m<=0)  3.3o
+post_filter                   Engine.post_filter[_merlin]                         the log-mel magnitudes | fs,     3.3p
+                                -> Engine.post_filter[_merlin]_backward             pf_coef, av_* / boost_*
 
 No double backward.  synthesis_from_compressed_batch with per_phase_type 'min_phase' / 'linear' (synthesis_from_mag_batch
 is the differentiable form), any synthesis with a post-filter, with pcm16_norm or with prepared=, and the constant-rate
 lossless analysis, have no backward pass.
 """
+from collections import namedtuple
+from itertools import accumulate
+
 import torch
 from torch.autograd.function import once_differentiable
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# the scaffold: what every Function below does with its inputs' descriptions and with the gradients (any device)
+# ------------------------------------------------------------------------------------------------------------------
+def _like(inputs):
+    """Per input what its gradient has to look like: (dtype, shape) of a tensor, None for a host array."""
+    return [(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else None for m in inputs]
+
+
+def _coerce(g, dtype=torch.float32, unit_cols=False):
+    """An incoming gradient as the kernels read it: of dtype and contiguous (unit_cols: a unit column stride is enough) --
+    the tensor itself where it already is, a converted contiguous copy otherwise.  None (nobody differentiated that
+    output) stays None."""
+    if g is None:
+        return None
+    ok = g.stride(1) == 1 if unit_cols else g.is_contiguous()
+    return g if g.dtype == dtype and ok else g.to(dtype).contiguous()
+
+
+def _offsets(rows):
+    """Row offsets [0, r0, r0 + r1, ...] of consecutive blocks of rows[i] rows."""
+    return [0] + list(accumulate(int(n) for n in rows))
+
+
+def _scatter(g, offs, like, need_in):
+    """A batch gradient cut back into per-input gradients.  g: ONE tensor whose rows offs[i]:offs[i + 1] belong to input i,
+    or a tuple of k stream tensors (None where no input of that stream needs one) for inputs that come utterance-major,
+    k per utterance (input i = stream i % k of utterance i // k, rows offs[i // k]:offs[i // k + 1]).  like: _like() of the
+    inputs; need_in: their needs_input_grad.  -> per input its rows in the input's dtype and shape, or None for a host
+    array and for an input that needs no gradient."""
+    streams = g if isinstance(g, (tuple, list)) else (g,)
+    k = len(streams)
+    out = []
+    for i, (lk, need) in enumerate(zip(like, need_in)):
+        if lk is None or not need:
+            out.append(None)
+        else:
+            out.append(streams[i % k][offs[i // k]:offs[i // k + 1]].to(lk[0]).reshape(lk[1]))
+    return tuple(out)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# lossless synthesis: packs its inputs itself and keeps them
+# ------------------------------------------------------------------------------------------------------------------
 class _LosslessSynthesis(torch.autograd.Function):
     """forward(plan, cat_fn, n_utts, *mats): mats = the batch's matrices, utterance-major (m_mag_0, m_real_0, m_imag_0,
     m_mag_1, ...: tensors or host arrays); cat_fn(feats) -> the three packed float32 device matrices (magphase.py's
@@ -97,8 +90,8 @@ class _LosslessSynthesis(torch.autograd.Function):
         cat = cat_fn(feats)
         pcm = plan.run(cat[0], cat[1], cat[2])
         ctx.plan = plan
-        ctx.rows = [int(f[0].shape[0]) for f in feats]
-        ctx.like = [(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else None for m in mats]
+        ctx.offs = _offsets(f[0].shape[0] for f in feats)
+        ctx.like = _like(mats)
         ctx.save_for_backward(*cat)
         return pcm
 
@@ -109,197 +102,175 @@ class _LosslessSynthesis(torch.autograd.Function):
         n_head = 3   # plan, cat_fn, n_utts
         need_in = ctx.needs_input_grad[n_head:]
         need = tuple(any(need_in[k::3]) for k in range(3))
-        if grad_out.dtype != torch.float32 or not grad_out.is_contiguous():
-            grad_out = grad_out.to(torch.float32).contiguous()
+        grad_out = _coerce(grad_out)
         with torch.cuda.device(grad_out.device):
             g = ctx.plan.run_backward(grad_out, mag, real, imag, need=need)
-        out, a = [], 0
-        for u, n in enumerate(ctx.rows):
-            for k in range(3):
-                like = ctx.like[3 * u + k]
-                if like is None or not need_in[3 * u + k]:
-                    out.append(None)
-                else:
-                    out.append(g[k][a:a + n].to(like[0]).reshape(like[1]))
-            a += n
-        return (None,) * n_head + tuple(out)
+        return (None,) * n_head + _scatter(g, ctx.offs, ctx.like, need_in)
 
 
 def synthesize(plan, cat_fn, feats):
     """plan.run on the packed matrices of feats = [(m_mag, m_real, m_imag, ...)], differentiable with respect to the
     matrices that are tensors requiring grad.  Returns the float32 [total_out] waveform buffer (with grad_fn)."""
+    plan.check_differentiable()
     mats = [x for f in feats for x in f[:3]]
     return _LosslessSynthesis.apply(plan, cat_fn, len(feats), *mats)
 
 
-class _LosslessAnalysis(torch.autograd.Function):
-    """forward(plan, *sigs): plan = a LosslessAnalysisPlan built from the utterances whose v_sig are sigs (tensors or
-    host arrays; the plan holds the samples as one float32 device buffer already); plan.run() is the forward launch,
-    plan.run_backward(...) the backward ones.  Outputs: the three float32 [total_frames x H] matrices of the batch; the
-    per-utterance results are row views of them."""
+# ------------------------------------------------------------------------------------------------------------------
+# signal -> rows: the four analyses
+# ------------------------------------------------------------------------------------------------------------------
+# What is particular to one analysis.  run(plan) -> its outputs as ONE flat tuple, the three differentiable float32
+# matrices first (anything after them is marked non-differentiable); keep: the indices of the outputs kept for the backward
+# pass; backward(plan, kept, grads) -> the float32 [total_smpls] sample gradient, grads = the three matrices' gradients
+# (contiguous float32, or None for an output nobody differentiated: not read by the kernels); n_smpls(plan): the utterances'
+# sample counts.
+_AnalysisPath = namedtuple("_AnalysisPath", "run keep backward n_smpls")
+
+
+def _run_type2_compressed(plan):
+    (mag, real, imag), gain, iters = plan.run(want_iters=True)
+    return mag, real, imag, gain, iters
+
+
+# the three [total_frames x H] matrices; all three are kept (X = mag (real + j imag): nothing else is)
+_LOSSLESS = _AnalysisPath(run=lambda p: p.run(), keep=(0, 1, 2),
+                          backward=lambda p, kept, grads: p.run_backward(kept[0], kept[1], kept[2], grads),
+                          n_smpls=lambda p: p.n_smpls)
+# [total_out_frames x mag_dim], [.. x phase_dim] twice: only these three small matrices are kept
+_COMPRESSED = _AnalysisPath(run=lambda p: p.run(), keep=(0, 1, 2),
+                            backward=lambda p, kept, grads: p.run_backward(kept, grads),
+                            n_smpls=lambda p: p.lossless.n_smpls)
+# (env, real, imag [total_frames x H]; the float64 per-frame gain, the int32 passes per envelope row): the pass counts only
+# are kept -- both sets of rows are recomputed
+_TYPE2 = _AnalysisPath(run=lambda p: p.run(want_iters=True), keep=(4,),
+                       backward=lambda p, kept, grads: p.run_backward(grads, kept[0]),
+                       n_smpls=lambda p: p.lossless.n_smpls)
+# (mag, real, imag as _COMPRESSED; gain, passes): the three small matrices and the pass counts are kept
+_TYPE2_COMPRESSED = _AnalysisPath(run=_run_type2_compressed, keep=(0, 1, 2, 4),
+                                  backward=lambda p, kept, grads: p.run_backward(kept[:3], grads, kept[3]),
+                                  n_smpls=lambda p: p.t2.lossless.n_smpls)
+
+
+class _Analysis(torch.autograd.Function):
+    """forward(path, plan, *sigs): plan = an analysis plan built from the utterances whose v_sig are sigs (tensors or host
+    arrays; the plan holds the samples as one float32 device buffer already), path = its _AnalysisPath.  Outputs: path.run's;
+    the per-utterance results are row views of them."""
 
     @staticmethod
-    def forward(ctx, plan, *sigs):
-        mag, real, imag = plan.run()
-        ctx.plan = plan
-        ctx.like = [(s.dtype, tuple(s.shape)) if torch.is_tensor(s) else None for s in sigs]
-        ctx.set_materialize_grads(False)     # an output nobody differentiated arrives as None: not read by the kernel
-        ctx.save_for_backward(mag, real, imag)
-        return mag, real, imag
+    def forward(ctx, path, plan, *sigs):
+        outs = tuple(path.run(plan))
+        ctx.path, ctx.plan = path, plan
+        ctx.like = _like(sigs)
+        ctx.set_materialize_grads(False)     # an output nobody differentiated arrives as None: not read by the kernels
+        if outs[3:]:
+            ctx.mark_non_differentiable(*outs[3:])
+        ctx.save_for_backward(*(outs[k] for k in path.keep))
+        return outs
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *grads):
-        mag, real, imag = ctx.saved_tensors
-        need_in = ctx.needs_input_grad[1:]
-        grads = tuple(g if g is None or (g.dtype == torch.float32 and g.is_contiguous())
-                      else g.to(torch.float32).contiguous() for g in grads)
-        with torch.cuda.device(mag.device):
-            gsig = ctx.plan.run_backward(mag, real, imag, grads)
-        out, a = [], 0
-        for like, need, n in zip(ctx.like, need_in, ctx.plan.n_smpls):
-            out.append(gsig[a:a + n].to(like[0]).reshape(like[1]) if like is not None and need else None)
-            a += n
-        return (None,) + tuple(out)
+        kept = ctx.saved_tensors
+        path, plan = ctx.path, ctx.plan
+        grads = tuple(_coerce(g) for g in grads[:3])
+        with torch.cuda.device(kept[0].device):
+            gsig = path.backward(plan, kept, grads)
+        return (None, None) + _scatter(gsig, _offsets(path.n_smpls(plan)), ctx.like, ctx.needs_input_grad[2:])
+
+
+def _analyze(path, plan, sigs):
+    plan.check_differentiable()      # what has no backward pass says so before the forward is launched
+    return _Analysis.apply(path, plan, *sigs)
 
 
 def analyze(plan, sigs):
     """plan.run(), differentiable with respect to the v_sig in sigs that are tensors requiring grad.  Returns the three
     float32 [total_frames x H] matrices (with grad_fn)."""
-    return _LosslessAnalysis.apply(plan, *sigs)
-
-
-class _CompressedAnalysis(torch.autograd.Function):
-    """forward(plan, *sigs): plan = a CompressedAnalysisPlan built from the utterances whose v_sig are sigs (tensors or
-    host arrays); plan.run() is the forward launch, plan.run_backward(...) the backward ones.  Outputs: the three float32
-    matrices of the batch ([total_out_frames x mag_dim], [.. x phase_dim] twice); the per-utterance results are row views of
-    them.  Only these three are kept for the backward pass."""
-
-    @staticmethod
-    def forward(ctx, plan, *sigs):
-        mag, real, imag = plan.run()
-        ctx.plan = plan
-        ctx.like = [(s.dtype, tuple(s.shape)) if torch.is_tensor(s) else None for s in sigs]
-        ctx.set_materialize_grads(False)     # an output nobody differentiated arrives as None: not read by the kernels
-        ctx.save_for_backward(mag, real, imag)
-        return mag, real, imag
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, *grads):
-        outs = ctx.saved_tensors
-        need_in = ctx.needs_input_grad[1:]
-        grads = tuple(g if g is None or (g.dtype == torch.float32 and g.is_contiguous())
-                      else g.to(torch.float32).contiguous() for g in grads)
-        with torch.cuda.device(outs[0].device):
-            gsig = ctx.plan.run_backward(outs, grads)
-        out, a = [], 0
-        for like, need, n in zip(ctx.like, need_in, ctx.plan.lossless.n_smpls):
-            out.append(gsig[a:a + n].to(like[0]).reshape(like[1]) if like is not None and need else None)
-            a += n
-        return (None,) + tuple(out)
+    return _analyze(_LOSSLESS, plan, sigs)
 
 
 def analyze_compressed(plan, sigs):
     """plan.run() of a CompressedAnalysisPlan, differentiable with respect to the v_sig in sigs that are tensors requiring
     grad.  Returns the three float32 device matrices (with grad_fn)."""
-    return _CompressedAnalysis.apply(plan, *sigs)
+    return _analyze(_COMPRESSED, plan, sigs)
 
 
-class _CompressedSynthesis(torch.autograd.Function):
-    """forward(plan, b_out_hpf, n_utts, *mats): plan = a CompressedSynthesisPlan built from the utterances whose
-    coefficient matrices are mats, utterance-major (m_mag_mel_log_0, m_real_mel_0, m_imag_mel_0, m_mag_mel_log_1, ...:
-    tensors or host arrays; the plan holds them packed as float32 device rows already); plan.run() and Engine.output_hpf
-    are the forward, plan.adjoint_hpf and plan.run_backward the backward.  Output: the ONE [total_out] waveform buffer
-    (float64 after the high-pass, float32 without it); the per-utterance signals are views of it."""
+def analyze_type2(plan, sigs):
+    """plan.run(want_iters=True) of a Type2AnalysisPlan, differentiable with respect to the v_sig in sigs that are tensors
+    requiring grad.  Returns (env, real, imag, gain, iters) as plan.run does, the three matrices with grad_fn."""
+    return _analyze(_TYPE2, plan, sigs)
+
+
+def analyze_compressed_type2(plan, sigs):
+    """plan.run(want_iters=True) of a Type2CompressedAnalysisPlan, differentiable with respect to the v_sig in sigs that are
+    tensors requiring grad.  Returns ((mag, real, imag) with grad_fn, gain)."""
+    mag, real, imag, gain, _iters = _analyze(_TYPE2_COMPRESSED, plan, sigs)
+    return (mag, real, imag), gain
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# coefficients -> waveform: the compressed, the type-2 and the magnitude-only synthesis
+# ------------------------------------------------------------------------------------------------------------------
+class _Synthesis(torch.autograd.Function):
+    """forward(plan, k, hpf, pass_need, *mats): plan = a CompressedSynthesisPlan (or one of its subclasses) built from the
+    utterances whose coefficient matrices are mats, utterance-major, k per utterance (tensors or host arrays; the plan holds
+    them packed as float32 device rows already); hpf = the output high-pass' design or None.  plan.run() and Engine.output_hpf
+    are the forward, plan.adjoint_hpf and plan.run_backward (given need= per stream with pass_need) the backward.  Output:
+    the ONE [total_out] waveform buffer (float64 after the high-pass, float32 without it); the per-utterance signals are
+    views of it.  Nothing is saved: the backward pass reads the plan's work buffers."""
 
     @staticmethod
-    def forward(ctx, plan, b_out_hpf, n_utts, *mats):
+    def forward(ctx, plan, k, hpf, pass_need, *mats):
         pcm = plan.run()
-        if b_out_hpf:
-            pcm = plan.engine.output_hpf(pcm, plan.out_off_host, plan.fs)
-        ctx.plan, ctx.hpf = plan, bool(b_out_hpf)
-        ctx.rows = [int(mats[3 * u].shape[0]) for u in range(n_utts)]
-        ctx.like = [(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else None for m in mats]
+        if hpf:
+            pcm = plan.engine.output_hpf(pcm, plan.out_off_host, plan.fs, design=hpf)
+        ctx.plan, ctx.k, ctx.hpf, ctx.pass_need = plan, k, hpf, pass_need
+        ctx.offs = _offsets(m.shape[0] for m in mats[::k])
+        ctx.like = _like(mats)
         return pcm
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
-        plan = ctx.plan
-        n_head = 3   # plan, b_out_hpf, n_utts
+        plan, k = ctx.plan, ctx.k
+        n_head = 4   # plan, k, hpf, pass_need
         need_in = ctx.needs_input_grad[n_head:]
-        need = tuple(any(need_in[k::3]) for k in range(3))
+        kw = dict(need=tuple(any(need_in[s::k]) for s in range(k))) if ctx.pass_need else {}
         with torch.cuda.device(grad_out.device):
-            if ctx.hpf:
-                g = plan.adjoint_hpf(grad_out)
-            else:
-                g = grad_out.to(torch.float32)
-            g = plan.run_backward(g.contiguous(), need=need)
-        out, a = [], 0
-        for u, n in enumerate(ctx.rows):
-            for k in range(3):
-                like = ctx.like[3 * u + k]
-                if like is None or not need_in[3 * u + k]:
-                    out.append(None)
-                else:
-                    out.append(g[k][a:a + n].to(like[0]).reshape(like[1]))
-            a += n
-        return (None,) * n_head + tuple(out)
+            g = plan.adjoint_hpf(grad_out, design=ctx.hpf) if ctx.hpf else grad_out
+            g = plan.run_backward(_coerce(g), **kw)
+        return (None,) * n_head + _scatter(g, ctx.offs, ctx.like, need_in)
+
+
+def _synthesize(plan, k, hpf, pass_need, mats):
+    plan.check_differentiable()      # what has no backward pass says so before the forward is launched
+    return _Synthesis.apply(plan, k, hpf, pass_need, *mats)
 
 
 def synthesize_compressed(plan, b_out_hpf, utts):
     """plan.run() of a CompressedSynthesisPlan (and the output high-pass), differentiable with respect to the coefficient
     matrices in utts = [(m_mag_mel_log, m_real_mel, m_imag_mel, v_lf0)] that are tensors requiring grad.  Returns the
     [total_out] waveform buffer (with grad_fn)."""
-    mats = [x for u in utts for x in u[:3]]
-    return _CompressedSynthesis.apply(plan, bool(b_out_hpf), len(utts), *mats)
-
-
-class _Type2Synthesis(torch.autograd.Function):
-    """forward(plan, n_utts, *mats): plan = a Type2SynthesisPlan built from the utterances whose coefficient matrices are
-    mats, utterance-major as for _CompressedSynthesis; plan.run() and Engine.output_hpf(design='ellip60') are the forward,
-    plan.adjoint_hpf(design='ellip60') and plan.run_backward the backward.  Output: the ONE float64 [total_out] waveform
-    buffer; the per-utterance signals are views of it."""
-
-    @staticmethod
-    def forward(ctx, plan, n_utts, *mats):
-        pcm = plan.engine.output_hpf(plan.run(), plan.out_off_host, plan.fs, design="ellip60")
-        ctx.plan = plan
-        ctx.rows = [int(mats[3 * u].shape[0]) for u in range(n_utts)]
-        ctx.like = [(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else None for m in mats]
-        return pcm
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_out):
-        plan = ctx.plan
-        n_head = 2   # plan, n_utts
-        need_in = ctx.needs_input_grad[n_head:]
-        need = tuple(any(need_in[k::3]) for k in range(3))
-        with torch.cuda.device(grad_out.device):
-            g = plan.run_backward(plan.adjoint_hpf(grad_out, design="ellip60").contiguous(), need=need)
-        out, a = [], 0
-        for u, n in enumerate(ctx.rows):
-            for k in range(3):
-                like = ctx.like[3 * u + k]
-                if like is None or not need_in[3 * u + k]:
-                    out.append(None)
-                else:
-                    out.append(g[k][a:a + n].to(like[0]).reshape(like[1]))
-            a += n
-        return (None,) * n_head + tuple(out)
+    return _synthesize(plan, 3, "butter40" if b_out_hpf else None, True, [x for u in utts for x in u[:3]])
 
 
 def synthesize_compressed_type2(plan, utts):
     """plan.run() of a Type2SynthesisPlan and the elliptic output high-pass, differentiable with respect to the coefficient
     matrices in utts = [(m_mag_mel_log, m_real_mel, m_imag_mel, v_lf0)] that are tensors requiring grad.  Returns the
     float64 [total_out] waveform buffer (with grad_fn)."""
-    plan._check_differentiable()     # what has no backward pass says so before the forward is launched
-    mats = [x for u in utts for x in u[:3]]
-    return _Type2Synthesis.apply(plan, len(utts), *mats)
+    return _synthesize(plan, 3, "ellip60", True, [x for u in utts for x in u[:3]])
 
 
+def synthesize_from_mag(plan, b_out_hpf, utts):
+    """plan.run() of a MagnitudeSynthesisPlan (and the output high-pass), differentiable with respect to the
+    m_mag_mel_log in utts = [(m_mag_mel_log, v_lf0)] that are tensors requiring grad.  Returns the [total_out] waveform
+    buffer (with grad_fn)."""
+    return _synthesize(plan, 1, "butter40" if b_out_hpf else None, False, [u[0] for u in utts])
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the rest: engine calls with a forward / backward of their own
+# ------------------------------------------------------------------------------------------------------------------
 class _TrueEnvelope(torch.autograd.Function):
     """forward(engine, in_type, ncoeffs, thres_db, *mats): mats = the [F_i x H] matrices of la.true_envelope_batch (tensors
     or host arrays); Engine.true_envelope is the forward launch, Engine.true_envelope_backward the backward one.  Outputs:
@@ -312,7 +283,7 @@ class _TrueEnvelope(torch.autograd.Function):
                                                    return_input=True)
         ctx.engine, ctx.in_type, ctx.ncoeffs = engine, in_type, ncoeffs
         ctx.offs, ctx.n_bins = [int(o) for o in offs], int(mats[0].shape[1])
-        ctx.like = [(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else None for m in mats]
+        ctx.like = _like(mats)
         ctx.mark_non_differentiable(iters)
         ctx.save_for_backward(x, iters)
         return out, iters
@@ -322,15 +293,10 @@ class _TrueEnvelope(torch.autograd.Function):
     def backward(ctx, grad_out, _grad_iters):
         x, iters = ctx.saved_tensors
         n_head = 4   # engine, in_type, ncoeffs, thres_db
-        need_in = ctx.needs_input_grad[n_head:]
-        if grad_out.dtype != torch.float32 or grad_out.stride(1) != 1:
-            grad_out = grad_out.to(torch.float32).contiguous()
+        grad_out = _coerce(grad_out, unit_cols=True)
         with torch.cuda.device(x.device):
             g = ctx.engine.true_envelope_backward(x, iters, grad_out, ctx.n_bins, ctx.in_type, ctx.ncoeffs)
-        out = []
-        for like, need, a, b in zip(ctx.like, need_in, ctx.offs[:-1], ctx.offs[1:]):
-            out.append(g[a:b, :ctx.n_bins].to(like[0]).reshape(like[1]) if like is not None and need else None)
-        return (None,) * n_head + tuple(out)
+        return (None,) * n_head + _scatter(g[:, :ctx.n_bins], ctx.offs, ctx.like, ctx.needs_input_grad[n_head:])
 
 
 def true_envelope(engine, mats, in_type, ncoeffs, thres_db):
@@ -341,85 +307,6 @@ def true_envelope(engine, mats, in_type, ncoeffs, thres_db):
     out, iters = _TrueEnvelope.apply(engine, in_type, int(ncoeffs), float(thres_db), *mats)
     offs = np.concatenate(([0], np.cumsum([int(m.shape[0]) for m in mats]))).astype(np.int64)
     return out, offs, iters
-
-
-class _Type2Analysis(torch.autograd.Function):
-    """forward(plan, *sigs): plan = a Type2AnalysisPlan built from the utterances whose v_sig are sigs (tensors or host
-    arrays); plan.run(want_iters=True) is the forward launch sequence, plan.run_backward the backward one.  Outputs: the
-    three float32 [total_frames x H] matrices of the batch (envelope, real, imag; the per-utterance results are row views
-    that leave out row 0), the float64 per-frame gain and the int32 passes per envelope row (neither differentiable).
-    Kept for the backward pass: the pass counts only -- both sets of rows are recomputed."""
-
-    @staticmethod
-    def forward(ctx, plan, *sigs):
-        env, real, imag, gain, iters = plan.run(want_iters=True)
-        ctx.plan = plan
-        ctx.like = [(s.dtype, tuple(s.shape)) if torch.is_tensor(s) else None for s in sigs]
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(gain, iters)
-        ctx.save_for_backward(iters)
-        return env, real, imag, gain, iters
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_env, g_real, g_imag, _g_gain, _g_iters):
-        (iters,) = ctx.saved_tensors
-        need_in = ctx.needs_input_grad[1:]
-        grads = tuple(g if g is None or (g.dtype == torch.float32 and g.is_contiguous())
-                      else g.to(torch.float32).contiguous() for g in (g_env, g_real, g_imag))
-        with torch.cuda.device(iters.device):
-            gsig = ctx.plan.run_backward(grads, iters)
-        out, a = [], 0
-        for like, need, n in zip(ctx.like, need_in, ctx.plan.lossless.n_smpls):
-            out.append(gsig[a:a + n].to(like[0]).reshape(like[1]) if like is not None and need else None)
-            a += n
-        return (None,) + tuple(out)
-
-
-def analyze_type2(plan, sigs):
-    """plan.run(want_iters=True) of a Type2AnalysisPlan, differentiable with respect to the v_sig in sigs that are tensors
-    requiring grad.  Returns (env, real, imag, gain, iters) as plan.run does, the three matrices with grad_fn."""
-    return _Type2Analysis.apply(plan, *sigs)
-
-
-class _Type2CompressedAnalysis(torch.autograd.Function):
-    """forward(plan, *sigs): plan = a Type2CompressedAnalysisPlan built from the utterances whose v_sig are sigs;
-    plan.run(want_iters=True) is the forward, plan.run_backward the backward.  Outputs: the three float32 matrices of the
-    batch ([total_out_frames x mag_dim], [.. x phase_dim] twice), the float64 per-frame gain and the int32 passes per
-    envelope row (neither differentiable).  Kept for the backward pass: the three small matrices and the pass counts."""
-
-    @staticmethod
-    def forward(ctx, plan, *sigs):
-        (mag, real, imag), gain, iters = plan.run(want_iters=True)
-        ctx.plan = plan
-        ctx.like = [(s.dtype, tuple(s.shape)) if torch.is_tensor(s) else None for s in sigs]
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(gain, iters)
-        ctx.save_for_backward(mag, real, imag, iters)
-        return mag, real, imag, gain, iters
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_mag, g_real, g_imag, _g_gain, _g_iters):
-        mag, real, imag, iters = ctx.saved_tensors
-        need_in = ctx.needs_input_grad[1:]
-        grads = tuple(g if g is None or (g.dtype == torch.float32 and g.is_contiguous())
-                      else g.to(torch.float32).contiguous() for g in (g_mag, g_real, g_imag))
-        with torch.cuda.device(mag.device):
-            gsig = ctx.plan.run_backward((mag, real, imag), grads, iters)
-        out, a = [], 0
-        for like, need, n in zip(ctx.like, need_in, ctx.plan.t2.lossless.n_smpls):
-            out.append(gsig[a:a + n].to(like[0]).reshape(like[1]) if like is not None and need else None)
-            a += n
-        return (None,) + tuple(out)
-
-
-def analyze_compressed_type2(plan, sigs):
-    """plan.run(want_iters=True) of a Type2CompressedAnalysisPlan, differentiable with respect to the v_sig in sigs that are
-    tensors requiring grad.  Returns ((mag, real, imag) with grad_fn, gain)."""
-    plan.check_grad_dims()           # what has no backward pass says so before the forward is launched
-    mag, real, imag, gain, _iters = _Type2CompressedAnalysis.apply(plan, *sigs)
-    return (mag, real, imag), gain
 
 
 class _MLPG(torch.autograd.Function):
@@ -439,7 +326,7 @@ class _MLPG(torch.autograd.Function):
         out = engine.mlpg_streams(buf, var, offs_dev, streams, windows)
         ctx.engine, ctx.streams, ctx.windows, ctx.width = engine, streams, windows, width
         ctx.offs = [int(o) for o in offs]
-        ctx.like = [(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else None for m in means]
+        ctx.like = _like(means)
         ctx.save_for_backward(var, offs_dev)
         return out
 
@@ -448,15 +335,10 @@ class _MLPG(torch.autograd.Function):
     def backward(ctx, grad_out):
         var, offs_dev = ctx.saved_tensors
         n_head = 5   # engine, var, streams, windows, width
-        need_in = ctx.needs_input_grad[n_head:]
-        if grad_out.dtype != torch.float64 or grad_out.stride(1) != 1 or not grad_out.is_contiguous():
-            grad_out = grad_out.to(torch.float64).contiguous()
+        grad_out = _coerce(grad_out, dtype=torch.float64)
         with torch.cuda.device(var.device):
             g = ctx.engine.mlpg_streams_backward(grad_out, var, offs_dev, ctx.streams, ctx.windows, ctx.width)
-        out = []
-        for like, need, a, b in zip(ctx.like, need_in, ctx.offs[:-1], ctx.offs[1:]):
-            out.append(g[a:b].to(like[0]).reshape(like[1]) if like is not None and need else None)
-        return (None,) * n_head + tuple(out)
+        return (None,) * n_head + _scatter(g, ctx.offs, ctx.like, ctx.needs_input_grad[n_head:])
 
 
 def mlpg(engine, means, var, streams, windows, width):
@@ -465,60 +347,19 @@ def mlpg(engine, means, var, streams, windows, width):
     return _MLPG.apply(engine, var, streams, windows, int(width), *means)
 
 
-class _MagnitudeSynthesis(torch.autograd.Function):
-    """forward(plan, b_out_hpf, n_utts, *mats): plan = a MagnitudeSynthesisPlan built from the utterances whose
-    m_mag_mel_log are mats (tensors or host arrays; the plan holds them packed as float32 device rows already); plan.run()
-    and Engine.output_hpf are the forward, plan.adjoint_hpf and plan.run_backward (k_synth_comp_bwd, k_min_phase_bwd,
-    k_rows_lerp_adjoint, k_mel_unwarp_bwd: DESIGN.md section 3.3o) the backward.  Output: the ONE [total_out] waveform
-    buffer (float64 after the high-pass, float32 without it); the per-utterance signals are views of it."""
-
-    @staticmethod
-    def forward(ctx, plan, b_out_hpf, n_utts, *mats):
-        pcm = plan.run()
-        if b_out_hpf:
-            pcm = plan.engine.output_hpf(pcm, plan.out_off_host, plan.fs)
-        ctx.plan, ctx.hpf = plan, bool(b_out_hpf)
-        ctx.rows = [int(m.shape[0]) for m in mats]
-        ctx.like = [(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else None for m in mats]
-        return pcm
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_out):
-        plan = ctx.plan
-        n_head = 3   # plan, b_out_hpf, n_utts
-        need_in = ctx.needs_input_grad[n_head:]
-        with torch.cuda.device(grad_out.device):
-            g = plan.adjoint_hpf(grad_out) if ctx.hpf else grad_out.to(torch.float32)
-            g = plan.run_backward(g.contiguous())
-        out, a = [], 0
-        for like, need, n in zip(ctx.like, need_in, ctx.rows):
-            out.append(g[a:a + n].to(like[0]).reshape(like[1]) if like is not None and need else None)
-            a += n
-        return (None,) * n_head + tuple(out)
-
-
-def synthesize_from_mag(plan, b_out_hpf, utts):
-    """plan.run() of a MagnitudeSynthesisPlan (and the output high-pass), differentiable with respect to the
-    m_mag_mel_log in utts = [(m_mag_mel_log, v_lf0)] that are tensors requiring grad.  Returns the [total_out] waveform
-    buffer (with grad_fn)."""
-    plan.check_differentiable()      # what has no backward pass says so before the forward is launched
-    return _MagnitudeSynthesis.apply(plan, bool(b_out_hpf), len(utts), *[u[0] for u in utts])
-
-
 class _MinPhase(torch.autograd.Function):
     """forward(engine, *mats): mats = the [F_i x H] magnitude matrices of la.build_min_phase_from_mag_spec_batch (tensors or
     host arrays); Engine.min_phase_rows (ONE mpx_min_phase launch over all rows) is the forward, mpx_min_phase_backward the
     backward.  Outputs: the unit phasor rows (cos phi, sin phi) of all matrices, float32 [sum F_i x H] views at the spectra's
     row pitch; the product with the magnitudes is the caller's (plain torch).  Kept for the backward pass: the three rows
-    the forward wrote."""
+    the forward wrote.  The incoming gradients go to the kernel as they arrive."""
 
     @staticmethod
     def forward(ctx, engine, *mats):
         o_m, o_r, o_i = engine.min_phase_rows(list(mats))
         ctx.engine = engine
-        ctx.rows = [int(m.shape[0]) for m in mats]
-        ctx.like = [(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else None for m in mats]
+        ctx.offs = _offsets(m.shape[0] for m in mats)
+        ctx.like = _like(mats)
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(o_m, o_r, o_i)
         return o_r, o_i
@@ -527,14 +368,9 @@ class _MinPhase(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g_r, g_i):
         o_m, o_r, o_i = ctx.saved_tensors
-        need_in = ctx.needs_input_grad[1:]
         with torch.cuda.device(o_m.device):
             g = ctx.engine.min_phase_backward(o_m, o_r, o_i, None, g_r, g_i)
-        out, a = [], 0
-        for like, need, n in zip(ctx.like, need_in, ctx.rows):
-            out.append(g[a:a + n].to(like[0]).reshape(like[1]) if like is not None and need else None)
-            a += n
-        return (None,) + tuple(out)
+        return (None,) + _scatter(g, ctx.offs, ctx.like, ctx.needs_input_grad[1:])
 
 
 def min_phase(engine, mats):
@@ -557,7 +393,7 @@ class _PostFilter(torch.autograd.Function):
         out = engine.post_filter_merlin(x, fs, **kw) if pf_type == "merlin" else engine.post_filter(x, fs, **kw)
         ctx.engine, ctx.pf_type, ctx.fs, ctx.kw = engine, pf_type, fs, kw
         ctx.offs = [int(o) for o in offs]
-        ctx.like = [(m.dtype, tuple(m.shape)) if torch.is_tensor(m) else None for m in mats]
+        ctx.like = _like(mats)
         if pf_type == "merlin":
             ctx.save_for_backward(x)
         else:
@@ -568,7 +404,6 @@ class _PostFilter(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_out):
         n_head = 4   # engine, pf_type, fs, opts
-        need_in = ctx.needs_input_grad[n_head:]
         with torch.cuda.device(grad_out.device):
             if ctx.pf_type == "merlin":
                 (x,) = ctx.saved_tensors
@@ -576,10 +411,7 @@ class _PostFilter(torch.autograd.Function):
             else:
                 ctx.saved_tensors   # (none kept; raises as torch does when the graph was freed)
                 g = ctx.engine.post_filter_backward(grad_out, ctx.fs, **ctx.kw)
-        out = []
-        for like, need, a, b in zip(ctx.like, need_in, ctx.offs[:-1], ctx.offs[1:]):
-            out.append(g[a:b].to(like[0]).reshape(like[1]) if like is not None and need else None)
-        return (None,) * n_head + tuple(out)
+        return (None,) * n_head + _scatter(g, ctx.offs, ctx.like, ctx.needs_input_grad[n_head:])
 
 
 def post_filter(engine, mats, pf_type, fs, opts):

@@ -184,6 +184,20 @@ def check_feature_tensor(t, name, lf0=False):
         raise ValueError("%s: must be 2-D [rows x width], got %d-D" % (name, t.dim()))
 
 
+def wants_grad(return_device, candidates, cpu_too=False):
+    """THE rule for running a call inside its torch.autograd.Function (magphase_amd/autograd.py): the result stays on the
+    device, torch is loaded, grad mode is on, and one of candidates (the call's flattened differentiable inputs, tensors
+    or host arrays) is a tensor that is not on the CPU and requires grad -- a CPU tensor is a host array to every path.
+    cpu_too: a CPU tensor that requires grad counts as well (la.true_envelope_batch alone).  Imports neither torch nor the
+    engine."""
+    import sys
+
+    torch = sys.modules.get("torch")
+    return bool(return_device and torch is not None and torch.is_grad_enabled()
+                and any(torch.is_tensor(x) and x.requires_grad and (cpu_too or x.device.type != "cpu")
+                        for x in candidates))
+
+
 def rows_pack_table(streams):
     """
     The descriptor table of mpx_rows_pack: streams is a list (at most three) of lists of 2-D tensors, streams[s][u] =

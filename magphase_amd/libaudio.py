@@ -415,9 +415,7 @@ def build_min_phase_from_mag_spec_batch(l_m_mag, return_device=False, engine=Non
         else:
             mats[k] = np.atleast_2d(np.asarray(m))
     offs = np.concatenate(([0], np.cumsum([int(m.shape[0]) for m in mats]))).astype(np.int64)
-    want_grad = bool(return_device and torch is not None and torch.is_grad_enabled()
-                     and any(t and m.requires_grad for t, m in zip(is_t, mats)))
-    if want_grad:
+    if hm.wants_grad(return_device, mats):   # (CPU tensors are host arrays by now)
         from .autograd import min_phase
 
         o_m, (o_r, o_i) = None, min_phase(e, mats)
@@ -548,10 +546,9 @@ def true_envelope_batch(list_of_matrices, in_type="abs", ncoeffs=60, thres_db=0.
     hm.true_envelope_check(int(mats[0].shape[1]), in_type, ncoeffs)
     from .engine import get_engine
 
-    import torch
-
     e = get_engine()
-    if return_device and torch.is_grad_enabled() and any(torch.is_tensor(m) and m.requires_grad for m in mats):
+    # cpu_too: _te_inputs leaves a CPU tensor a tensor, and one that requires grad has always gone into the Function
+    if hm.wants_grad(return_device, mats, cpu_too=True):
         from . import autograd
 
         out, offs, iters = autograd.true_envelope(e, mats, in_type, int(ncoeffs), float(thres_db))

@@ -291,13 +291,8 @@ def analysis_lossless_batch(utts, fft_len=None, engine=None, return_device=False
 
 def _run_lossless_analysis(plan, utts, return_device):
     """plan.run() -> the batch's three float32 device matrices.  Through autograd.analyze -- the same launch inside a
-    torch.autograd.Function -- when the result stays on the device, grad mode is on and some v_sig is a device tensor that
-    requires grad (a CPU tensor is a host array to the plan)."""
-    import sys
-
-    torch = sys.modules.get("torch")
-    if (return_device and torch is not None and torch.is_grad_enabled()
-            and any(torch.is_tensor(u[0]) and u[0].requires_grad and u[0].device.type != "cpu" for u in utts)):
+    torch.autograd.Function -- under hostmath.wants_grad's rule for the v_sig (a CPU tensor is a host array to the plan)."""
+    if hm.wants_grad(return_device, [u[0] for u in utts]):
         from .autograd import analyze
 
         return analyze(plan, [u[0] for u in utts])
@@ -353,13 +348,9 @@ def synthesis_from_lossless_batch(feats, engine=None, return_device=False):
 
 def _run_lossless_synthesis(engine, plan, feats, H, return_device):
     """plan.run on the packed matrices of feats (_feats_cat_device) -> the float32 [total_out] device buffer.  Through
-    autograd.synthesize -- the same two calls inside a torch.autograd.Function -- when the result stays on the device,
-    grad mode is on and one of the matrices is a tensor that requires grad (CPU tensors are host arrays by now)."""
-    import sys
-
-    torch = sys.modules.get("torch")
-    if (return_device and torch is not None and torch.is_grad_enabled()
-            and any(torch.is_tensor(x) and x.requires_grad for f in feats for x in f[:3])):
+    autograd.synthesize -- the same two calls inside a torch.autograd.Function -- under hostmath.wants_grad's rule for the
+    matrices (CPU tensors are host arrays by now)."""
+    if hm.wants_grad(return_device, [x for f in feats for x in f[:3]]):
         from .autograd import synthesize
 
         return synthesize(plan, lambda fs_: _feats_cat_device(engine, fs_, H), feats)
@@ -824,8 +815,7 @@ def post_filter_batch(mats, fs, pf_type='magphase', pf_coef=1.4, av_len_at_zero=
     engine = engine or get_engine()
     import torch
 
-    wants_grad = bool(return_device and torch.is_grad_enabled()
-                      and any(_is_device_tensor(m) and m.requires_grad for m in mats))
+    wants_grad = hm.wants_grad(return_device, mats)
     total = int(sum(int(m.shape[0]) for m in mats))
     if total == 0:
         out = torch.zeros((0, D), dtype=torch.float32, device=engine.device)
@@ -856,16 +846,6 @@ def _output_hpf(v_syn_sig, fs):
 
     v_b, v_a = signal.butter(4, 40 / (fs / 2.0), btype='highpass')
     return signal.lfilter(v_b, v_a, v_syn_sig)
-
-
-def _compressed_synthesis_wants_grad(utts, return_device):
-    """The result stays on the device, grad mode is on and one of the coefficient matrices is a device tensor that
-    requires grad (CPU tensors take the host path)."""
-    import sys
-
-    torch = sys.modules.get("torch")
-    return bool(return_device and torch is not None and torch.is_grad_enabled()
-                and any(torch.is_tensor(x) and x.requires_grad and x.device.type != "cpu" for u in utts for x in u[:3]))
 
 
 def synthesis_from_compressed_batch(utts, fs, fft_len=None, b_voi_ap_win=True, b_const_rate=False, alpha_phase=None,
@@ -909,7 +889,7 @@ def synthesis_from_compressed_batch(utts, fs, fft_len=None, b_voi_ap_win=True, b
     recomputes the noise spectra).  No double backward."""
     if return_device and async_out:
         raise ValueError("return_device and async_out exclude each other (async_out is a download)")
-    want_grad = _compressed_synthesis_wants_grad(utts, return_device)
+    want_grad = hm.wants_grad(return_device, [x for u in utts for x in u[:3]])   # (CPU tensors take the host path)
     if want_grad:   # what has no backward pass says so before anything is built
         if per_phase_type in ('min_phase', 'linear'):
             raise NotImplementedError("per_phase_type=%r has no backward pass: only 'magphase' is differentiable"
@@ -990,11 +970,7 @@ def synthesis_from_mag_batch(utts, fs, fft_len=None, phase='min_phase', b_voi_ap
     utts = [tuple(u) for u in utts]
     if any(len(u) != 2 for u in utts):
         raise ValueError("utts: a list of (m_mag_mel_log, v_lf0)")
-    import sys
-
-    torch = sys.modules.get("torch")
-    want_grad = bool(return_device and torch is not None and torch.is_grad_enabled()
-                     and any(torch.is_tensor(u[0]) and u[0].requires_grad and u[0].device.type != "cpu" for u in utts))
+    want_grad = hm.wants_grad(return_device, [u[0] for u in utts])
     if want_grad:   # what has no backward pass says so before anything is built
         if b_post_filter and b_post_filter != 'no':
             raise NotImplementedError("b_post_filter=%r has no backward pass" % (b_post_filter,))
@@ -1140,13 +1116,9 @@ def analysis_compressed_batch(utts, fft_len=None, mag_dim=60, phase_dim=10, b_co
 
 def _run_compressed_analysis(plan, utts):
     """plan.run() -> the batch's three float32 device matrices, for return_device.  Through autograd.analyze_compressed --
-    the same launch inside a torch.autograd.Function -- when grad mode is on and some v_sig is a device tensor that requires
-    grad (a CPU tensor is a host array to the plan; a prepared= batch was built from host arrays)."""
-    import sys
-
-    torch = sys.modules.get("torch")
-    if (torch is not None and torch.is_grad_enabled()
-            and any(torch.is_tensor(u[0]) and u[0].requires_grad and u[0].device.type != "cpu" for u in utts)):
+    the same launch inside a torch.autograd.Function -- under hostmath.wants_grad's rule for the v_sig (a CPU tensor is a
+    host array to the plan; a prepared= batch was built from host arrays)."""
+    if hm.wants_grad(True, [u[0] for u in utts]):
         from .autograd import analyze_compressed
 
         return analyze_compressed(plan, [u[0] for u in utts])
@@ -1222,16 +1194,6 @@ def _is_device_tensor(x):
     return torch is not None and torch.is_tensor(x) and x.device.type != "cpu"
 
 
-def _wants_grad(utts, return_device):
-    """A type-2 analysis call runs inside its torch.autograd.Function when the result stays on the device, grad mode is on
-    and some v_sig is a device tensor that requires grad (the rule of _run_lossless_analysis)."""
-    import sys
-
-    torch = sys.modules.get("torch")
-    return bool(return_device and torch is not None and torch.is_grad_enabled()
-                and any(_is_device_tensor(u[0]) and u[0].requires_grad for u in utts))
-
-
 def _type2_check(utts, fft_len):
     """Host argument checks of the type-2 analysis: (v_sig, fs, v_pm_sec, v_voi) tuples, one fft_len the device path
     takes (1024, 2048 or 4096) for the whole call, epochs and voicing of one length."""
@@ -1284,7 +1246,7 @@ def analysis_lossless_type2_batch(utts, fft_len=None, engine=None, return_device
     for lens in plan.long_frame_lens:
         for n in lens:  # Q19: truncation warns, it does not raise (magphase.py:311-315)
             warnings.warn(_WARN_LONG % (plan.fft_len, n))
-    if _wants_grad(utts, return_device):
+    if hm.wants_grad(return_device, [u[0] for u in utts]):
         from .autograd import analyze_type2
 
         env, real, imag, gain, iters = analyze_type2(plan, [u[0] for u in utts])
@@ -1360,7 +1322,7 @@ def analysis_compressed_type2_batch(utts, fft_len=None, mag_dim=60, phase_dim=45
     for lens in plan.t2.long_frame_lens:
         for n in lens:
             warnings.warn(_WARN_LONG % (plan.fft_len, n))
-    with_grad = _wants_grad(utts, return_device)
+    with_grad = hm.wants_grad(return_device, [u[0] for u in utts])
     if with_grad:
         from .autograd import analyze_compressed_type2
 
@@ -1482,7 +1444,7 @@ def synthesis_from_compressed_type2_batch(utts, fs, fft_len=None, hf_slope_coeff
     utts = list(utts)
     if not utts:
         return []
-    want_grad = _compressed_synthesis_wants_grad(utts, return_device)
+    want_grad = hm.wants_grad(return_device, [x for u in utts for x in u[:3]])   # (CPU tensors take the host path)
     if want_grad and pcm16_norm is not False:   # what has no backward pass says so before anything is built
         raise NotImplementedError("pcm16_norm=%r (int16 output) has no backward pass" % (pcm16_norm,))
     utts, on_dev = _tensor_inputs(utts, _SYN_NAMES, lf0_at=3)
@@ -1571,13 +1533,11 @@ def _mlpg_device_var(engine, var, per_frame, width):
 def _mlpg_run(engine, means, var, per_frame, w, streams, width, return_device):
     """The launches of mlpg_batch / mlpg_streams_batch -> (float64 device buffer [sum F_i x sum D] (None when the batch has
     no frames), packed means or None, row offsets)."""
-    import torch
-
     offs = np.concatenate(([0], np.cumsum([int(m.shape[0]) for m in means]))).astype(np.int64)
     if int(offs[-1]) == 0:
         return None, None, offs
     var_dev = _mlpg_device_var(engine, var, per_frame, width)
-    if return_device and torch.is_grad_enabled() and any(torch.is_tensor(m) and m.requires_grad for m in means):
+    if hm.wants_grad(return_device, means):   # (hm.mlpg_check made host arrays of CPU tensors)
         from . import autograd
 
         buf = None

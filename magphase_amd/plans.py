@@ -386,6 +386,9 @@ class LosslessAnalysisPlan:
             self._bwd = (self.engine.to_device(soff, np.int64), int(soff[-1]))
         return self._bwd
 
+    def check_differentiable(self):
+        """What run_backward cannot take, said before any launch: nothing."""
+
     def run_backward(self, mag, real, imag, grads):
         """The gradient of a loss with respect to the batch's samples, float32 [total_smpls] (utterance u at the offset
         of its samples in self.sig), given mag / real / imag = run()'s rows and grads = (dL/d mag, dL/d real, dL/d imag)
@@ -522,6 +525,9 @@ class LosslessSynthesisPlan:
             d = self.engine.to_device_packed([("pos", pos, np.int64), ("lo", lo, np.int32), ("hi", hi, np.int32)])
             self._bwd = (d["pos"], d["lo"], d["hi"])
         return self._bwd
+
+    def check_differentiable(self):
+        """What run_backward cannot take, said before any launch: nothing."""
 
     def run_backward(self, grad_out, mag, real, imag, need=(True, True, True)):
         """The gradients of run()'s waveform with respect to the rows of mag / real / imag, given grad_out = dL/d(waveform)
@@ -747,6 +753,9 @@ class LosslessConstRateSynthesisPlan:
         return _run_ola(e, lambda strips, out: e.synthesis_lossless_ola_lerp(self.fft_len, mag, real, imag, self.rows, s,
                                                                               strips, out),
                         self.fft_len, s, strips, out, self.total_out)
+
+    def check_differentiable(self):
+        """What run_backward cannot take, said before any launch: nothing."""
 
     def run_backward(self, grad_out, mag, real, imag, need=(True, True, True)):
         """The gradients of run()'s waveform with respect to the constant-rate rows of mag / real / imag, given grad_out
@@ -1318,7 +1327,8 @@ class CompressedSynthesisPlan:
             self._bwd = b
         return b
 
-    def _check_differentiable(self):
+    def check_differentiable(self):
+        """What run_backward cannot take, said before any launch."""
         if not self._bwd_entry:
             raise NotImplementedError("%s has no backward pass" % type(self).__name__)
         if self.per_phase_type != "magphase":
@@ -1345,7 +1355,15 @@ class CompressedSynthesisPlan:
         stores them, MAGPHASE_NOISE_SPECTRA=store, is differentiated the same way and the stored spectra are not read),
         at the constant rate k_rows_lerp_adjoint at width H and the forward's unwarp again at the rows' rate (E),
         k_mel_unwarp_bwd (up to three jobs in one launch), at the constant rate k_rows_lerp_adjoint at width phase_dim."""
-        self._check_differentiable()
+        return self._run_backward(grad_pcm, "spec", tuple(bool(n) for n in need), mark=mark)
+
+    def _run_backward(self, grad_pcm, spec, need, min_phase=False, phase_jobs=True, mark=None):
+        """The body of run_backward, here and in MagnitudeSynthesisPlan.  spec: the key of the three work-buffer rows the
+        pair kernel read ('spec', or 'spec_v': k_min_phase's outputs); need: which of the per-frame gradient rows (g_m, g_a,
+        g_b) k_synth_comp_bwd writes; min_phase: k_min_phase_bwd folds g_a / g_b into g_m (in place) after it; phase_jobs:
+        k_mel_unwarp_bwd runs the phase jobs that need[1:] ask for (false: the magnitude job alone, no phase operand).
+        -> (o_m, o_a, o_b), None where not computed."""
+        self.check_differentiable()
         torch = _torch()
         e, N = self.engine, self.fft_len
         H = N // 2 + 1
@@ -1353,27 +1371,31 @@ class CompressedSynthesisPlan:
         mark = mark or (lambda name: None)
         if (grad_pcm.dtype != torch.float32 or int(grad_pcm.numel()) != self.total_out or not grad_pcm.is_contiguous()):
             raise ValueError("run_backward: grad_pcm must be a contiguous float32 [%d]" % self.total_out)
-        need = tuple(bool(n) for n in need)
-        dims = (self.mag_dim, self.phase_dim, self.phase_dim)
+        want = need if phase_jobs else (need[0], False, False)
         if F == 0 or R == 0 or not any(need):
             return tuple(torch.zeros((R, d), dtype=torch.float32, device=e.device) if n else None
-                         for n, d in zip(need, dims))
+                         for n, d in zip(want, (self.mag_dim, self.phase_dim, self.phase_dim)))
         buf = getattr(self, "_buf", None)
         if buf is None:
             raise RuntimeError("run_backward: call run() first (the backward pass reads the forward's unwarped rows)")
         t = self.backward_tables()
         ld = buf["ld"]
-        mag, real, imag = buf["spec"]
+        mag, real, imag = buf[spec]
         n_per = int(self.n_per)
         n_ph = min((n_per + 63) // 64 * 64, H)
+        tab = e.tables(N)
         mark("start")
         # per-frame gradient rows, allocated apart from spec (whose rows the kernel reads)
         g_m, g_a, g_b = (e.empty((F, ld))[:, :H] if n else None for n in need)
-        e.launch(self._bwd_entry, N, e.tables(N), grad_pcm, self.total_out, t["pos"], t["lo"], t["hi"],
+        e.launch(self._bwd_entry, N, tab, grad_pcm, self.total_out, t["pos"], t["lo"], t["hi"],
                  F, mag, real, imag, ld, self.noise, self.npos, self.nleft, self.nright, self.wtype, self.voiced,
                  buf["inv_gain"], self.win_l, self.win_r, self.per_v, self.ap_v, self.ap_u, n_per, g_m, g_a, g_b, ld)
         mark("k_synth_comp_bwd")
-        e_mag, ld_e, g_e, ld_g = mag, ld, g_m, ld
+        if min_phase:   # in place: element k of a row is read and written by one lane
+            e.launch("mpx_min_phase_backward", N, tab, mag, real, imag, ld, g_m, g_a, g_b, ld, n_ph, F, g_m, ld)
+            mark("k_min_phase_bwd")
+        # E, the unwarped magnitude the mel unwarp's backward multiplies by: spec's, whichever rows the pair kernel read
+        e_mag, g_e, ld_g = buf["spec"][0], g_m, ld
         if self.b_const_rate and need[0]:
             g_e = e.rows_lerp_adjoint((g_m, None, None), t["adj"], self.rowt, R)[0]
             ld_g = int(g_e.stride(0))
@@ -1385,12 +1407,17 @@ class CompressedSynthesisPlan:
             del s_r, s_i
             mark("k_mel_unwarp_mfma")
         o_m = e.empty((R, self.mag_dim)) if need[0] else None
-        n_prow = F if self.b_const_rate else R      # (variable rate: rows == frames)
-        o_a, o_b = (e.empty((n_prow, self.phase_dim)) if n else None for n in need[1:])
-        e.launch("mpx_mel_unwarp_backward", H, e_mag, ld_e, g_e, ld_g, self.u_mag, self.mag_dim, R, o_m, g_a, g_b, ld, n_ph,
-                 self.u_phase, self.phase_dim, n_prow, o_a, o_b)
+        if phase_jobs:
+            n_prow = F if self.b_const_rate else R      # (variable rate: rows == frames)
+            o_a, o_b = (e.empty((n_prow, self.phase_dim)) if n else None for n in need[1:])
+            u_phase = self.u_phase
+        else:   # the magnitude job alone
+            g_a = g_b = o_a = o_b = u_phase = None
+            n_ph = n_prow = 0
+        e.launch("mpx_mel_unwarp_backward", H, e_mag, ld, g_e, ld_g, self.u_mag, self.mag_dim, R, o_m, g_a, g_b, ld, n_ph,
+                 u_phase, self.phase_dim, n_prow, o_a, o_b)
         mark("k_mel_unwarp_bwd")
-        if self.b_const_rate and (need[1] or need[2]):
+        if self.b_const_rate and (o_a is not None or o_b is not None):
             _none, o_a, o_b = e.rows_lerp_adjoint((None, o_a, o_b), t["adj"], self.rowt, R)
             mark("k_rows_lerp_adjoint")
         return o_m, o_a, o_b
@@ -1452,10 +1479,10 @@ class Type2SynthesisPlan(CompressedSynthesisPlan):
             e.constant(("bin_curve_t2", k, int(fs), N, self.hf_slope_coeff), lambda k=k: self._bin_curves_host()[k])
             for k in range(3))
 
-    def _check_differentiable(self):
+    def check_differentiable(self):
         """run_backward serves this plan as it stands: u_phase and n_per are the type-2 ones, the
         gain is constant.  What k_mel_unwarp_bwd cannot take is said here, before any launch."""
-        super()._check_differentiable()
+        super().check_differentiable()
         check_type2_grad_dims(self.mag_dim, self.phase_dim)
 
     @property
@@ -1528,8 +1555,8 @@ class MagnitudeSynthesisPlan(CompressedSynthesisPlan):
                          defer_rng=defer_rng)
 
     def check_differentiable(self):
-        """What run_backward cannot take, said before any launch.  (CompressedSynthesisPlan._check_differentiable and its
-        refusal of these per_phase_types stand: this plan has a backward pass of its own.)"""
+        """What run_backward cannot take, said before any launch.  The plan's own rules, not CompressedSynthesisPlan's: its
+        per_phase_type is the one this backward pass is for."""
         if self.apply_post_filter:
             raise NotImplementedError("b_post_filter has no backward pass")
         if int(self.mag_dim) > 64:
@@ -1540,58 +1567,63 @@ class MagnitudeSynthesisPlan(CompressedSynthesisPlan):
         """The gradient of run()'s waveform with respect to the magnitude rows a_mag, float32 [n_rows x mag_dim], given
         grad_pcm = dL/d(run()'s result): contiguous float32 [total_out].  After run(): the rows the pair kernel read and
         the noise gains are taken from the plan's work buffers."""
-        self.check_differentiable()
-        torch = _torch()
-        e, N = self.engine, self.fft_len
-        H = N // 2 + 1
-        F, R = self.total_frames, self.n_rows
-        mark = mark or (lambda name: None)
-        if (grad_pcm.dtype != torch.float32 or int(grad_pcm.numel()) != self.total_out or not grad_pcm.is_contiguous()):
-            raise ValueError("run_backward: grad_pcm must be a contiguous float32 [%d]" % self.total_out)
-        if F == 0 or R == 0:
-            return torch.zeros((R, self.mag_dim), dtype=torch.float32, device=e.device)
-        buf = getattr(self, "_buf", None)
-        if buf is None:
-            raise RuntimeError("run_backward: call run() first (the backward pass reads the forward's unwarped rows)")
-        t = self.backward_tables()
-        ld = buf["ld"]
         min_phase = self.phase == "min_phase"
         # the rows k_synth_comp_pair read: k_min_phase's outputs, or the unwarped magnitude beside the constant phasor 1 + 0j
-        mag, real, imag = buf["spec_v"] if min_phase else buf["spec"]
-        n_per = int(self.n_per)
-        n_ph = min((n_per + 63) // 64 * 64, H)
-        tab = e.tables(N)
-        mark("start")
-        g_m = e.empty((F, ld))[:, :H]
-        g_a, g_b = (e.empty((F, ld))[:, :H] for _ in range(2)) if min_phase else (None, None)
-        e.launch(self._bwd_entry, N, tab, grad_pcm, self.total_out, t["pos"], t["lo"], t["hi"],
-                 F, mag, real, imag, ld, self.noise, self.npos, self.nleft, self.nright, self.wtype, self.voiced,
-                 buf["inv_gain"], self.win_l, self.win_r, self.per_v, self.ap_v, self.ap_u, n_per, g_m, g_a, g_b, ld)
-        mark("k_synth_comp_bwd")
-        if min_phase:   # in place: element k of a row is read and written by one lane
-            e.launch("mpx_min_phase_backward", N, tab, mag, real, imag, ld, g_m, g_a, g_b, ld, n_ph, F, g_m, ld)
-            mark("k_min_phase_bwd")
-        e_mag, g_e, ld_g = buf["spec"][0], g_m, ld
-        if self.b_const_rate:
-            g_e = e.rows_lerp_adjoint((g_m, None, None), t["adj"], self.rowt, R)[0]
-            ld_g = int(g_e.stride(0))
-            mark("k_rows_lerp_adjoint")
-            # E = exp(U_mag^T a_mag) at the rows' rate: the forward's unwarp again (its phase outputs are scratch)
-            e_mag, s_r, s_i = (e.empty((R, ld)) for _ in range(3))
-            e.launch("mpx_mel_unwarp", R, H, self.a_mag, self.mag_dim, self.u_mag, e_mag, self.a_real, self.a_imag,
-                     self.phase_dim, self.u_phase, s_r, s_i, ld)
-            del s_r, s_i
-            mark("k_mel_unwarp_mfma")
-        o_m = e.empty((R, self.mag_dim))
-        e.launch("mpx_mel_unwarp_backward", H, e_mag, ld, g_e, ld_g, self.u_mag, self.mag_dim, R, o_m, None, None, ld, 0,
-                 None, self.phase_dim, 0, None, None)
-        mark("k_mel_unwarp_bwd")
-        return o_m
+        return self._run_backward(grad_pcm, "spec_v" if min_phase else "spec", (True, min_phase, min_phase),
+                                  min_phase=min_phase, phase_jobs=False, mark=mark)[0]
 
 
 # ======================================================================================================
 # compressed-feature analysis (magphase.py:2947-2988, 2490-2544)
 # ======================================================================================================
+def _check_warp_grads(plan, grads):
+    """The (dL/d m_mag_mel_log, dL/d m_real_mel, dL/d m_imag_mel) a compressed analysis' run_backward takes."""
+    torch, Fo = _torch(), plan.total_out_frames
+    for g, shp in zip(grads, ((Fo, plan.mag_dim), (Fo, plan.phase_dim), (Fo, plan.phase_dim))):
+        if g is not None and (g.dtype != torch.float32 or tuple(g.shape) != shp or not g.is_contiguous()):
+            raise ValueError("run_backward: gradients must be contiguous float32 of the outputs' shapes")
+
+
+def _lerp_adjoint_table(plan, n_var):
+    """The frame ranges of the row interpolation's adjoint over the plan's n_var variable-rate rows
+    (hostmath.lerp_adjoint_table of its host row tables), uploaded by the first backward pass."""
+    if getattr(plan, "_adj", None) is None:
+        r0, r1, rt = plan._rows_host
+        plan._adj = plan.engine.to_device(hm.lerp_adjoint_table(r0, r1, rt, n_var).reshape(-1), np.int32)
+    return plan._adj
+
+
+def _warp_backward(plan, outs, grads, rows, tabs, live, n_var, mask_nonfinite=False, mark=None):
+    """The gradients of a compressed analysis' three matrices taken back through the two mel warps, onto the n_var
+    variable-rate rows = (mag, real, imag) the warps read (recomputed by the caller): k_phase_grad_mask (the forward's
+    voicing mask and clip, read from outs), k_mel_warp_bwd (the three jobs in one launch; live: the phase job's row flags
+    or None) and, where the forward read its rows through the row tables tabs = (row0, row1, rowt) (None: output rows ==
+    rows), k_rows_lerp_adjoint at width phase_dim before it and on the magnitude gradients after it.  mask_nonfinite: an
+    output frame whose log-mel row the forward wrote non-finite gets a zero magnitude gradient.  -> per-row gradients."""
+    e, H = plan.engine, int(plan.fft_len) // 2 + 1
+    mark = mark or (lambda name: None)
+    g_m, g_r, g_i = grads
+    h_r, h_i = e.phase_grad_mask(outs[1], outs[2], plan.voi, g_r, g_i)
+    if tabs is not None:
+        # the masked phase gradients onto the variable-rate rows the forward interpolated from (width phase_dim)
+        _none, h_r, h_i = e.rows_lerp_adjoint((None, h_r, h_i), _lerp_adjoint_table(plan, n_var), plan.rowt, n_var)
+    mark("k_phase_grad_mask")
+    have_ph = h_r is not None or h_i is not None
+    g_rows = e.mel_warp_backward(H, mag=(g_m, plan.w_mag, rows[0], tabs) if g_m is not None else None,
+                                 phase=(h_r, h_i, plan.w_ph, rows[1], rows[2], live) if have_ph else None)
+    mark("k_mel_warp_bwd")
+    if g_rows[0] is not None and mask_nonfinite:
+        # An output frame whose log-mel row the forward wrote as NaN (an envelope row it reads has a zero bin: digital
+        # silence) has no gradient: zero -- not the kernel's NaN x 0, which the interpolation's adjoint would carry
+        # into the finite neighbouring row.  (k_true_envelope_bwd gives such an envelope row a zero gradient too.)
+        g_rows[0].masked_fill_((~_torch().isfinite(outs[0]).all(dim=1))[:, None], 0.0)
+    if g_rows[0] is not None and tabs is not None:
+        g_rows = (e.rows_lerp_adjoint((g_rows[0], None, None), _lerp_adjoint_table(plan, n_var), plan.rowt, n_var)[0],) \
+            + tuple(g_rows[1:])
+        mark("k_rows_lerp_adjoint")
+    return g_rows
+
+
 class CompressedAnalysisPlan:
     """
     Lossless analysis plan + host tables for the mel warp of a batch (one sample rate).  run() = k_analysis ->
@@ -1739,6 +1771,11 @@ class CompressedAnalysisPlan:
         mark("k_mel_warp_mfma")
         return out
 
+    def check_differentiable(self):
+        """What run_backward cannot take, said before any launch."""
+        if self._warp_name == "mpx_mel_warp_fbank":
+            raise NotImplementedError("the filter-bank magnitudes (b_mag_fbank_mel) have no backward pass")
+
     def run_backward(self, outs, grads, mark=None):
         """The gradient of a loss with respect to the batch's samples, float32 [total_smpls] (utterance u at the offset of
         its samples in self.lossless.sig), given outs = run()'s three matrices and grads = (dL/d m_mag_mel_log,
@@ -1747,47 +1784,25 @@ class CompressedAnalysisPlan:
         The lossless rows are RECOMPUTED (the fused forward never wrote them, and nothing of size F x H is kept between the
         passes): self.lossless.run with the forward's precision and rows_in_use=None -- every row is written, also the phase
         rows the constant-rate forward leaves out: the lossless backward multiplies real / imag into its result even where
-        the gradient is zero.  Then k_phase_grad_mask (the forward's voicing mask and clip, read from outs), at the
-        constant rate k_rows_lerp_adjoint at width phase_dim, k_mel_warp_bwd (the three jobs in one launch), at the
-        constant rate k_rows_lerp_adjoint on the magnitude gradients, and LosslessAnalysisPlan.run_backward."""
-        if self._warp_name == "mpx_mel_warp_fbank":
-            raise NotImplementedError("the filter-bank magnitudes (b_mag_fbank_mel) have no backward pass")
+        the gradient is zero.  Then _warp_backward (at the constant rate through the row tables) and
+        LosslessAnalysisPlan.run_backward."""
+        self.check_differentiable()
         torch = _torch()
-        e, pl, N = self.engine, self.lossless, int(self.fft_len)
-        H = N // 2 + 1
+        e, pl = self.engine, self.lossless
         Fo, n_var, total = self.total_out_frames, int(pl.total_frames), int(pl.total_smpls)
         mark = mark or (lambda name: None)
         mark("start")
-        shapes = ((Fo, self.mag_dim), (Fo, self.phase_dim), (Fo, self.phase_dim))
-        for g, shp in zip(grads, shapes):
-            if g is not None and (g.dtype != torch.float32 or tuple(g.shape) != shp or not g.is_contiguous()):
-                raise ValueError("run_backward: gradients must be contiguous float32 of the outputs' shapes")
-        g_m, g_r, g_i = grads
+        _check_warp_grads(self, grads)
         if Fo == 0 or n_var == 0 or total == 0 or all(g is None for g in grads):
             return torch.zeros((total,), dtype=torch.float32, device=e.device)
         precise = os.environ.get("MAGPHASE_COMP_ANALYSIS", "f64") != "f32"
         rows = pl.run(precise=precise, rows_in_use=None)
         mark("rows")
-        h_r, h_i = e.phase_grad_mask(outs[1], outs[2], self.voi, g_r, g_i)
-        tabs = live = None
-        if self.b_const_rate:
-            if getattr(self, "_adj", None) is None:
-                r0, r1, rt = self._rows_host
-                self._adj = e.to_device(hm.lerp_adjoint_table(r0, r1, rt, n_var).reshape(-1), np.int32)
-            tabs = (self.row0, self.row1, self.rowt)
-            # the masked phase gradients onto the variable-rate rows the forward interpolated from (width phase_dim)
-            _none, h_r, h_i = e.rows_lerp_adjoint((None, h_r, h_i), self._adj, self.rowt, n_var)
-            live = self.rows_in_use   # (None under MAGPHASE_WARP_PHASE_ROWS=0: no tile is skipped)
+        if self.b_const_rate:   # (rows_in_use is None under MAGPHASE_WARP_PHASE_ROWS=0: no tile is skipped)
+            tabs, live = (self.row0, self.row1, self.rowt), self.rows_in_use
         else:
-            live = self.voi
-        mark("k_phase_grad_mask")
-        have_ph = h_r is not None or h_i is not None
-        g_rows = e.mel_warp_backward(H, mag=(g_m, self.w_mag, rows[0], tabs) if g_m is not None else None,
-                                     phase=(h_r, h_i, self.w_ph, rows[1], rows[2], live) if have_ph else None)
-        mark("k_mel_warp_bwd")
-        if self.b_const_rate and g_rows[0] is not None:
-            g_rows = (e.rows_lerp_adjoint((g_rows[0], None, None), self._adj, self.rowt, n_var)[0],) + tuple(g_rows[1:])
-            mark("k_rows_lerp_adjoint")
+            tabs, live = None, self.voi
+        g_rows = _warp_backward(self, outs, grads, rows, tabs, live, n_var, mark=mark)
         gsig = pl.run_backward(rows[0], rows[1], rows[2], g_rows)
         mark("k_analysis_lossless_bwd")
         return gsig
@@ -1903,6 +1918,9 @@ class Type2AnalysisPlan:
                                     pl.total_smpls, (pos,) + self._host_lr2)
         return self._tab2
 
+    def check_differentiable(self):
+        """What run_backward cannot take, said before any launch: nothing."""
+
     def run_backward(self, grads, iters, want_decisions=False):
         """The gradient of a loss with respect to the batch's samples, float32 [total_smpls], given grads = (dL/d env,
         dL/d real, dL/d imag) of run()'s three matrices -- float32 [total_frames x H] with unit column stride, or None for
@@ -1992,8 +2010,9 @@ class Type2CompressedAnalysisPlan:
         outs, gain, iters = self._run(want_iters)
         return (outs, gain, iters) if want_iters else (outs, gain)
 
-    def check_grad_dims(self):
-        """k_mel_warp_bwd produces the gradient of at most 64 coefficient columns per job."""
+    def check_differentiable(self):
+        """What run_backward cannot take, said before any launch: k_mel_warp_bwd produces the gradient of at most 64
+        coefficient columns per job."""
         for name, d in (("mag_dim", self.mag_dim), ("phase_dim", self.phase_dim)):
             if int(d) > 64:
                 raise NotImplementedError("%s = %d: the backward pass of the type-2 analysis takes at most 64 coefficient "
@@ -2002,39 +2021,19 @@ class Type2CompressedAnalysisPlan:
     def run_backward(self, outs, grads, iters):
         """The gradient of a loss with respect to the batch's samples, float32 [total_smpls], given outs = run()'s three
         matrices, grads = (dL/d m_mag_mel_log, dL/d m_real_mel, dL/d m_imag_mel) as contiguous float32 matrices of their
-        shapes or None, and iters = run(want_iters=True)'s pass counts.  The tail of CompressedAnalysisPlan.run_backward
-        on the type-2 row tables (which the forward reads at either rate): the type-2 rows are recomputed with the
-        forward's pass counts forced, k_phase_grad_mask, k_rows_lerp_adjoint at width phase_dim, k_mel_warp_bwd with the
-        magnitude job against the envelope rows, k_rows_lerp_adjoint on the magnitude gradients; then
+        shapes or None, and iters = run(want_iters=True)'s pass counts.  The type-2 rows are recomputed
+        with the forward's pass counts forced; _warp_backward, as in CompressedAnalysisPlan.run_backward, on the type-2 row
+        tables (which the forward reads at either rate), the magnitude job against the envelope rows; then
         Type2AnalysisPlan.run_backward.  DESIGN.md section 3.3m."""
-        self.check_grad_dims()
+        self.check_differentiable()
         torch = _torch()
         e, t2 = self.engine, self.t2
-        H = self.fft_len // 2 + 1
         Fo, F, total = self.total_out_frames, int(t2.total_frames), int(t2.lossless.total_smpls)
-        shapes = ((Fo, self.mag_dim), (Fo, self.phase_dim), (Fo, self.phase_dim))
-        for g, shp in zip(grads, shapes):
-            if g is not None and (g.dtype != torch.float32 or tuple(g.shape) != shp or not g.is_contiguous()):
-                raise ValueError("run_backward: gradients must be contiguous float32 of the outputs' shapes")
-        g_m, g_r, g_i = grads
+        _check_warp_grads(self, grads)
         if Fo == 0 or F == 0 or total == 0 or all(g is None for g in grads):
             return torch.zeros((total,), dtype=torch.float32, device=e.device)
-        env, real, imag, _gain, _it = t2.run(forced_iters=iters)
-        h_r, h_i = e.phase_grad_mask(outs[1], outs[2], self.voi, g_r, g_i)
-        if getattr(self, "_adj", None) is None:
-            r0, r1, rt = self._rows_host
-            self._adj = e.to_device(hm.lerp_adjoint_table(r0, r1, rt, F).reshape(-1), np.int32)
-        _none, h_r, h_i = e.rows_lerp_adjoint((None, h_r, h_i), self._adj, self.rowt, F)
-        have_ph = h_r is not None or h_i is not None
-        tabs = (self.row0, self.row1, self.rowt)
-        g_rows = e.mel_warp_backward(H, mag=(g_m, self.w_mag, env, tabs) if g_m is not None else None,
-                                     phase=(h_r, h_i, self.w_ph, real, imag, None) if have_ph else None)
-        if g_rows[0] is not None:
-            # An output frame whose log-mel row the forward wrote as NaN (an envelope row it reads has a zero bin: digital
-            # silence) has no gradient: zero -- not the kernel's NaN x 0, which the interpolation's adjoint would carry
-            # into the finite neighbouring row.  (k_true_envelope_bwd gives such an envelope row a zero gradient too.)
-            g_rows[0].masked_fill_((~torch.isfinite(outs[0]).all(dim=1))[:, None], 0.0)
-            g_rows = (e.rows_lerp_adjoint((g_rows[0], None, None), self._adj, self.rowt, F)[0],) + tuple(g_rows[1:])
+        rows = t2.run(forced_iters=iters)[:3]   # (env, real, imag)
+        g_rows = _warp_backward(self, outs, grads, rows, (self.row0, self.row1, self.rowt), None, F, mask_nonfinite=True)
         return t2.run_backward(g_rows, iters)
 
     def _run(self, want_iters):

@@ -134,8 +134,10 @@ def test_the_compressed_plan_still_refuses_these_phase_types():
         plan = CompressedSynthesisPlan.__new__(CompressedSynthesisPlan)
         plan.per_phase_type, plan.apply_post_filter = ppt, False
         with pytest.raises(NotImplementedError, match="per_phase_type"):
-            plan._check_differentiable()
-    assert MagnitudeSynthesisPlan._check_differentiable is CompressedSynthesisPlan._check_differentiable
+            plan.check_differentiable()
+        plan = MagnitudeSynthesisPlan.__new__(MagnitudeSynthesisPlan)      # its own backward pass: not refused
+        plan.per_phase_type, plan.apply_post_filter, plan.mag_dim = ppt, False, 64
+        plan.check_differentiable()
     plan = MagnitudeSynthesisPlan.__new__(MagnitudeSynthesisPlan)
     plan.apply_post_filter, plan.mag_dim = True, 60
     with pytest.raises(NotImplementedError, match="b_post_filter"):

@@ -75,7 +75,7 @@ def test_more_than_64_columns_are_refused_by_name():
         plan = Type2CompressedAnalysisPlan.__new__(Type2CompressedAnalysisPlan)
         plan.mag_dim, plan.phase_dim = kw["mag_dim"], kw["phase_dim"]
         with pytest.raises(NotImplementedError, match=name):
-            plan.check_grad_dims()
+            plan.check_differentiable()
 
 
 def test_chain_model_against_the_golden_file(golden_dir):

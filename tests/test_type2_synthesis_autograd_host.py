@@ -194,9 +194,9 @@ def test_cpu_tensors_that_require_grad_take_the_host_path():
     """The predicate of the device path: CPU tensors, a host return and no_grad are not differentiated."""
     import torch
 
-    from magphase_amd import magphase as mp
+    from magphase_amd import hostmath as hm
 
     x = torch.zeros(4, 60, requires_grad=True)
     utts = [(x, torch.zeros(4, 45), torch.zeros(4, 45), np.zeros(4))]
-    assert not mp._compressed_synthesis_wants_grad(utts, True)
-    assert not mp._compressed_synthesis_wants_grad(utts, False)
+    assert not hm.wants_grad(True, [m for u in utts for m in u[:3]])
+    assert not hm.wants_grad(False, [m for u in utts for m in u[:3]])
