@@ -878,6 +878,45 @@ int mpx_mlpg_apply(void* stream, const void* x, int32_t x_f64, int64_t ld_x, con
                    int32_t n_win, const double* windows, double* y, int64_t ld_y);
 
 /*
+ * Variance gradients of MLPG and the trajectory likelihood ("variances").  Operands are typed and
+ * pitched as in mpx_mlpg_solve (float32 / float64, any row pitch, ld_var == 0: the global row); all arithmetic and every
+ * output is float64; no atomics, deterministic; an element's or a system's result does not depend on the batch it is in;
+ * nothing outside an utterance's rows is read.  Every entry returns 0 without a launch when total_frames or n_utts is 0.
+ * mpx_mlpg_var_backward: g[t, k D + d] = -p^2 (W_k z)[t, d] (mean[t, k D + d] - (W_k c)[t, d]), p = 1 / var[t, k D + d]: the
+ * gradient of a loss on the trajectory with respect to the variances, for z = A^-1 dL/dc (mpx_mlpg_solve, rhs_direct) and
+ * the trajectory c, both float64 [total_frames x D].  g: float64 [total_frames x K D] at ld_g.  With ld_var == 0 it also
+ * writes gsum [K D], the column sums of g over all rows (the gradient of the global row), through work
+ * [mpx_mlpg_colsum_work_doubles(total_frames, K D)]; gsum and work may be null otherwise.
+ * mpx_mlpg_column_sums: sums[col] = sum over the rows of x [total_frames x width] (float64 at ld_x): per column one
+ * partial sum per tile of 128 rows, rows in ascending order, then the tiles in ascending order -- the same bits every run.
+ * mpx_mlpg_trajectory_nll: nll[u D + d] = -log N(x[., d]; c[., d], A^-1) of utterance u, one lane per system, for the
+ * trajectory c of a preceding mpx_mlpg_solve launch and the static target x [total_frames x D]:
+ * 1/2 sum_k sum_t p_k[t] (W_k (x - c))[t]^2 - 1/2 sum_i log d_i + F/2 log 2 pi, d_i the pivots of the LDL^T factor; 0 for
+ * an utterance without frames.  nll: float64 [n_utts x D].
+ * mpx_mlpg_trajectory_nll_backward: the gradients of sum go[u D + d] nll[u D + d], one lane per system:
+ * g_mean[t, k D + d] = -go p (W_k (x - c))[t] and g_var[t, k D + d] = -go p^2 ((W_k e)^2 / 2 - (W_k e)(mean - W_k c) - s_k / 2)
+ * with s_k[t] = (W_k A^-1 W_k^T)[t, t] from the band of A^-1, e = x - c; both float64 [total_frames x K D]; either may be
+ * null (not computed).  work: float64 [mpx_mlpg_nll_work_doubles(total_frames, D)] (the factor as three planes), needed
+ * with g_var.  With ld_var == 0 the gradient of the global row is mpx_mlpg_column_sums of g_var.
+ */
+int64_t mpx_mlpg_colsum_work_doubles(int64_t total_frames, int64_t width);
+int mpx_mlpg_column_sums(void* stream, const double* x, int64_t ld_x, int64_t total_frames, int64_t width, double* sums,
+                         double* work);
+int mpx_mlpg_var_backward(void* stream, const double* z, int64_t ld_z, const double* c, int64_t ld_c, const void* mean,
+                          int32_t mean_f64, int64_t ld_mean, const void* var, int32_t var_f64, int64_t ld_var,
+                          const int32_t* utt_frame_off, int32_t n_utts, int64_t total_frames, int32_t D, int32_t n_win,
+                          const double* windows, double* g, int64_t ld_g, double* gsum, double* work);
+int mpx_mlpg_trajectory_nll(void* stream, const double* c, int64_t ld_c, const void* x, int32_t x_f64, int64_t ld_x,
+                            const void* var, int32_t var_f64, int64_t ld_var, const int32_t* utt_frame_off, int32_t n_utts,
+                            int64_t total_frames, int32_t D, int32_t n_win, const double* windows, double* nll);
+int64_t mpx_mlpg_nll_work_doubles(int64_t total_frames, int32_t D);
+int mpx_mlpg_trajectory_nll_backward(void* stream, const void* mean, int32_t mean_f64, int64_t ld_mean, const void* var,
+                                     int32_t var_f64, int64_t ld_var, const double* c, int64_t ld_c, const void* x,
+                                     int32_t x_f64, int64_t ld_x, const double* go, const int32_t* utt_frame_off,
+                                     int32_t n_utts, int64_t total_frames, int32_t D, int32_t n_win, const double* windows,
+                                     double* g_mean, int64_t ld_gm, double* g_var, int64_t ld_gv, double* work);
+
+/*
  * MagPhase post-filter (magphase.py:2300-2378, Q20) on [n_frames x dim] log-mel magnitudes.  half_len: int32
  * [nx_last - nx_first + 1] half lengths of the centred moving average of bins nx_first..nx_last (host table,
  * magphase.py:2342-2344); tilt: float32[dim] enhancement factors (np.linspace(boost_at_zero, boost_at_nyq, dim)).

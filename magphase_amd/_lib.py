@@ -128,6 +128,14 @@ PROTOTYPES = {
     "mpx_mlpg_work_doubles": (i64, [i64, i32]),
     "mpx_mlpg_solve": (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, i64, i32, i32, vp, i32, vp, i64, vp]),
     "mpx_mlpg_apply": (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i64]),
+    "mpx_mlpg_colsum_work_doubles": (i64, [i64, i64]),
+    "mpx_mlpg_column_sums": (i32, [vp, vp, i64, i64, i64, vp, vp]),
+    "mpx_mlpg_var_backward": (i32, [vp, vp, i64, vp, i64, vp, i32, i64, vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, i64,
+                                    vp, vp]),
+    "mpx_mlpg_trajectory_nll": (i32, [vp, vp, i64, vp, i32, i64, vp, i32, i64, vp, i32, i64, i32, i32, vp, vp]),
+    "mpx_mlpg_nll_work_doubles": (i64, [i64, i32]),
+    "mpx_mlpg_trajectory_nll_backward": (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i64, vp, i32, i64, vp, vp, i32, i64,
+                                               i32, i32, vp, vp, i64, vp, i64, vp]),
 }
 SYMBOLS = tuple(PROTOTYPES)
 # mpx_roundtrip_lossless_ola_flags: how the feature rows are stored (MPX_RT_STORE_ROWS, by line, MPX_RT_STORE_NT), by the

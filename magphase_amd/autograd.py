@@ -17,7 +17,10 @@ true_envelope                 Engine.true_envelope                              
                                 -> Engine.true_envelope_backward                    stop test (pass counts held)
 analyze_type2                 Type2AnalysisPlan.run -> .run_backward              v_sig | v_pm_sec, v_voi, fs,     3.3m
 analyze_compressed_type2      Type2CompressedAnalysisPlan.run -> .run_backward      the per-frame gain             3.3m
-mlpg                          Engine.mlpg_streams -> .mlpg_streams_backward       the means | variances, windows   3.3n
+mlpg                          Engine.mlpg_streams -> .mlpg_streams_backward       the means, with var_grad the     3.3n
+                                (var_grad: .mlpg_streams_var_backward)              variances | windows
+mlpg_trajectory_nll           Engine.mlpg_solve, .mlpg_trajectory_nll             the means, device variances      3.3n
+                                -> .mlpg_trajectory_nll_backward                    | targets, windows
 synthesize_from_mag           MagnitudeSynthesisPlan.run, Engine.output_hpf       m_mag_mel_log | v_lf0, fs,       3.3o
                                 -> .adjoint_hpf, .run_backward                      noise and its gains
 min_phase                     Engine.min_phase_rows -> .min_phase_backward        the magnitudes (not where m<=0)  3.3o
@@ -315,36 +318,108 @@ class _MLPG(torch.autograd.Function):
     [(first column, D), ...].  Engine.mlpg_streams is the forward launch (one mpx_mlpg_solve per stream).  Output: the ONE
     float64 [sum F_i x sum D] buffer of trajectories.  The backward pass keeps no factor: per stream it solves A z = g
     again from the variances (mpx_mlpg_solve with the right-hand side given) and applies P_k W_k (mpx_mlpg_apply).  Kept:
-    the variances and the frame offsets -- MLPG is linear in the means, so the means themselves are not."""
+    the variances and the frame offsets -- MLPG is linear in the means, so the means themselves are not.
+    The variance path (n_means < len(mats): mats = the means, then the caller's variance tensors -- ONE [width] global row
+    or one [F_i x width] matrix per utterance, of which var is the packed, detached device form): the packed means and the
+    output are kept as well, and Engine.mlpg_streams_var_backward adds mpx_mlpg_var_backward to the two launches above."""
 
     @staticmethod
-    def forward(ctx, engine, var, streams, windows, width, *means):
+    def forward(ctx, engine, var, streams, windows, width, n_means, *mats):
         import numpy as np
 
+        means, var_in = mats[:n_means], mats[n_means:]
         buf, offs = engine.mlpg_pack(list(means), width)
         offs_dev = engine.to_device(offs.astype(np.int32), np.int32)
         out = engine.mlpg_streams(buf, var, offs_dev, streams, windows)
-        ctx.engine, ctx.streams, ctx.windows, ctx.width = engine, streams, windows, width
+        ctx.engine, ctx.streams, ctx.windows, ctx.width, ctx.n_means = engine, streams, windows, width, n_means
         ctx.offs = [int(o) for o in offs]
-        ctx.like = _like(means)
-        ctx.save_for_backward(var, offs_dev)
+        ctx.like = _like(mats)
+        if var_in:
+            ctx.save_for_backward(var, offs_dev, buf, out)
+        else:
+            ctx.save_for_backward(var, offs_dev)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
-        var, offs_dev = ctx.saved_tensors
-        n_head = 5   # engine, var, streams, windows, width
+        n_head = 6   # engine, var, streams, windows, width, n_means
+        n = ctx.n_means
+        need_in = ctx.needs_input_grad[n_head:]
         grad_out = _coerce(grad_out, dtype=torch.float64)
+        if len(ctx.like) == n:
+            var, offs_dev = ctx.saved_tensors
+            with torch.cuda.device(var.device):
+                g = ctx.engine.mlpg_streams_backward(grad_out, var, offs_dev, ctx.streams, ctx.windows, ctx.width)
+            return (None,) * n_head + _scatter(g, ctx.offs, ctx.like, need_in)
+        var, offs_dev, buf, out = ctx.saved_tensors
         with torch.cuda.device(var.device):
-            g = ctx.engine.mlpg_streams_backward(grad_out, var, offs_dev, ctx.streams, ctx.windows, ctx.width)
-        return (None,) * n_head + _scatter(g, ctx.offs, ctx.like, ctx.needs_input_grad[n_head:])
+            g, gv = ctx.engine.mlpg_streams_var_backward(grad_out, buf, out, var, offs_dev, ctx.streams, ctx.windows,
+                                                         ctx.width, need_mean=any(need_in[:n]))
+        g_means = _scatter(g, ctx.offs, ctx.like[:n], need_in[:n]) if g is not None else (None,) * n
+        return (None,) * n_head + g_means + _var_grads(gv, ctx.offs, ctx.like[n:], need_in[n:])
 
 
-def mlpg(engine, means, var, streams, windows, width):
+def _var_grads(gv, offs, like, need_in):
+    """The variances' gradient cut back to the caller's tensors: a [width] vector for the ONE global row, else the rows of
+    a [sum F_i x width] matrix per utterance."""
+    if gv.dim() == 1:
+        return (gv.to(like[0][0]).reshape(like[0][1]) if like[0] is not None and need_in[0] else None,)
+    return _scatter(gv, offs, like, need_in)
+
+
+def mlpg(engine, means, var, streams, windows, width, var_inputs=()):
     """Engine.mlpg_streams on the packed means, differentiable with respect to the mean matrices that are tensors
-    requiring grad (the variances and the windows get no gradient).  -> the float64 [sum F_i x sum D] buffer with grad_fn."""
-    return _MLPG.apply(engine, var, streams, windows, int(width), *means)
+    requiring grad and to var_inputs (the caller's variance tensors behind the device form var: the one global row, or
+    one matrix per utterance; empty: the variances get no gradient).  The windows get none.  -> the float64
+    [sum F_i x sum D] buffer with grad_fn."""
+    return _MLPG.apply(engine, var, streams, windows, int(width), len(means), *means, *var_inputs)
+
+
+class _MLPGTrajectoryNLL(torch.autograd.Function):
+    """forward(engine, var, x, windows, D, n_means, *mats): mats = the [F_i x K D] mean matrices of
+    mp.mlpg_trajectory_nll_batch, then the caller's variance tensors (as in _MLPG; none: no gradient for them); var = the
+    device variances, x = the packed static targets [sum F_i x D] (no gradient).  Forward: mpx_mlpg_solve, then
+    mpx_mlpg_trajectory_nll.  Output: float64 [n_utts x D].  Kept: the packed means, the variances, the trajectory, the
+    targets and the frame offsets; the backward pass is ONE mpx_mlpg_trajectory_nll_backward launch (and the column pass
+    for a global variance row)."""
+
+    @staticmethod
+    def forward(ctx, engine, var, x, windows, D, n_means, *mats):
+        import numpy as np
+
+        means = mats[:n_means]
+        K = int(windows.shape[0]) + 1
+        buf, offs = engine.mlpg_pack(list(means), K * D)
+        offs_dev = engine.to_device(offs.astype(np.int32), np.int32)
+        c = engine.mlpg_solve(buf, var, offs_dev, D, windows)
+        nll = engine.mlpg_trajectory_nll(c, x, var, offs_dev, D, windows)
+        ctx.engine, ctx.windows, ctx.D, ctx.n_means = engine, windows, D, n_means
+        ctx.offs = [int(o) for o in offs]
+        ctx.like = _like(mats)
+        ctx.save_for_backward(var, offs_dev, buf, c, x)
+        return nll
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, go):
+        var, offs_dev, buf, c, x = ctx.saved_tensors
+        n_head = 6   # engine, var, x, windows, D, n_means
+        n = ctx.n_means
+        need_in = ctx.needs_input_grad[n_head:]
+        go = _coerce(go, dtype=torch.float64)
+        with torch.cuda.device(var.device):
+            g, gv = ctx.engine.mlpg_trajectory_nll_backward(buf, var, c, x, go, offs_dev, ctx.D, ctx.windows,
+                                                            need_mean=any(need_in[:n]), need_var=any(need_in[n:]))
+        g_means = _scatter(g, ctx.offs, ctx.like[:n], need_in[:n]) if g is not None else (None,) * n
+        g_vars = _var_grads(gv, ctx.offs, ctx.like[n:], need_in[n:]) if gv is not None else (None,) * (len(ctx.like) - n)
+        return (None,) * n_head + g_means + g_vars
+
+
+def mlpg_trajectory_nll(engine, means, var, x, windows, D, var_inputs=()):
+    """The trajectory likelihood of the packed targets x under MLPG of the means, differentiable with respect to the mean
+    matrices that are tensors requiring grad and to var_inputs (as in mlpg()).  -> float64 [n_utts x D] with grad_fn."""
+    return _MLPGTrajectoryNLL.apply(engine, var, x, windows, int(D), len(means), *means, *var_inputs)
 
 
 class _MinPhase(torch.autograd.Function):

@@ -1615,6 +1615,124 @@ class Engine:
             o += d
         return g
 
+    def _mlpg_f64(self, t, width, what, total):
+        o64, ld = self._mlpg_operand(t, width, what, total)
+        if not o64:
+            raise TypeError("%s must be float64" % what)
+        return ld
+
+    def mlpg_column_sums(self, x, sums=None):
+        """ONE mpx_mlpg_column_sums call (k_mlpg_colsum_tiles, k_mlpg_colsum_final): the column sums of a float64
+        [total x width] device matrix in a fixed order (tiles of 128 rows, then the tiles) -> float64 [width]."""
+        torch = _torch()
+        total, width = int(x.shape[0]), int(x.shape[1])
+        ld = self._mlpg_f64(x, width, "mlpg: x", total)
+        if sums is None:
+            sums = torch.zeros(width, dtype=torch.float64, device=self.device)
+        if sums.dtype != torch.float64 or int(sums.numel()) != width or not sums.is_contiguous():
+            raise ValueError("mlpg: sums must be %d contiguous float64" % width)
+        work = torch.empty(int(self.lib.mpx_mlpg_colsum_work_doubles(total, width)), dtype=torch.float64,
+                           device=self.device)
+        self.launch("mpx_mlpg_column_sums", x, ld, total, width, sums, work)
+        return sums
+
+    def mlpg_var_backward(self, z, c, mean, var, offs_dev, D, windows, out=None, gsum=None):
+        """ONE mpx_mlpg_var_backward call (k_mlpg_var_bwd; with a global variance also the column pass): the gradient of a
+        loss on the trajectory with respect to the variances, -p^2 (W_k z)(mu_k - W_k c), for z = A^-1 dL/dc and the
+        trajectory c (float64 [total x D]), mean and var as mlpg_solve takes them.  -> (float64 [total x K D], float64
+        [K D] column sums with a global variance, else None)."""
+        torch = _torch()
+        total, K = int(mean.shape[0]), int(windows.shape[0]) + 1
+        ld_z = self._mlpg_f64(z, D, "mlpg: z", total)
+        ld_c = self._mlpg_f64(c, D, "mlpg: c", total)
+        m64, ld_m = self._mlpg_operand(mean, K * D, "mlpg: mean", total)
+        v64, ld_v = self._mlpg_var(var, K * D, total)
+        if out is None:
+            out = torch.empty((total, K * D), dtype=torch.float64, device=self.device)
+        ld_o = self._mlpg_f64(out, K * D, "mlpg: g", total)
+        work = None
+        if ld_v == 0:
+            if gsum is None:
+                gsum = torch.zeros(K * D, dtype=torch.float64, device=self.device)
+            if gsum.dtype != torch.float64 or int(gsum.numel()) != K * D or not gsum.is_contiguous():
+                raise ValueError("mlpg: gsum must be %d contiguous float64" % (K * D))
+            work = torch.empty(int(self.lib.mpx_mlpg_colsum_work_doubles(total, K * D)), dtype=torch.float64,
+                               device=self.device)
+        else:
+            gsum = None
+        wins = (ctypes.c_double * windows.size)(*[float(v) for v in windows.reshape(-1)])
+        self.launch("mpx_mlpg_var_backward", z, ld_z, c, ld_c, mean, m64, ld_m, var, v64, ld_v, offs_dev,
+                    int(offs_dev.numel()) - 1, total, int(D), K - 1, wins, out, ld_o, gsum, work)
+        return out, gsum
+
+    def mlpg_trajectory_nll(self, c, x, var, offs_dev, D, windows):
+        """ONE mpx_mlpg_trajectory_nll launch (k_mlpg_nll): -log N(x; c, A^-1) per system for the trajectory c (float64
+        [total x D], of mlpg_solve on the same variances) and the static target x (float32 / float64 [total x D]).
+        -> float64 [n_utts x D]; 0 for an utterance without frames."""
+        torch = _torch()
+        total, K, n_utts = int(c.shape[0]), int(windows.shape[0]) + 1, int(offs_dev.numel()) - 1
+        ld_c = self._mlpg_f64(c, D, "mlpg: c", total)
+        x64, ld_x = self._mlpg_operand(x, D, "mlpg: x", total)
+        v64, ld_v = self._mlpg_var(var, K * D, total)
+        nll = torch.zeros((n_utts, D), dtype=torch.float64, device=self.device)
+        wins = (ctypes.c_double * windows.size)(*[float(v) for v in windows.reshape(-1)])
+        self.launch("mpx_mlpg_trajectory_nll", c, ld_c, x, x64, ld_x, var, v64, ld_v, offs_dev, n_utts, total, int(D),
+                    K - 1, wins, nll)
+        return nll
+
+    def mlpg_trajectory_nll_backward(self, mean, var, c, x, go, offs_dev, D, windows, need_mean=True, need_var=True):
+        """ONE mpx_mlpg_trajectory_nll_backward launch (k_mlpg_nll_bwd; with a global variance also
+        mpx_mlpg_column_sums): the gradients of sum go * nll (go: float64 [n_utts x D]) with respect to the means and the
+        variances.  -> (g_mean float64 [total x K D] or None, g_var: float64 [total x K D] for per-frame variances, [K D]
+        for a global row, or None)."""
+        torch = _torch()
+        total, K, n_utts = int(mean.shape[0]), int(windows.shape[0]) + 1, int(offs_dev.numel()) - 1
+        m64, ld_m = self._mlpg_operand(mean, K * D, "mlpg: mean", total)
+        v64, ld_v = self._mlpg_var(var, K * D, total)
+        ld_c = self._mlpg_f64(c, D, "mlpg: c", total)
+        x64, ld_x = self._mlpg_operand(x, D, "mlpg: x", total)
+        if go.dtype != torch.float64 or tuple(go.shape) != (n_utts, D) or not go.is_contiguous():
+            raise ValueError("mlpg: go must be a contiguous float64 [%d x %d] matrix" % (n_utts, D))
+        if not (need_mean or need_var):
+            return None, None
+        g_mean = torch.empty((total, K * D), dtype=torch.float64, device=self.device) if need_mean else None
+        g_var = torch.empty((total, K * D), dtype=torch.float64, device=self.device) if need_var else None
+        work = torch.empty(int(self.lib.mpx_mlpg_nll_work_doubles(total, D)), dtype=torch.float64,
+                           device=self.device) if need_var else None
+        wins = (ctypes.c_double * windows.size)(*[float(v) for v in windows.reshape(-1)])
+        self.launch("mpx_mlpg_trajectory_nll_backward", mean, m64, ld_m, var, v64, ld_v, c, ld_c, x, x64, ld_x, go, offs_dev,
+                    n_utts, total, int(D), K - 1, wins, g_mean, K * D, g_var, K * D, work)
+        if need_var and ld_v == 0:
+            g_var = self.mlpg_column_sums(g_var)
+        return g_mean, g_var
+
+    def mlpg_streams_var_backward(self, grad_out, buf, out, var, offs_dev, streams, windows, width, need_mean=True):
+        """mlpg_streams_backward with the variances' gradient as well: per stream z = A^-1 g, then P_k W_k z (need_mean)
+        and mpx_mlpg_var_backward on z, the trajectory `out` (mlpg_streams' result) and the packed means `buf`.
+        -> (float64 [total x width] or None, the variances' gradient: float64 [total x width] for per-frame variances,
+        [width] for a global row); columns of no stream are zero."""
+        torch = _torch()
+        total, K = int(grad_out.shape[0]), int(windows.shape[0]) + 1
+        covered = sum(K * d for _, d in streams) == width
+        alloc = torch.empty if covered else torch.zeros
+        g = alloc((total, width), dtype=torch.float64, device=self.device) if need_mean else None
+        glob = var.dim() == 1
+        gv = alloc((total, width), dtype=torch.float64, device=self.device)
+        gsum = torch.zeros(width, dtype=torch.float64, device=self.device) if glob else None
+        dmax = max(d for _, d in streams)
+        z = torch.empty((total, dmax), dtype=torch.float64, device=self.device)
+        work = torch.empty(int(self.lib.mpx_mlpg_work_doubles(total, dmax)), dtype=torch.float64, device=self.device)
+        o = 0
+        for c, d in streams:
+            v = var[c:c + K * d] if glob else var[:, c:c + K * d]
+            self.mlpg_solve(grad_out[:, o:o + d], v, offs_dev, d, windows, rhs=True, out=z[:, :d], work=work)
+            if need_mean:
+                self.mlpg_apply(z[:, :d], v, offs_dev, d, windows, out=g[:, c:c + K * d])
+            self.mlpg_var_backward(z[:, :d], out[:, o:o + d], buf[:, c:c + K * d], v, offs_dev, d, windows,
+                                   out=gv[:, c:c + K * d], gsum=gsum[c:c + K * d] if glob else None)
+            o += d
+        return g, (gsum if glob else gv)
+
     def warp_mag_matrix(self, mag_dim, H, alpha, b_mag_fbank_mel=False):
         """Device-resident [mag_dim x H] matrix of the magnitude compression and the name of the C entry point that goes
         with it: the cepstral mel warp (la.sp_mel_warp, mpx_mel_warp) or the mel filter bank (la.sp_mel_warp_fbank,

@@ -1527,6 +1527,51 @@ def mlpg_check(means, var, windows, what="mlpg_batch", width_of=None, var_cols=N
     return means, var, w, D, per_frame
 
 
+def mlpg_var_inputs(var_given, var, per_frame):
+    """The variance tensors a gradient can reach, for var_grad=True and for the trajectory likelihood: var_given = what
+    the caller passed, var = what mlpg_check made of it.  Per-frame: the checked matrices (still attached to the caller's
+    tensors); global: the caller's own vector.  -> the list, or None when one of them is a host array or a CPU tensor."""
+    import sys
+
+    torch = sys.modules.get("torch")
+    if torch is None:
+        return None
+    cand = list(var) if per_frame else [var_given]
+    if not cand or not all(torch.is_tensor(v) and v.device.type != "cpu" for v in cand):
+        return None
+    return cand
+
+
+def mlpg_var_grad_check(var_grad, return_device, var_given, var, per_frame, what):
+    """var_grad of mlpg_batch / mlpg_streams_batch -> the variance tensors to differentiate ([] without var_grad).
+    var_grad=True needs return_device and variances in device tensors (ValueError)."""
+    if not var_grad:
+        return []
+    if not return_device:
+        raise ValueError("%s: var_grad=True needs return_device=True (a host result carries no gradient)" % what)
+    cand = mlpg_var_inputs(var_given, var, per_frame)
+    if cand is None:
+        raise ValueError("%s: var_grad=True needs the variances in device tensors, not host arrays" % what)
+    return cand
+
+
+def mlpg_targets_check(targets, means, D, what="mlpg_trajectory_nll_batch"):
+    """The static targets of the trajectory likelihood: one [F_i x D] matrix per utterance (as the means: numpy or torch,
+    float32 / float64).  Host targets must be finite."""
+    if isinstance(targets, np.ndarray) or not isinstance(targets, (list, tuple)):
+        raise ValueError("%s: targets must be a list of [frames x D] matrices" % what)
+    if len(targets) != len(means):
+        raise ValueError("%s: one target matrix per utterance expected (%d given for %d utterances)"
+                         % (what, len(targets), len(means)))
+    out = [_mlpg_matrix(x, "%s: targets[%d]" % (what, i), D) for i, x in enumerate(targets)]
+    for i, (x, m) in enumerate(zip(out, means)):
+        if int(x.shape[0]) != int(m.shape[0]):
+            raise ValueError("%s: targets[%d] has %d rows, means[%d] has %d" % (what, i, x.shape[0], i, m.shape[0]))
+        if isinstance(x, np.ndarray) and not np.all(np.isfinite(x)):
+            raise ValueError("%s: targets[%d]: every value must be finite" % (what, i))
+    return out
+
+
 def mlpg_layout(layout, vuv, K, what="mlpg_streams_batch"):
     """The streams of mlpg_streams_batch: layout = ((name, dim), ...), stream s in K dim_s columns [static | delta | acc]
     one after the other, then one voicing column when vuv.  -> (layout as ((str, int), ...), [(first column, dim), ...],

@@ -1530,25 +1530,27 @@ def _mlpg_device_var(engine, var, per_frame, width):
         (var if not isinstance(var, np.ndarray) else engine.to_device(var, var.dtype))
 
 
-def _mlpg_run(engine, means, var, per_frame, w, streams, width, return_device):
+def _mlpg_run(engine, means, var, per_frame, w, streams, width, return_device, var_inputs=()):
     """The launches of mlpg_batch / mlpg_streams_batch -> (float64 device buffer [sum F_i x sum D] (None when the batch has
-    no frames), packed means or None, row offsets)."""
+    no frames), packed means or None, row offsets).  var_inputs: the variance tensors of var_grad=True."""
     offs = np.concatenate(([0], np.cumsum([int(m.shape[0]) for m in means]))).astype(np.int64)
     if int(offs[-1]) == 0:
         return None, None, offs
     var_dev = _mlpg_device_var(engine, var, per_frame, width)
-    if hm.wants_grad(return_device, means):   # (hm.mlpg_check made host arrays of CPU tensors)
+    if not hm.wants_grad(return_device, var_inputs):
+        var_inputs = ()
+    if var_inputs or hm.wants_grad(return_device, means):   # (hm.mlpg_check made host arrays of CPU tensors)
         from . import autograd
 
         buf = None
-        out = autograd.mlpg(engine, means, var_dev, streams, w, width)
+        out = autograd.mlpg(engine, means, var_dev, streams, w, width, var_inputs)
     else:
         buf, _ = engine.mlpg_pack(means, width)
         out = engine.mlpg_streams(buf, var_dev, engine.to_device(offs.astype(np.int32), np.int32), streams, w)
     return out, buf, offs
 
 
-def mlpg_batch(means, var, windows=MLPG_WINDOWS, engine=None, return_device=False):
+def mlpg_batch(means, var, windows=MLPG_WINDOWS, engine=None, return_device=False, var_grad=False):
     """
     Maximum-likelihood parameter generation on the device (k_mlpg_solve): the trajectory c = A^-1 b with
     A = sum_k W_k^T P_k W_k and b = sum_k W_k^T P_k mu_k over the K = 1 + len(windows) streams (static, then one per
@@ -1562,14 +1564,20 @@ def mlpg_batch(means, var, windows=MLPG_WINDOWS, engine=None, return_device=Fals
     Autograd: with return_device, grad mode on and a device mean matrix that requires grad, the results carry a grad_fn
     and backward() gives each mean matrix a gradient in its own dtype and shape (dL/dmu_k = P_k W_k A^-1 dL/dc); the
     forward values are the same bits either way.  Variances and windows get no gradient; no double backward.
+    var_grad=True (with return_device, and the variances in device tensors: ValueError otherwise): a variance tensor that
+    requires grad gets one too, in its own dtype and shape -- dL/dvar_k[t] = -(W_k z)[t] (mu_k[t] - (W_k c)[t]) / var_k[t]^2
+    with z = A^-1 dL/dc (k_mlpg_var_bwd), a global row the sum over all frames of the batch -- whether or not a mean
+    requires grad; the forward values are the same bits.
     Not Merlin's code: the mathematics is restated, parity with Merlin / bandmat is unpinned.
     """
+    var_given = var
     means, var, w, D, per_frame = hm.mlpg_check(means, var, windows, "mlpg_batch")
     if not means:
         return []
+    var_inputs = hm.mlpg_var_grad_check(var_grad, return_device, var_given, var, per_frame, "mlpg_batch")
     engine = engine or get_engine()
     K = w.shape[0] + 1
-    out, _buf, offs = _mlpg_run(engine, means, var, per_frame, w, [(0, D)], K * D, return_device)
+    out, _buf, offs = _mlpg_run(engine, means, var, per_frame, w, [(0, D)], K * D, return_device, var_inputs)
     if out is None:
         if return_device:
             import torch
@@ -1581,6 +1589,57 @@ def mlpg_batch(means, var, windows=MLPG_WINDOWS, engine=None, return_device=Fals
         return rows
     host = out.cpu().numpy()
     return [host[int(a):int(b)] for a, b in zip(offs[:-1], offs[1:])]
+
+
+def mlpg_trajectory_nll_batch(means, var, targets, windows=MLPG_WINDOWS, engine=None, return_device=False):
+    """
+    The trajectory negative log-likelihood -log N(x; c, A^-1) of natural static features under the MLPG system
+    (k_mlpg_solve, then k_mlpg_nll): c = A^-1 b is the MLPG trajectory of the means, A = sum_k W_k^T P_k W_k, and per
+    utterance and dimension
+        NLL = 1/2 sum_k sum_t p_k[t] (W_k (x - c))[t]^2 - 1/2 sum_i log d_i + F/2 log 2 pi,
+    d_i the pivots of the LDL^T factor of A.  means, var: as mlpg_batch takes them; targets: list of
+    [F_i x D] static matrices (host arrays or device tensors, float32 / float64, any row stride).  Returns [n_utts x D]
+    float64 (a numpy array; return_device: a device tensor); an utterance without frames gives zeros.
+    Autograd: with return_device, grad mode on and a device mean or variance tensor that requires grad, the result
+    carries a grad_fn and backward() gives the means and the device variance tensors gradients in their own dtype and
+    shape (k_mlpg_nll_bwd; a global variance row: the sum over all frames of the batch).  The targets get none.
+    One stream per call: pass column slices per stream; voicing-dependent lf0 likelihoods are the caller's.
+    """
+    what = "mlpg_trajectory_nll_batch"
+    var_given = var
+    means, var, w, D, per_frame = hm.mlpg_check(means, var, windows, what)
+    targets = hm.mlpg_targets_check(targets, means, D if means else None, what)
+    if not means:
+        return np.zeros((0, 0))
+    var_inputs = hm.mlpg_var_inputs(var_given, var, per_frame) or []
+    engine = engine or get_engine()
+    import torch
+
+    K = w.shape[0] + 1
+    offs = np.concatenate(([0], np.cumsum([int(m.shape[0]) for m in means]))).astype(np.int64)
+    if int(offs[-1]) == 0:
+        z = torch.zeros((len(means), D), dtype=torch.float64, device=engine.device)
+        return z if return_device else z.cpu().numpy()
+    var_dev = _mlpg_device_var(engine, var, per_frame, K * D)
+    x, _ = engine.mlpg_pack(targets, D)
+    if not hm.wants_grad(return_device, var_inputs):
+        var_inputs = []
+    if var_inputs or hm.wants_grad(return_device, means):
+        from . import autograd
+
+        nll = autograd.mlpg_trajectory_nll(engine, means, var_dev, x, w, D, var_inputs)
+    else:
+        buf, _ = engine.mlpg_pack(means, K * D)
+        offs_dev = engine.to_device(offs.astype(np.int32), np.int32)
+        nll = engine.mlpg_trajectory_nll(engine.mlpg_solve(buf, var_dev, offs_dev, D, w), x, var_dev, offs_dev, D, w)
+    return nll if return_device else nll.detach().cpu().numpy()
+
+
+def mlpg_trajectory_nll(m_mean, var, m_target, windows=MLPG_WINDOWS):
+    """mlpg_trajectory_nll_batch for one utterance: [F x K D] means, [K D] or [F x K D] variances, [F x D] static
+    targets -> [D] float64."""
+    per_frame = getattr(var, "ndim", None) == 2 or (hasattr(var, "dim") and var.dim() == 2)
+    return mlpg_trajectory_nll_batch([m_mean], [var] if per_frame else var, [m_target], windows=windows)[0]
 
 
 def mlpg(m_mean, var, windows=MLPG_WINDOWS):
@@ -1627,7 +1686,7 @@ MLPG_LAYOUT = (("mag", 60), ("real", 10), ("imag", 10), ("lf0", 1))
 
 
 def mlpg_streams_batch(cmps, var, layout=MLPG_LAYOUT, vuv=True, vuv_thres=0.5, windows=MLPG_WINDOWS, engine=None,
-                       return_device=False):
+                       return_device=False, var_grad=False):
     """
     MLPG of an acoustic model's whole output rows.  cmps: list of [F_i x W] matrices (numpy or device tensors, as
     mlpg_batch takes them); stream s of layout = ((name, dim), ...) occupies K dim_s columns [static | delta | acc], the
@@ -1639,7 +1698,7 @@ def mlpg_streams_batch(cmps, var, layout=MLPG_LAYOUT, vuv=True, vuv_thres=0.5, w
     'lf0' as a vector, set to the unvoiced value of la.f0_to_lf0 (-1e10) where the voicing column is <= vuv_thres.
     return_device: device tensors (column slices of one float64 buffer; v_lf0 a float64 device vector), which the synthesis
     reads where they lie.  Autograd as in mlpg_batch (the voicing decision is not differentiated; unvoiced frames send no
-    gradient to lf0).
+    gradient to lf0).  var_grad as in mlpg_batch; the voicing column of the variances gets zeros.
     """
     import torch
 
@@ -1653,13 +1712,15 @@ def mlpg_streams_batch(cmps, var, layout=MLPG_LAYOUT, vuv=True, vuv_thres=0.5, w
             raise ValueError("mlpg_streams_batch: the layout asks for %d columns, the matrices have %d" % (need, width))
         return 0
 
+    var_given = var
     means, var, w, _D, per_frame = hm.mlpg_check(cmps, var, windows, "mlpg_streams_batch", width_of=width_of,
                                                  var_cols=slice(0, need - (1 if vuv else 0)))
     if not means:
         return []
+    var_inputs = hm.mlpg_var_grad_check(var_grad, return_device, var_given, var, per_frame, "mlpg_streams_batch")
     width = int(means[0].shape[1])
     engine = engine or get_engine()
-    out, buf, offs = _mlpg_run(engine, means, var, per_frame, w, streams, width, return_device)
+    out, buf, offs = _mlpg_run(engine, means, var, per_frame, w, streams, width, return_device, var_inputs)
     if out is None:
         z = [np.zeros(0) if n == "lf0" else np.zeros((0, d)) for n, d in layout]
         if return_device:
