@@ -452,6 +452,32 @@ int mpx_griffin_lim_ola(void* stream, int fft_len, const void* tables, const flo
                         int32_t n_slots, const int32_t* pm_rel, float* phase_out, float* strips, float* sig_out,
                         int64_t ld);
 
+/*
+ * The inputs of Griffin-Lim's FIRST synthesis from the target magnitudes and an initial phase (magphase.py:3334-3356:
+ * frames = ifft(M e^{j phi}).real with phi not necessarily Hermitian), as the rows mpx_synthesis_lossless_ola reads
+ * (k_gl_fold, one thread per frame and bin, float64 arithmetic rounded once to float32).
+ * Frames frame0 .. frame0 + n_frames - 1 of mag and of the outputs (row pitch ld, H = fft_len / 2 + 1 columns) are
+ * folded; `phase` points at the phase of frame frame0 (the caller folds a batch in groups of utterances):
+ *   MPX_GL_FOLD_HALF   float32 [n_frames x H] at pitch ld_phase, a Hermitian extension; columns 0 and H - 1 count as 0
+ *                      whatever they hold.  Outputs (M, cos phi (-1)^k, sin phi (-1)^k).
+ *   MPX_GL_FOLD_FULL   float32 [n_frames x fft_len] at pitch ld_phase.  c_k = (e^{j phi_k} + e^{-j phi_{N-k}}) / 2 (the
+ *                      real cos phi_0 and cos phi_{N/2} at the ends); outputs mag' = M |c| and the phasor c (-1)^k / |c|,
+ *                      (0, 0, 0) where |c| = 0.
+ *   MPX_GL_FOLD_WORDS  numpy's raw MT19937 words (uint32, 8-byte aligned, the `raw` buffer of mpx_noise_numpy_mt19937),
+ *                      two per sample, row-major over [n_frames x fft_len]: r = ((w0 >> 5) 2^26 + (w1 >> 6)) / 2^53 (what
+ *                      np.random.rand returns), phi = 2 pi (r - 0.5), then the FULL fold.  ld_phase is not read.
+ * out_phase: null, or rows (pitch ld) that receive float32 phi_k, k < H (HALF: with the zeroed ends).  Every element of
+ * columns 0 .. H - 1 of the output rows is written exactly once, nothing else is written.  n_frames == 0 returns MPX_OK
+ * without a launch; MPX_ERR_ARG (detected on the host, without a device) for another fft_len, an unknown form, a
+ * negative size, ld < H, ld_phase smaller than the phase rows, or a null pointer with frames to fold.
+ */
+#define MPX_GL_FOLD_HALF 0
+#define MPX_GL_FOLD_FULL 1
+#define MPX_GL_FOLD_WORDS 2
+int mpx_griffin_lim_fold(void* stream, int fft_len, int32_t form, const float* mag, const void* phase, int64_t ld_phase,
+                         int64_t frame0, int64_t n_frames, float* out_mag, float* out_real, float* out_imag,
+                         float* out_phase, int64_t ld);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Compressed-feature synthesis (magphase.py:825-997 synthesis_from_compressed, b_fbank_mel=False, per_phase_type='magphase')
  * ------------------------------------------------------------------------------------------------------------------ */

@@ -62,6 +62,7 @@ PROTOTYPES = {
     "mpx_roundtrip_frame_terms": (i32, [i32, vp, vp, i64, vp]),
     "mpx_roundtrip_slot_costs": (i32, [vp, i32]),
     "mpx_griffin_lim_ola": (i32, [vp, i32] + [vp] * 5 + [i64, vp, vp, i32, vp, vp, i32] + [vp] * 4 + [i64]),
+    "mpx_griffin_lim_fold": (i32, [vp, i32, i32, vp, vp, i64, i64, i64, vp, vp, vp, vp, i64]),
     "mpx_mel_unwarp": (i32, [vp, i64, i32, vp, i32] + [vp] * 4 + [i32, vp, vp, vp, i64]),
     "mpx_mel_unwarp_rows": (i32, [vp, i64, i32, vp, i32] + [vp] * 4 + [i32, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp,
                              i32]),

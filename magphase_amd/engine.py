@@ -398,9 +398,10 @@ class Engine:
         q = int(pos) + int(n_words)
         return q if (n_words == 0 or q <= 624) else ((q - 1) % 624) + 1
 
-    def _mt_generate(self, key, pos, n, key_from_compute):
+    def _mt_generate(self, key, pos, n, key_from_compute, with_raw=False):
         """n uniforms continuing numpy's MT19937 stream from (key [624 words on the device], word cursor pos), on the
         generator's own stream: (samples float32 [n], state int32 [625] = key + cursor after them, event).
+        with_raw: the generator's raw words (int32 [2 n], two per sample) as a fourth element instead of dropping them.
         key_from_compute: the key was just uploaded in the compute stream (the generator's stream waits for it; a state
         that comes from the generator's own stream needs no wait -- and must not get one: waiting for the compute stream here
         is waiting for the previous launch)."""
@@ -438,6 +439,8 @@ class Engine:
                     done.record(rng)
                     for t_ in (key,):
                         t_.record_stream(rng)
+        if with_raw:
+            return out, state, done, raw
         return out, state, done
 
     def numpy_global_uniform(self, n, defer=False):
@@ -503,6 +506,43 @@ class Engine:
         if not defer:
             self.mt_sync()
         return out
+
+    # words of at most this many samples are resident at a time when Griffin-Lim's 'random' initial phases are drawn on the
+    # device (magphase.griffin_lim_batch(fold='device')): 2^27 samples = 1 GiB of raw words (+ 0.5 GiB of the float32
+    # samples the generator's entry writes beside them)
+    GL_WORDS_GROUP_SAMPLES = 1 << 27
+
+    def numpy_global_words(self, n, defer=False):
+        """The raw MT19937 words of np.random.rand's next n samples (int32 [2 n] on the device, two per sample: the `raw`
+        buffer of mpx_noise_numpy_mt19937), numpy's global stream continued on the device as numpy_global_uniform does:
+        the global state is left where n host draws would leave it, a pending deferred state is continued (samples that
+        were generated ahead and not handed out are given up first: mt_sync), and with defer=True the advanced state
+        stays on the device until mt_sync().  The words are ready on torch's current stream of the device."""
+        torch = _torch()
+        n = int(n)
+        pend = getattr(self, "_mt_pending", None)
+        if pend is not None and (pend["buf"] is None or pend["used"] != pend["gen"]):
+            self.mt_sync()   # (numpy's state where the handed-out samples end; the words continue from there)
+            pend = None
+        if pend is None:
+            st = np.random.get_state()
+            if st[0] != "MT19937":
+                raise RuntimeError("numpy's global generator is not MT19937")
+            key = self.to_device(np.ascontiguousarray(st[1], dtype=np.uint32).view(np.int32), np.int32)
+            pos, meta, fresh = int(st[2]), (st[0], st[3], st[4]), True
+        else:
+            key, pos, meta, fresh = pend["end_state"], pend["end_pos"], pend["meta"], False
+        gen, state, done, raw = self._mt_generate(key, pos, n, fresh, with_raw=True)
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            if done is not None:
+                cur.wait_event(done)
+                raw.record_stream(cur)
+        self._mt_pending = {"key": key, "pos": pos, "meta": meta, "buf": gen, "gen": n, "lead": 0, "used": n,
+                            "end_state": state, "end_pos": self._mt_next_pos(pos, 2 * n), "done": done}
+        if not defer:
+            self.mt_sync()
+        return raw[:2 * n]
 
     def mt_sync(self):
         """Puts a deferred MT19937 state (numpy_global_uniform(defer=True)) back into numpy's global generator: the state
@@ -1946,6 +1986,38 @@ class Engine:
                     plan.frame_right, int(plan.total_frames), target, it.runs, int(it.n_runs), it.slot_off, it.slot_runs,
                     int(it.n_slots), plan.pm_rel, phase_out, strips, sig_out, int(target.stride(0)))
         return sig_out
+
+    GL_FOLD_FORMS = {"half": 0, "full": 1, "words": 2}   # MPX_GL_FOLD_HALF / _FULL / _WORDS
+
+    def griffin_lim_fold(self, fft_len, form, target, phase, frame0, n_frames, outs, phase_out=None, phase_offset=0):
+        """hostmath.griffin_lim_fold on the device (mpx_griffin_lim_fold, k_gl_fold) for rows frame0 .. frame0 + n_frames - 1
+        of target (device magnitude rows [F x H]) into the same rows of outs = (mag', phasor real, phasor imag) and, if
+        given, of phase_out -- all of target's row pitch.  form 'half' / 'full': phase is a float32 device matrix
+        [n_frames x H] / [n_frames x fft_len] (unit column stride) whose row 0 belongs to frame0; 'words': the int32 words of
+        numpy_global_words, the range's first sample at sample phase_offset."""
+        torch = _torch()
+        ld = int(target.stride(0)) if target.shape[0] > 1 else max(int(target.stride(0)), int(target.shape[1]))
+        for t in tuple(outs) + ((phase_out,) if phase_out is not None else ()):
+            if t.dtype != torch.float32 or t.shape != target.shape or (t.shape[0] > 1 and int(t.stride(0)) != ld):
+                raise ValueError("griffin_lim_fold: the outputs must be float32 rows of the target's shape and pitch")
+        if form == "words":
+            if phase.dtype != torch.int32 or phase.dim() != 1 or not phase.is_contiguous():
+                raise ValueError("griffin_lim_fold: words must be a contiguous int32 vector")
+            if 2 * (int(phase_offset) + int(n_frames) * int(fft_len)) > phase.numel():
+                raise ValueError("griffin_lim_fold: the words do not cover the frames")
+            ptr, ld_phase = phase.data_ptr() + 8 * int(phase_offset), 0
+        else:
+            width = int(fft_len) if form == "full" else int(fft_len) // 2 + 1
+            if (phase.dtype != torch.float32 or phase.dim() != 2 or phase.shape[0] < n_frames or phase.shape[1] != width
+                    or phase.stride(1) != 1):
+                raise ValueError("griffin_lim_fold: phase must be float32 [n_frames x %d] with unit column stride" % width)
+            ptr, ld_phase = phase.data_ptr(), max(int(phase.stride(0)), width) if phase.shape[0] > 1 else width
+        if target.dtype != torch.float32 or target.dim() != 2 or target.shape[1] != int(fft_len) // 2 + 1:
+            raise ValueError("griffin_lim_fold: target must be float32 [F x fft_len / 2 + 1]")
+        if frame0 < 0 or n_frames < 0 or frame0 + n_frames > target.shape[0]:
+            raise ValueError("griffin_lim_fold: frames %d .. %d of %d" % (frame0, frame0 + n_frames, target.shape[0]))
+        self.launch("mpx_griffin_lim_fold", int(fft_len), self.GL_FOLD_FORMS[form], target, ptr, ld_phase, int(frame0),
+                    int(n_frames), outs[0], outs[1], outs[2], phase_out, ld)
 
     def ola_fixup(self, fft_len, plan, strips, pcm_out):
         """Completes the run boundaries; a run table that knows its widest fix range (fix_width: the round-trip plan's

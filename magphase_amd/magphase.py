@@ -576,7 +576,173 @@ def _griffin_lim_check(utts, win_func, phase_init, niters):
     return shifts, inits, N
 
 
-def griffin_lim_batch(utts, win_func=np.hanning, phase_init='random', niters=30, engine=None, return_device=False):
+def _griffin_lim_tensor_args(utts, phase_init):
+    """torch tensors among griffin_lim_batch's m_mag and phase_init, checked without a device: float32 / float16 /
+    bfloat16 / float64 and 2-D (ValueError naming the utterance otherwise); CPU tensors become host arrays (float16 /
+    bfloat16 widened to float32: exact).  Returns (utts, phase_init, the tensors that are not on the CPU)."""
+    import sys
+
+    torch = sys.modules.get("torch")
+    per_utt = isinstance(phase_init, (list, tuple))
+    inits = list(phase_init) if per_utt else [phase_init]
+    if torch is None or not any(torch.is_tensor(x) for x in [u[0] for u in utts] + inits):
+        return utts, phase_init, []
+    on_dev = []
+
+    def host_or_device(x, name):
+        if not torch.is_tensor(x):
+            return x
+        hm.check_feature_tensor(x, name)
+        if x.device.type == "cpu":
+            x = x.detach()
+            return (x.float() if x.element_size() == 2 else x).numpy()
+        on_dev.append((name, x))
+        return x.detach()
+
+    utts = [(host_or_device(u[0], "utts[%d]: m_mag" % i),) + tuple(u[1:]) for i, u in enumerate(utts)]
+    inits = [host_or_device(x, "phase_init[%d]" % i if per_utt else "phase_init") for i, x in enumerate(inits)]
+    return utts, (inits if per_utt else inits[0]), on_dev
+
+
+def _shape_only(x):
+    """A device tensor's stand-in for the host checks (shape only; no memory, no device access)."""
+    return x if isinstance(x, np.ndarray) or not hasattr(x, "data_ptr") else np.broadcast_to(np.float32(0), tuple(x.shape))
+
+
+def _griffin_lim_min_phase(engine, N, tgt, mp_rows, i_re, i_im, want_phase):
+    """la.build_min_phase_from_mag_spec's phasors of rows mp_rows of tgt, bins 0 and N/2 at phase 0, (-1)^k folded in,
+    written to those rows of i_re / i_im; returns their phases when want_phase."""
+    torch = __import__("torch")
+    H = N // 2 + 1
+    ld = int(engine.lib.mpx_spec_ld(H))
+    idx = np.concatenate(mp_rows)
+    rows = torch.from_numpy(idx.astype(np.int32)).to(engine.device)
+    n = int(idx.size)
+    o_m, o_r, o_i = (engine.empty((n, ld)) for _ in range(3))
+    engine.launch("mpx_min_phase", N, engine.tables(N), tgt, rows, rows,
+                  torch.zeros(n, dtype=torch.float32, device=engine.device), n, o_m, o_r, o_i, ld)
+    re, im = o_r[:, :H].clone(), o_i[:, :H].clone()
+    re[:, 0], im[:, 0], re[:, -1], im[:, -1] = 1.0, 0.0, 1.0, 0.0
+    mp_phase = torch.atan2(im, re) if want_phase else None
+    sgn = torch.ones(H, dtype=torch.float32, device=engine.device)
+    sgn[1::2] = -1.0
+    ridx = rows.long()
+    i_re[ridx] = re * sgn
+    i_im[ridx] = im * sgn
+    return mp_phase
+
+
+def _griffin_lim_device_fold(engine, utts, shifts, inits, N, niters, return_device):
+    """griffin_lim_batch with the initial phase and the fold on the device (fold='device'): the target rows are gathered
+    by Engine.pack_rows when one of them is a device tensor, else uploaded as with the host fold; the rest is
+    _griffin_lim_device_rows."""
+    torch = __import__("torch")
+    H = N // 2 + 1
+    sizes = [int(m.shape[0]) for m, _ in utts]
+    F = int(sum(sizes))
+    tgt = engine.empty((max(F, 1), int(engine.lib.mpx_spec_ld(H))))[:F, :H]
+    for init in inits:   # the reference zeroes columns 0 and H - 1 of an ndarray init in place; a device tensor is not written
+        print('Starting Griffin-Lim. It could take a while...')
+        if isinstance(init, np.ndarray):
+            init[:, 0] = 0
+            init[:, -1] = 0
+    if any(torch.is_tensor(m) for m, _ in utts):
+        engine.pack_rows([[m for m, _ in utts]], [tgt])
+    else:
+        tgt.copy_(torch.from_numpy(np.concatenate([np.asarray(m, dtype=np.float32) for m, _ in utts])))
+    return _griffin_lim_device_rows(engine, tgt, sizes, shifts, inits, N, niters, return_device)
+
+
+def _griffin_lim_device_rows(engine, tgt, sizes, shifts, inits, N, niters, return_device, init_rows=None):
+    """Griffin-Lim from device target rows tgt ([sum(sizes) x H] at pitch mpx_spec_ld), initial phase and fold on the
+    device: array inits -- host or device -- are gathered into one float32 [rows x H] matrix and folded as
+    MPX_GL_FOLD_HALF, 'random' utterances are folded from numpy's raw words (Engine.numpy_global_words, in groups of at
+    most Engine.GL_WORDS_GROUP_SAMPLES samples), 'linear' is (M, 1, 0), 'min_phase' takes mpx_min_phase's phasors.
+    init_rows: three matrices of tgt's shape and pitch to fold into (allocated here when None).  Returns a list of
+    (signal, phase rows) per utterance: float64 host arrays, or float32 device views with return_device."""
+    torch = __import__("torch")
+    H = N // 2 + 1
+    U = len(sizes)
+    f_off = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+    F = int(f_off[-1])
+    ld = int(engine.lib.mpx_spec_ld(H))
+    dev = lambda: engine.empty((max(F, 1), ld))[:F, :H]   # noqa: E731
+    i_mag, i_re, i_im = init_rows if init_rows is not None else (dev(), dev(), dev())
+    del init_rows
+    ph_dev = dev() if niters == 1 else None
+    outs = (i_mag, i_re, i_im)
+    # array inits: one gather, then one fold per utterance
+    arr = [u for u in range(U) if not isinstance(inits[u], str)]
+    if arr:
+        half = engine.empty((sum(sizes[u] for u in arr), H))
+        engine.pack_rows([[inits[u] for u in arr]], [half])
+        o = 0
+        for u in arr:
+            engine.griffin_lim_fold(N, "half", tgt, half[o:o + sizes[u]], int(f_off[u]), sizes[u], outs, ph_dev)
+            o += sizes[u]
+        del half
+    # 'linear': angle(fft(delta_{N/2})) is 0 or pi, the fold is (M, 1, 0) exactly
+    lin = [u for u in range(U) if isinstance(inits[u], str) and inits[u] == "linear"]
+    if lin:
+        row = None
+        if ph_dev is not None:
+            ph, _full = hm.griffin_lim_initial_phase("linear", np.empty((1, H)))
+            row = torch.from_numpy(np.ascontiguousarray(ph[0, :H], dtype=np.float32)).to(engine.device)
+        for u in lin:
+            a, b = int(f_off[u]), int(f_off[u + 1])
+            i_mag[a:b] = tgt[a:b]
+            i_re[a:b] = 1.0
+            i_im[a:b] = 0.0
+            if row is not None:
+                ph_dev[a:b] = row
+    # 'min_phase': mpx_min_phase's phasors, as with the host fold
+    mp_u = [u for u in range(U) if isinstance(inits[u], str) and inits[u] == "min_phase"]
+    if mp_u:
+        mp_rows = [np.arange(int(f_off[u]), int(f_off[u + 1])) for u in mp_u]
+        for u in mp_u:
+            a, b = int(f_off[u]), int(f_off[u + 1])
+            i_mag[a:b] = tgt[a:b]
+        mp_phase = _griffin_lim_min_phase(engine, N, tgt, mp_rows, i_re, i_im, ph_dev is not None)
+        if mp_phase is not None:
+            ph_dev[torch.from_numpy(np.concatenate(mp_rows)).to(engine.device)] = mp_phase
+    # 'random': consecutive utterances are one contiguous draw of numpy's stream; generated and folded in groups
+    rnd = [u for u in range(U) if isinstance(inits[u], str) and inits[u] == "random"]
+    k = 0
+    while k < len(rnd):
+        group, n = [rnd[k]], sizes[rnd[k]] * N
+        k += 1
+        while k < len(rnd) and n + sizes[rnd[k]] * N <= engine.GL_WORDS_GROUP_SAMPLES:
+            group.append(rnd[k])
+            n += sizes[rnd[k]] * N
+            k += 1
+        words = engine.numpy_global_words(n, defer=True)
+        o = j = 0
+        while j < len(group):   # utterances that follow one another in the batch: one launch
+            j1 = j + 1
+            while j1 < len(group) and group[j1] == group[j1 - 1] + 1:
+                j1 += 1
+            a, b = int(f_off[group[j]]), int(f_off[group[j1 - 1] + 1])
+            engine.griffin_lim_fold(N, "words", tgt, words, a, b - a, outs, ph_dev, phase_offset=o)
+            o += (b - a) * N
+            j = j1
+        del words
+    if rnd:
+        engine.mt_sync()
+    plan = GriffinLimPlan(engine, shifts, N)
+    init = [i_mag, i_re, i_im]
+    del i_mag, i_re, i_im, outs   # plan.run releases the init rows after the first synthesis
+    sig, ph_last = plan.run(tgt, init, niters, phase_rows=True)
+    if niters > 1:
+        ph_dev = ph_last
+    cut = lambda x, off: [x[int(off[u]):int(off[u + 1])] for u in range(U)]   # noqa: E731
+    if return_device:
+        return list(zip(cut(sig, plan.out_off_host), cut(ph_dev, f_off)))
+    h_sig, h_ph = engine.to_host_f64(sig), engine.to_host_f64(ph_dev)
+    return [(s.copy(), p.copy()) for s, p in zip(cut(h_sig, plan.out_off_host), cut(h_ph, f_off))]
+
+
+def griffin_lim_batch(utts, win_func=np.hanning, phase_init='random', niters=30, engine=None, return_device=False,
+                      fold=None):
     """
     griffin_lim (magphase.py:3320-3372) for a batch: utts = [(m_mag, v_shift), ...] with one fft_len per call;
     phase_init: one of 'random' / 'linear' / 'min_phase' / an ndarray for all, or a list with one per utterance.  Equal to
@@ -586,10 +752,37 @@ def griffin_lim_batch(utts, win_func=np.hanning, phase_init='random', niters=30,
     is one mpx_griffin_lim_ola launch.  Returns a list of (v_sig, m_phase) float64 (device float32 with return_device).
     Deviation: shifts outside the reference's domain raise ValueError for every niters (the reference only fails once
     it analyses, niters >= 2).
+    Device tensors: m_mag and an array phase_init may be 2-D torch tensors on the engine's device (float32 / float16 /
+    bfloat16 / float64, any row stride: gathered by Engine.pack_rows; never written).  CPU tensors are host arrays;
+    tensors of another device and integer / bool / complex tensors raise ValueError before any draw or launch.  v_shift
+    stays a host vector.
+    fold: where the initial phase is built and folded into the first synthesis' inputs.  'host': numpy, as described
+    above.  'device': mpx_griffin_lim_fold (k_gl_fold) -- 'random' continues numpy's global
+    MT19937 stream on the device (Engine.numpy_global_words: the state is left where the host draws would leave it, no
+    [F x N] phase matrix exists) and the phases returned for niters = 1 are the kernel's float32 rows.  None: 'device' if
+    an input is a device tensor, else 'host'; 'host' with a device tensor raises ValueError.
     """
     utts = list(utts)
     if not utts:
         return []
+    if fold not in (None, 'host', 'device'):
+        raise ValueError("griffin_lim_batch: fold must be None, 'host' or 'device', not %r" % (fold,))
+    utts, phase_init, on_dev = _griffin_lim_tensor_args(utts, phase_init)
+    if on_dev and fold == 'host':
+        raise ValueError("griffin_lim_batch: fold='host' with a device tensor (%s)" % on_dev[0][0])
+    if on_dev or fold == 'device':
+        real = list(phase_init) if isinstance(phase_init, (list, tuple)) else [phase_init] * len(utts)
+        shifts, _stand_ins, N = _griffin_lim_check(
+            [(_shape_only(m),) + tuple(r) for m, *r in utts], win_func,
+            [_shape_only(x) for x in phase_init] if isinstance(phase_init, (list, tuple)) else _shape_only(phase_init),
+            niters)
+        engine = engine or get_engine()
+        for name, x in on_dev:
+            if x.device != getattr(engine, "device", None):
+                raise ValueError("griffin_lim_batch: %s is on %s, the engine runs on %s"
+                                 % (name, x.device, getattr(engine, "device", None)))
+        utts = [(m if hasattr(m, "data_ptr") else np.asarray(m), v) for m, v in utts]
+        return _griffin_lim_device_fold(engine, utts, shifts, real, N, niters, return_device)
     shifts, inits, N = _griffin_lim_check(utts, win_func, phase_init, niters)
     H = N // 2 + 1
     sizes = [np.shape(m)[0] for m, _ in utts]
@@ -618,23 +811,8 @@ def griffin_lim_batch(utts, win_func=np.hanning, phase_init='random', niters=30,
         d.copy_(torch.from_numpy(h))
     del h_mag, h_re, h_im   # (the copies above are synchronous: the host rows are no longer needed)
     mp_phase = None
-    if mp_rows:   # la.build_min_phase_from_mag_spec's phasors, bins 0 and N/2 at phase 0, (-1)^k folded in
-        idx = np.concatenate(mp_rows)
-        rows = torch.from_numpy(idx.astype(np.int32)).to(engine.device)
-        n = int(idx.size)
-        o_m, o_r, o_i = (engine.empty((n, ld)) for _ in range(3))
-        engine.launch("mpx_min_phase", N, engine.tables(N), tgt, rows, rows,
-                      torch.zeros(n, dtype=torch.float32, device=engine.device), n, o_m, o_r, o_i, ld)
-        re, im = o_r[:, :H].clone(), o_i[:, :H].clone()
-        re[:, 0], im[:, 0], re[:, -1], im[:, -1] = 1.0, 0.0, 1.0, 0.0
-        if niters == 1:
-            mp_phase = torch.atan2(im, re)
-        sgn = torch.ones(H, dtype=torch.float32, device=engine.device)
-        sgn[1::2] = -1.0
-        ridx = rows.long()
-        i_re[ridx] = re * sgn
-        i_im[ridx] = im * sgn
-        del o_m, o_r, o_i, re, im
+    if mp_rows:
+        mp_phase = _griffin_lim_min_phase(engine, N, tgt, mp_rows, i_re, i_im, niters == 1)
     plan = GriffinLimPlan(engine, shifts, N)
     init = [i_mag, i_re, i_im]
     del i_mag, i_re, i_im   # plan.run releases the init rows after the first synthesis
@@ -667,6 +845,133 @@ def griffin_lim(m_mag, v_shift, win_func=np.hanning, phase_init='random', niters
     return griffin_lim_batch([(m_mag, v_shift)], win_func=win_func,
                              phase_init=[phase_init] if isinstance(phase_init, np.ndarray) else phase_init,
                              niters=niters)[0]
+
+
+def _griffin_lim_from_mag_tables(lf0s, fs, N, b_const_rate):
+    """The frame tables of synthesis_from_compressed (magphase.py:846-870, :879: integer shifts, constant -> variable rate
+    rows) for a batch of host lf0 vectors, checked against Griffin-Lim's domain; ValueError naming the utterance."""
+    from . import hostplan
+
+    try:
+        try:
+            r = hostplan.plan_synthesis([np.exp(l) for l in lf0s], fs, N, b_const_rate, True)
+        except hostplan.PlanFallback:
+            r = hostplan.plan_synthesis_numpy(lf0s, fs, N, b_const_rate, True)
+    except ValueError:   # which utterance: one at a time, in numpy (the reference's arithmetic, spelled out)
+        for i, l in enumerate(lf0s):
+            try:
+                hostplan.plan_synthesis_numpy([l], fs, N, b_const_rate, True)
+            except ValueError as err:
+                raise ValueError("utts[%d]: v_lf0 gives shifts outside Griffin-Lim's domain at fft_len %d (v_shift[0] <= "
+                                 "%d, the others <= %d): %s" % (i, N, N // 2, N // 2 - 1, err)) from None
+        raise
+    fo = np.asarray(r["frame_off"], dtype=np.int64)
+    shifts = []
+    for i in range(len(lf0s)):
+        v = np.asarray(r["v_shift"][int(fo[i]):int(fo[i + 1])], dtype=np.int64)
+        if v.size == 0:
+            raise ValueError("utts[%d]: no synthesis frames" % i)
+        right = np.append(v[1:], v[-1])
+        if np.any(v < 0) or v[0] > N // 2 or np.any(right > N // 2 - 1):
+            raise ValueError("utts[%d]: v_lf0 gives shifts outside Griffin-Lim's domain at fft_len %d (v_shift[0] <= %d, "
+                             "the others <= %d)" % (i, N, N // 2, N // 2 - 1))
+        shifts.append(v)
+    return r, shifts
+
+
+def griffin_lim_from_mag_batch(utts, fs, fft_len=None, phase_init='min_phase', niters=30, b_const_rate=False,
+                               b_fbank_mel=False, engine=None, return_device=False):
+    """Pitch-synchronous Griffin-Lim from the mel-log magnitudes and lf0 alone -- the third phase option of a
+    magnitude-only acoustic model, beside synthesis_from_mag_batch's 'min_phase' and 'zero'.  utts: list of
+    (m_mag_mel_log [rows x mag_dim], v_lf0 [rows]), host arrays or device tensors as synthesis_from_mag_batch takes them.
+    The target magnitudes are exp of the mel unwarp on the device, one row per synthesis frame (mpx_mel_unwarp; at the
+    constant rate mpx_mel_unwarp_rows with the constant -> variable rate row tables); the shifts are the integer v_shift of
+    synthesis_from_compressed (magphase.py:846-870, :879), so the signal has the length and the epochs of
+    synthesis_from_mag_batch on the same input; the rest is griffin_lim_batch(fold='device') on those device rows with
+    phase_init 'min_phase', 'random' (numpy's global generator, continued on the device) or 'linear' for the whole batch.
+    No noise is drawn and no noise table is built: nothing is taken from numpy's generator except the 'random' init.
+    Returns the signals: float64 host arrays, or float32 device views with return_device.
+    ValueError, naming the utterance, where a shift leaves Griffin-Lim's domain (v_shift[0] <= fft_len / 2, the others
+    <= fft_len / 2 - 1) or the utterances differ in mag_dim; ValueError for an fft_len without Griffin-Lim kernels and an
+    unknown phase_init.  No post-filter argument: post_filter_batch composes in front of this.  No autograd: the
+    iterations are not differentiated, a tensor that requires grad is read as a constant."""
+    utts = [tuple(u) for u in utts]
+    if any(len(u) != 2 for u in utts):
+        raise ValueError("utts: a list of (m_mag_mel_log, v_lf0)")
+    if not isinstance(phase_init, str) or phase_init not in _GL_INITS:
+        raise ValueError("griffin_lim_from_mag: unknown phase_init %r (%s)" % (phase_init, ", ".join(_GL_INITS)))
+    if isinstance(niters, bool) or not isinstance(niters, (int, np.integer)) or niters < 1:
+        raise ValueError("griffin_lim_from_mag: niters must be an integer >= 1")
+    if not utts:
+        return []
+    N = int(fft_len) if fft_len else hm.define_fft_len(fs)
+    if N not in hm.GL_FFT_LENS:
+        raise ValueError("griffin_lim_from_mag: fft_len %d; supported: %s" % (N, hm.GL_FFT_LENS))
+    alpha = hm.define_alpha(fs)
+    utts, _on_dev = _tensor_inputs(utts, _MAG_NAMES, lf0_at=1)
+    is_t = lambda x: hasattr(x, "data_ptr")   # noqa: E731  (what _tensor_inputs left: tensors that are not on the CPU)
+    mags = [m if is_t(m) else np.atleast_2d(np.asarray(m)) for m, _ in utts]
+    lf0s = [l if is_t(l) else np.atleast_1d(np.asarray(l, dtype=np.float64)) for _, l in utts]
+    mag_dim = int(mags[0].shape[1]) if len(mags[0].shape) == 2 else -1
+    for i, (m, l) in enumerate(zip(mags, lf0s)):
+        if len(m.shape) != 2 or int(m.shape[1]) != mag_dim:
+            raise ValueError("utts[%d]: m_mag_mel_log must be [rows x %d] like utts[0]'s, got shape %s"
+                             % (i, mag_dim, tuple(m.shape)))
+        if int(m.shape[0]) != int(l.shape[0]) or int(m.shape[0]) == 0:
+            raise ValueError("utts[%d]: m_mag_mel_log has %d rows, v_lf0 %d" % (i, int(m.shape[0]), int(l.shape[0])))
+    if not any(is_t(l) for l in lf0s):   # host lf0: every check before the first device call
+        r, shifts = _griffin_lim_from_mag_tables(lf0s, fs, N, b_const_rate)
+    engine = engine or get_engine()
+    for i, m in enumerate(mags):
+        if is_t(m) and m.device != getattr(engine, "device", None):
+            raise ValueError("utts[%d]: m_mag_mel_log is on %s, the engine runs on %s"
+                             % (i, m.device, getattr(engine, "device", None)))
+    if any(is_t(l) for l in lf0s):
+        r, shifts = _griffin_lim_from_mag_tables(engine.lf0_to_host(lf0s), fs, N, b_const_rate)
+    torch = __import__("torch")
+    H = N // 2 + 1
+    n_rows = int(sum(int(m.shape[0]) for m in mags))
+    sizes = [int(v.size) for v in shifts]
+    F = int(sum(sizes))
+    a_mag = engine.empty((n_rows, mag_dim))
+    if any(is_t(m) for m in mags):
+        engine.pack_rows([mags], [a_mag])
+    else:
+        a_mag.copy_(torch.from_numpy(np.concatenate([np.asarray(m, dtype=np.float32) for m in mags])))
+    if b_fbank_mel:
+        u_mag = engine.constant(("u_mag_fbank", mag_dim, H, float(alpha)), lambda: hm.unwarp_fbank_matrix(mag_dim, H, alpha))
+    else:
+        u_mag = engine.constant(("u_mag", mag_dim, H, float(alpha)), lambda: hm.unwarp_matrix(mag_dim, H, alpha))
+    # the unwarp's two phase jobs run on one zero column each; their outputs are the rows the fold overwrites afterwards
+    u_zero = engine.constant(("u_zero", 1, H), lambda: np.zeros((1, H)))
+    zcol = torch.zeros((n_rows, 1), dtype=torch.float32, device=engine.device)
+    ld = int(engine.lib.mpx_spec_ld(H))
+    dev = lambda: engine.empty((max(F, 1), ld))[:F, :H]   # noqa: E731
+    tgt, i_mag, i_re, i_im = dev(), dev(), dev(), dev()
+    if b_const_rate:
+        row0 = np.asarray(r["row0"])
+        CompressedSynthesisPlan._check_rows_for_tiles(row0, np.asarray(r["row1"]))
+        t = engine.to_device_packed([
+            ("row0", row0, np.int32), ("row1", r["row1"], np.int32), ("rowt", r["rowt"], np.float32),
+            ("tile_first", np.searchsorted(row0, 31 * np.arange((n_rows + 30) // 31 + 1), side="left"), np.int32)])
+        engine.launch("mpx_mel_unwarp_rows", F, H, a_mag, mag_dim, u_mag, tgt, zcol, zcol, 1, u_zero, i_re, i_im, ld,
+                      t["row0"], t["row1"], t["rowt"], n_rows, t["tile_first"], None, 0)
+    else:
+        if F != n_rows:
+            raise RuntimeError("griffin_lim_from_mag: %d frames for %d variable-rate rows" % (F, n_rows))
+        engine.launch("mpx_mel_unwarp", n_rows, H, a_mag, mag_dim, u_mag, tgt, zcol, zcol, 1, u_zero, i_re, i_im, ld)
+    for _ in utts:
+        print('Starting Griffin-Lim. It could take a while...')
+    out = _griffin_lim_device_rows(engine, tgt, sizes, shifts, [phase_init] * len(utts), N, niters, return_device,
+                                   init_rows=(i_mag, i_re, i_im))
+    return [sig for sig, _phase in out]
+
+
+def griffin_lim_from_mag(m_mag_mel_log, v_lf0, fs, fft_len=None, phase_init='min_phase', niters=30, b_const_rate=False,
+                         b_fbank_mel=False):
+    """One utterance of griffin_lim_from_mag_batch: the float64 signal."""
+    return griffin_lim_from_mag_batch([(m_mag_mel_log, v_lf0)], fs, fft_len=fft_len, phase_init=phase_init,
+                                      niters=niters, b_const_rate=b_const_rate, b_fbank_mel=b_fbank_mel)[0]
 
 
 def copy_synthesis_lossless(wav_file, fft_len=None):
