@@ -352,6 +352,31 @@ int mpx_analysis_lossless_backward(void* stream, int fft_len, const void* tables
                                    int64_t total_smpls);
 
 /*
+ * mpx_analysis_lossless_backward for rows that mpx_rows_lerp took to a constant frame rate afterwards (the constant-rate
+ * lossless analysis): grad_mag / grad_real / grad_imag are the gradients of the CONSTANT-rate rows out[c] =
+ * fma(x[row1[c]] - x[row0[c]], row_t[c], x[row0[c]]), [n_const_rows x fft_len/2 + 1] at row pitch ld_grad; mag / real /
+ * imag are the variable-rate rows x of the n_frames frames, as above.  ranges: int32 [n_frames x 4] = (a0, a1, b0, b1)
+ * per FRAME f -- the constant-rate rows with row0 == f are [a0, a1), those with row1 == f are [b0, b1)
+ * (hostmath.lerp_adjoint_table(row0, row1, row_t, n_frames)); row_t float32 [n_const_rows].  The frame kernel forms
+ * frame f's gradient row in registers as it loads it: c ascending over the union of the two ranges, weight 1 in both,
+ * 1 - row_t[c] in the first only, row_t[c] in the second only, acc = fmaf(w, grad_X[c][k], acc) from 0 -- the operation
+ * sequence of mpx_rows_lerp_adjoint, so grad_sig equals mpx_rows_lerp_adjoint followed by mpx_analysis_lossless_backward
+ * bit for bit, without the [n_frames x fft_len/2 + 1] gradient rows in between and with one launch fewer.  Ranges are
+ * clamped to [0, n_const_rows) whatever the table holds; a frame no row reads contributes zeros.  Everything else is as
+ * for mpx_analysis_lossless_backward: two launches, no atomics, one writer per element, deterministic; a null grad_X is
+ * never read; all three null, or n_frames == 0, launches nothing and leaves grad_sig untouched.  n_const_rows == 0 with
+ * frames and a gradient pointer zeroes grad_sig (ranges and row_t may then be null).
+ */
+int mpx_analysis_lossless_const_rate_backward(void* stream, int fft_len, const void* tables, const float* mag,
+                                              const float* real, const float* imag, int64_t ld, const float* grad_mag,
+                                              const float* grad_real, const float* grad_imag, int64_t ld_grad,
+                                              int64_t n_const_rows, const int32_t* ranges, const float* row_t,
+                                              const int64_t* frame_pos, const int32_t* frame_left,
+                                              const int32_t* frame_right, const int64_t* scratch_off, int64_t n_frames,
+                                              float* scratch, int64_t scratch_floats, float* grad_sig,
+                                              int64_t total_smpls);
+
+/*
  * Copy synthesis in one launch: analysis_lossless (magphase.py:2869-2906: windowing :74-119, analysis_with_del_comp_from_pm
  * :266-334, compute_lossless_feats :457-476) followed by synthesis_from_lossless (:1759-1776, ola :34-62) on the same
  * frames, as demos/demo_copy_synthesis_lossless.py:44-50 calls them back to back.  Frame f is cut out of `sig` exactly as

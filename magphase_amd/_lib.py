@@ -51,6 +51,8 @@ PROTOTYPES = {
     "mpx_rows_lerp_adjoint": (i32, [vp, i32, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, i64]),
     "mpx_analysis_lossless_backward": (i32, [vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, i64,
                                              vp, i64]),
+    "mpx_analysis_lossless_const_rate_backward": (i32, [vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, i64, i64, vp, vp, vp, vp,
+                                                        vp, vp, i64, vp, i64, vp, i64]),
     "mpx_ola_fixup": (i32, [vp, i32, vp, i32, vp, vp]),
     "mpx_ola_fixup_width": (i32, [vp, i32, vp, i32, vp, vp, i32]),
     "mpx_roundtrip_lossless_ola": (i32, [vp, i32] + [vp] * 5 + [i64, vp, i32, vp, vp, i32] + [vp] * 6 + [i64]),

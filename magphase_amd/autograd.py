@@ -8,6 +8,8 @@ entry function                forward -> backward                               
 synthesize                    Lossless[ConstRate]SynthesisPlan.run                m_mag, m_real, m_imag            3.3h
                                 -> .run_backward                                    | v_f0, fs
 analyze                       LosslessAnalysisPlan.run -> .run_backward           v_sig | v_pm_sec, v_voi, fs      3.3i
+analyze_const_rate            LosslessConstRateAnalysisPlan.run -> .run_backward  v_sig | v_pm_sec, v_voi, fs,     3.3i
+                                                                                    const_rate_ms
 analyze_compressed            CompressedAnalysisPlan.run -> .run_backward         v_sig | v_pm_sec, v_voi, fs      3.3j
 synthesize_compressed         CompressedSynthesisPlan.run, Engine.output_hpf      m_mag_mel_log, m_real_mel,       3.3k
                                 -> .adjoint_hpf, .run_backward                      m_imag_mel | v_lf0, fs, noise
@@ -28,8 +30,8 @@ post_filter                   Engine.post_filter[_merlin]                       
                                 -> Engine.post_filter[_merlin]_backward             pf_coef, av_* / boost_*
 
 No double backward.  synthesis_from_compressed_batch with per_phase_type 'min_phase' / 'linear' (synthesis_from_mag_batch
-is the differentiable form), any synthesis with a post-filter, with pcm16_norm or with prepared=, and the constant-rate
-lossless analysis, have no backward pass.
+is the differentiable form) and any synthesis with a post-filter, with pcm16_norm or with prepared= have no backward
+pass.
 """
 from collections import namedtuple
 from itertools import accumulate
@@ -139,6 +141,10 @@ def _run_type2_compressed(plan):
 _LOSSLESS = _AnalysisPath(run=lambda p: p.run(), keep=(0, 1, 2),
                           backward=lambda p, kept, grads: p.run_backward(kept[0], kept[1], kept[2], grads),
                           n_smpls=lambda p: p.n_smpls)
+# the three [total_out_frames x H] constant-rate matrices; nothing is kept (the variable-rate rows are recomputed)
+_CONST_RATE = _AnalysisPath(run=lambda p: p.run(), keep=(),
+                            backward=lambda p, kept, grads: p.run_backward(grads),
+                            n_smpls=lambda p: p.lossless.n_smpls)
 # [total_out_frames x mag_dim], [.. x phase_dim] twice: only these three small matrices are kept
 _COMPRESSED = _AnalysisPath(run=lambda p: p.run(), keep=(0, 1, 2),
                             backward=lambda p, kept, grads: p.run_backward(kept, grads),
@@ -176,7 +182,9 @@ class _Analysis(torch.autograd.Function):
         kept = ctx.saved_tensors
         path, plan = ctx.path, ctx.plan
         grads = tuple(_coerce(g) for g in grads[:3])
-        with torch.cuda.device(kept[0].device):
+        # (a path that keeps nothing: the device of the first gradient given -- backward() is not called without one)
+        dev = kept[0].device if kept else next(g for g in grads if g is not None).device
+        with torch.cuda.device(dev):
             gsig = path.backward(plan, kept, grads)
         return (None, None) + _scatter(gsig, _offsets(path.n_smpls(plan)), ctx.like, ctx.needs_input_grad[2:])
 
@@ -190,6 +198,12 @@ def analyze(plan, sigs):
     """plan.run(), differentiable with respect to the v_sig in sigs that are tensors requiring grad.  Returns the three
     float32 [total_frames x H] matrices (with grad_fn)."""
     return _analyze(_LOSSLESS, plan, sigs)
+
+
+def analyze_const_rate(plan, sigs):
+    """plan.run() of a LosslessConstRateAnalysisPlan, differentiable with respect to the v_sig in sigs that are tensors
+    requiring grad.  Returns the three float32 [total_out_frames x H] matrices (with grad_fn)."""
+    return _analyze(_CONST_RATE, plan, sigs)
 
 
 def analyze_compressed(plan, sigs):

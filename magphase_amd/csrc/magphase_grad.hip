@@ -1,5 +1,6 @@
 // magphase_grad.hip -- backward passes of the lossless synthesis (first part of this file) and of
-// the lossless analysis (section 3.3i: k_analysis_lossless_bwd, k_analysis_bwd_gather, further down).
+// the lossless analysis (section 3.3i: k_analysis_lossless_bwd<P, CR>, k_analysis_bwd_gather, further down; CR: the
+// gradients come on the constant-rate rows of the constant-rate analysis and are gathered per frame in registers).
 //
 //   k_synth_lossless_bwd<P, L>  one wavefront per frame, persistent waves (grid-stride over frames), the shape of
 //                               k_analysis: the N samples of the incoming waveform gradient around the frame's pitch mark
@@ -327,7 +328,8 @@ __global__ __launch_bounds__(kAdjWaves * 64) void k_rows_lerp_adjoint(int H, con
 //   b = N irfft_N(Y), Y_k = gX_k / 2 for 0 < k < N/2, Y_0 = Re gX_0, Y_{N/2} = Re gX_{N/2}   (the transpose of rfft_N)
 //   gfrm[k] = b[(k - rot) mod N] w(k) for 0 <= k < len,   gsig[pos - L + k] += gfrm[k]
 //
-//   k_analysis_lossless_bwd<P>  one wavefront per frame, persistent waves (grid-stride), the shape of k_synth_lossless:
+//   k_analysis_lossless_bwd<P, CR>  (CR = false here; the CR arm is described at the kernel)
+//                               one wavefront per frame, persistent waves (grid-stride), the shape of k_synth_lossless:
 //                               the six rows of a frame in the paired layout of feat_load_paired (ascending bins
 //                               lane + 64 j and their mirrors M - k: every load one contiguous 256-byte block) -> gX ->
 //                               merge_pair_step / merge_handover -> wave_fft<P, +1> -> rotation, hann_half -> the frame's
@@ -349,6 +351,36 @@ __device__ __forceinline__ void ana_bwd_bin(float m, float a, float b, float gm,
     x_i = gs * b + (gi - b * d) * inv;
 }
 
+// merge_pair_step (mpx_common.hpp) in two parts, for the CR arm of k_analysis_lossless_bwd: the step's twiddle
+// conj(W_N^k) = (wl_c + j wl_s) e^{2 pi i q / 2P}, and the step given it.  merge_pair_step writes the twiddle as
+// wr = wl_c cq - wl_s sq, wi = wl_c sq + wl_s cq and leaves it to the compiler which product of each sum is folded into
+// the fused multiply-add and which is rounded on its own.  The four products of step q are shared with step P/2 - q
+// (cos and sin change places), so that choice depends on the order in which the instruction selector meets the steps --
+// it is made per basic block, and the CR = false arm and this one do not have the same blocks: built from the same
+// expressions, the two arms' twiddles differed in the last bit at P = 16 / 32, and the fused backward pass with them
+// from the staged one.  So the CR arm spells out what the CR = false instantiations do (read from their gfx950 code with
+// a symbolic trace of the twiddle registers, and held bit for bit by tests/test_gpu_const_rate_analysis_autograd.py): of
+// the two products of a sum one is fused and the other rounded first -- at P = 16 / 32 the one with the larger constant
+// is fused, at P = 8 the one with the smaller constant; at cq == sq the product of wl_s is fused.
+template <int P>
+__device__ __forceinline__ void merge_twiddle(int q, float wl_c, float wl_s, float& wr, float& wi) {
+#pragma clang fp contract(off)
+    const float cq = cos2p<P>(q), sq = sin2p<P>(q);
+    // fuse_c: the products with cq are the fused ones (wl_c cq in wr, wl_s cq in wi); else those with sq
+    const bool tie = (cq == sq), fuse_c = (P == 8) ? (cq < sq) : (cq > sq);
+    wr = fuse_c ? __builtin_fmaf(wl_c, cq, -(wl_s * sq)) : __builtin_fmaf(-wl_s, sq, wl_c * cq);
+    wi = (fuse_c || tie) ? __builtin_fmaf(wl_s, cq, wl_c * sq) : __builtin_fmaf(wl_c, sq, wl_s * cq);
+}
+__device__ __forceinline__ void merge_pair_step_w(float x_r, float x_i, float p_r, float p_i, float wr, float wi,
+                                                  float& out_r, float& out_i, float& z_r, float& z_i) {
+    const float er = x_r + p_r, ei = x_i - p_i, tr = x_r - p_r, ti = x_i + p_i;
+    const float orr = wr * tr - wi * ti, oi = wr * ti + wi * tr;
+    out_r = er - oi;
+    out_i = ei + orr;
+    z_r = er + oi;
+    z_i = orr - ei;
+}
+
 // Waves per workgroup: k_analysis' 12 (three per SIMD, <= 168 VGPRs) for P = 8 / 16; P = 32 holds 64 spectrum registers
 // beside the row loads and needs more than 168 (it spilled 51 at any load group size): 8 waves, two per SIMD, as
 // k_synth_lossless.
@@ -357,12 +389,24 @@ constexpr int ana_bwd_waves() { return P == 32 ? kWavesPerBlock : kAnaWaves; }
 template <int P>
 constexpr size_t lds_bytes_ana_bwd() { return sizeof(float) * (size_t)(tw_floats<P>() + ana_bwd_waves<P>() * P * kXStride); }
 
-template <int P>
+//
+// CR = true (the constant-rate analysis, mpx_analysis_lossless_const_rate_backward): gmag / greal / gimag are the gradients
+// of the CONSTANT-rate rows out[c] = fma(rows[row1_c] - rows[row0_c], t_c, rows[row0_c]), [n_crows x H] at pitch ldg, and
+// the wave forms frame f's own gradient row in registers while it loads a group of bin pairs: rng[4 f .. 4 f + 3] =
+// (a0, a1, b0, b1) (hostmath.lerp_adjoint_table over the variable frames: the constant-rate rows with row0 == f are
+// [a0, a1), those with row1 == f are [b0, b1), clamped to [0, n_crows) whatever the table holds), c ascending over their
+// union, w = 1 in both, 1 - t_c in the first only, t_c in the second only, acc = fmaf(w, g[c][k], acc) from 0 -- per
+// element k_rows_lerp_adjoint's operation sequence, so the result equals the staged form (that kernel, then CR = false)
+// bit for bit, and nothing [nframes x H]-sized is written or read for the gradients.  A frame no row reads has a zero
+// gradient row and still writes its zeros to the scratch.  The accumulators are the load group's own g / gq registers;
+// the gather runs BEFORE the group's six forward loads, so that a row's 6 CH loads in flight stand where those would.
+template <int P, bool CR = false>
 __global__ __launch_bounds__(64 * ana_bwd_waves<P>()) void k_analysis_lossless_bwd(
     const float* __restrict__ mag, const float* __restrict__ real, const float* __restrict__ imag, long long ld,
     const float* __restrict__ gmag, const float* __restrict__ greal, const float* __restrict__ gimag, long long ldg,
     const int* __restrict__ fleft, const int* __restrict__ fright, const long long* __restrict__ soff, long long nframes,
-    const float* __restrict__ tw_g, float* __restrict__ scratch, long long scratch_floats) {
+    const float* __restrict__ tw_g, float* __restrict__ scratch, long long scratch_floats, const int* __restrict__ rng,
+    const float* __restrict__ rowt, int n_crows) {
     constexpr int M = 64 * P, N = 2 * M, LB = ilog2(P), HP = P / 2;
     constexpr int CH = 4;   // bin pairs per load group: 12 CH row values in flight beside the 2 P of the growing spectrum
     constexpr int kWaves = ana_bwd_waves<P>(), kThr = 64 * kWaves;
@@ -390,10 +434,54 @@ __global__ __launch_bounds__(64 * ana_bwd_waves<P>()) void k_analysis_lossless_b
         const float* row[3] = {mag + f * ld, real + f * ld, imag + f * ld};
         const float* grow[3] = {gmag ? gmag + f * ldg : nullptr, greal ? greal + f * ldg : nullptr,
                                 gimag ? gimag + f * ldg : nullptr};
+        // CR: the constant-rate streams from their row 0, frame f's two row ranges (wave-uniform) and the gathered
+        // gradient of bin M/2 + lane (formed with the last group)
+        const float* gsrc[3] = {gmag, greal, gimag};
+        int a0 = 0, a1 = 0, b0 = 0, b1 = 0, c_lo = 0, c_hi = 0;
+        float gh[3] = {0.0f, 0.0f, 0.0f};
+        if constexpr (CR) {
+            a0 = min(max(rng[4 * f + 0], 0), n_crows);
+            a1 = min(max(rng[4 * f + 1], 0), n_crows);
+            b0 = min(max(rng[4 * f + 2], 0), n_crows);
+            b1 = min(max(rng[4 * f + 3], 0), n_crows);
+            const bool has_a = a1 > a0, has_b = b1 > b0;
+            c_lo = has_a ? (has_b ? min(a0, b0) : a0) : b0;
+            c_hi = has_a ? (has_b ? max(a1, b1) : a1) : (has_b ? b1 : b0);
+        }
         float xr[P], xi[P], zr[HP], zi[HP];
+        float twr[HP], twi[HP];   // CR: the steps' twiddles (see merge_twiddle)
+        if constexpr (CR) {
+#pragma unroll
+            for (int j = 0; j < HP; ++j) merge_twiddle<P>(j, wl_c, wl_s, twr[j], twi[j]);
+        }
 #pragma unroll
         for (int c = 0; c < HP; c += CH) {
             float v[3][CH], vq[3][CH], g[3][CH], gq[3][CH];
+            float ga[3][CH], gqa[3][CH];   // CR: the group's gathered gradients, formed before its forward rows are loaded
+            if constexpr (CR) {
+#pragma unroll
+                for (int s = 0; s < 3; ++s)
+#pragma unroll
+                    for (int e = 0; e < CH; ++e) ga[s][e] = gqa[s][e] = 0.0f;
+                for (int r = c_lo; r < c_hi; ++r) {
+                    const bool in_a = (r >= a0 && r < a1), in_b = (r >= b0 && r < b1);
+                    if (!in_a && !in_b) continue;   // wave-uniform
+                    const float t = rowt[r];
+                    const float w = (in_a && in_b) ? 1.0f : (in_a ? 1.0f - t : t);
+#pragma unroll
+                    for (int s = 0; s < 3; ++s) {
+                        if (!gsrc[s]) continue;   // wave-uniform: a null stream is never loaded
+                        const float* lo = gsrc[s] + (long long)r * ldg + lane;
+                        const float* hi = gsrc[s] + (long long)r * ldg + (M - lane);
+#pragma unroll
+                        for (int e = 0; e < CH; ++e) {
+                            ga[s][e] = fmaf(w, lo[64 * (c + e)], ga[s][e]);
+                            gqa[s][e] = fmaf(w, hi[-64 * (c + e)], gqa[s][e]);
+                        }
+                        if (c + CH >= HP) gh[s] = fmaf(w, lo[M / 2], gh[s]);
+                    }
+                }
+            }
 #pragma unroll
             for (int s = 0; s < 3; ++s) {
                 const float* lo = row[s] + lane;
@@ -405,16 +493,26 @@ __global__ __launch_bounds__(64 * ana_bwd_waves<P>()) void k_analysis_lossless_b
                     g[s][e] = gq[s][e] = 0.0f;
                 }
             }
+            if constexpr (!CR) {
 #pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                if (!grow[s]) continue;   // wave-uniform
-                const float* lo = grow[s] + lane;
-                const float* hi = grow[s] + (M - lane);
+                for (int s = 0; s < 3; ++s) {
+                    if (!grow[s]) continue;   // wave-uniform
+                    const float* lo = grow[s] + lane;
+                    const float* hi = grow[s] + (M - lane);
 #pragma unroll
-                for (int e = 0; e < CH; ++e) {
-                    g[s][e] = lo[64 * (c + e)];
-                    gq[s][e] = hi[-64 * (c + e)];
+                    for (int e = 0; e < CH; ++e) {
+                        g[s][e] = lo[64 * (c + e)];
+                        gq[s][e] = hi[-64 * (c + e)];
+                    }
                 }
+            } else {
+#pragma unroll
+                for (int s = 0; s < 3; ++s)
+#pragma unroll
+                    for (int e = 0; e < CH; ++e) {
+                        g[s][e] = ga[s][e];
+                        gq[s][e] = gqa[s][e];
+                    }
             }
 #pragma unroll
             for (int e = 0; e < CH; ++e) {
@@ -427,16 +525,22 @@ __global__ __launch_bounds__(64 * ana_bwd_waves<P>()) void k_analysis_lossless_b
                 ana_bwd_bin(vq[0][e], vq[1][e], vq[2][e], gq[0][e], gq[1][e], gq[2][e], sc, p_r, p_i);
                 x_i = edge ? 0.0f : x_i;
                 p_i = edge ? 0.0f : p_i;
-                merge_pair_step<P>(j, x_r, x_i, p_r, p_i, wl_c, wl_s, xr[j], xi[j], zr[j], zi[j]);
+                if constexpr (!CR) merge_pair_step<P>(j, x_r, x_i, p_r, p_i, wl_c, wl_s, xr[j], xi[j], zr[j], zi[j]);
+                else merge_pair_step_w(x_r, x_i, p_r, p_i, twr[j], twi[j], xr[j], xi[j], zr[j], zi[j]);
             }
         }
         {   // bin M/2 is its own mirror (lane 0): Z = 2 conj(Y).  Every lane loads "its" bin M/2 + lane (feat_load_paired)
             float v[3], g[3] = {0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int s = 0; s < 3; ++s) v[s] = row[s][M / 2 + lane];
+            if constexpr (!CR) {
 #pragma unroll
-            for (int s = 0; s < 3; ++s)
-                if (grow[s]) g[s] = grow[s][M / 2 + lane];
+                for (int s = 0; s < 3; ++s)
+                    if (grow[s]) g[s] = grow[s][M / 2 + lane];
+            } else {
+#pragma unroll
+                for (int s = 0; s < 3; ++s) g[s] = gh[s];
+            }
             float h_r, h_i;
             ana_bwd_bin(v[0], v[1], v[2], g[0], g[1], g[2], 0.5f, h_r, h_i);
             merge_handover<P>(zr, zi, 2.0f * h_r, -2.0f * h_i, xr, xi, lane);
@@ -566,12 +670,63 @@ int mpx_analysis_lossless_backward(void* stream, int fft_len, const void* tables
         hipLaunchKernelGGL((k_analysis_lossless_bwd<PP>), grid, block, lds_bytes_ana_bwd<PP>(), s, mag, real, imag,   \
                            (long long)ld, grad_mag, grad_real, grad_imag, (long long)ld_grad, frame_left, frame_right, \
                            (const long long*)scratch_off, (long long)n_frames, (const float*)tables, scratch,         \
-                           (long long)scratch_floats);                                                               \
+                           (long long)scratch_floats, (const int*)nullptr, (const float*)nullptr, 0);                \
     } while (0)
     if (P == 32) MPX_LAUNCH_ABWD(32);
     else if (P == 16) MPX_LAUNCH_ABWD(16);
     else MPX_LAUNCH_ABWD(8);
 #undef MPX_LAUNCH_ABWD
+    MPX_HIP_CHECK(hipGetLastError());
+    if (total_smpls > 0) {
+        hipLaunchKernelGGL(k_analysis_bwd_gather, dim3((unsigned)((total_smpls + 255) / 256)), dim3(256), 0, s, scratch,
+                           (long long)scratch_floats, (const long long*)frame_pos, frame_left,
+                           (const long long*)scratch_off, (long long)n_frames, grad_sig, (long long)total_smpls);
+        MPX_HIP_CHECK(hipGetLastError());
+    }
+    return MPX_OK;
+}
+
+int mpx_analysis_lossless_const_rate_backward(void* stream, int fft_len, const void* tables, const float* mag,
+                                              const float* real, const float* imag, int64_t ld, const float* grad_mag,
+                                              const float* grad_real, const float* grad_imag, int64_t ld_grad,
+                                              int64_t n_const_rows, const int32_t* ranges, const float* row_t,
+                                              const int64_t* frame_pos, const int32_t* frame_left,
+                                              const int32_t* frame_right, const int64_t* scratch_off, int64_t n_frames,
+                                              float* scratch, int64_t scratch_floats, float* grad_sig,
+                                              int64_t total_smpls) {
+    const int P = p_of(fft_len);
+    if (!P) return fail(MPX_ERR_ARG, "mpx_analysis_lossless_const_rate_backward: fft_len must be 1024, 2048 or 4096%s");
+    if (n_frames < 0 || total_smpls < 0 || scratch_floats < 0 || n_const_rows < 0)
+        return fail(MPX_ERR_ARG, "mpx_analysis_lossless_const_rate_backward: negative count%s");
+    if (ld < fft_len / 2 + 1 || ld_grad < fft_len / 2 + 1)
+        return fail(MPX_ERR_ARG, "mpx_analysis_lossless_const_rate_backward: ld < fft_len/2 + 1%s");
+    if (n_const_rows > 2147483647LL)
+        return fail(MPX_ERR_ARG, "mpx_analysis_lossless_const_rate_backward: too many constant-rate rows%s");
+    if (n_frames == 0) return MPX_OK;
+    if (!grad_mag && !grad_real && !grad_imag) return MPX_OK;   // nothing to propagate: grad_sig is not written
+    if (!tables || !mag || !real || !imag || !frame_pos || !frame_left || !frame_right || !scratch_off ||
+        (scratch_floats > 0 && !scratch) || (total_smpls > 0 && !grad_sig) || (n_const_rows > 0 && (!ranges || !row_t)))
+        return fail(MPX_ERR_ARG, "mpx_analysis_lossless_const_rate_backward: null pointer%s");
+    if ((total_smpls + 255) / 256 > 2147483647LL)
+        return fail(MPX_ERR_ARG, "mpx_analysis_lossless_const_rate_backward: too many samples%s");
+    hipStream_t s = (hipStream_t)stream;
+    if (n_const_rows == 0) {   // no row reads any frame: the gradient is zero (and the tables may be null)
+        if (total_smpls > 0) MPX_HIP_CHECK(hipMemsetAsync(grad_sig, 0, sizeof(float) * (size_t)total_smpls, s));
+        return MPX_OK;
+    }
+#define MPX_LAUNCH_ABWD_CR(PP)                                                                                        \
+    do {                                                                                                              \
+        const dim3 grid(grid_for(n_frames, ana_bwd_waves<PP>())), block(64 * ana_bwd_waves<PP>());                    \
+        if (int rc = set_lds((k_analysis_lossless_bwd<PP, true>), lds_bytes_ana_bwd<PP>())) return rc;                \
+        hipLaunchKernelGGL((k_analysis_lossless_bwd<PP, true>), grid, block, lds_bytes_ana_bwd<PP>(), s, mag, real,   \
+                           imag, (long long)ld, grad_mag, grad_real, grad_imag, (long long)ld_grad, frame_left,       \
+                           frame_right, (const long long*)scratch_off, (long long)n_frames, (const float*)tables,     \
+                           scratch, (long long)scratch_floats, ranges, row_t, (int)n_const_rows);                    \
+    } while (0)
+    if (P == 32) MPX_LAUNCH_ABWD_CR(32);
+    else if (P == 16) MPX_LAUNCH_ABWD_CR(16);
+    else MPX_LAUNCH_ABWD_CR(8);
+#undef MPX_LAUNCH_ABWD_CR
     MPX_HIP_CHECK(hipGetLastError());
     if (total_smpls > 0) {
         hipLaunchKernelGGL(k_analysis_bwd_gather, dim3((unsigned)((total_smpls + 255) / 256)), dim3(256), 0, s, scratch,

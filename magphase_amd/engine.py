@@ -1878,6 +1878,37 @@ class Engine:
                     plan.pos, plan.left, plan.right, soff, nfr, scratch, scratch_floats, out, total)
         return out
 
+    def analysis_lossless_const_rate_backward(self, fft_len, plan, mag, real, imag, grads, ranges, rowt):
+        """mpx_analysis_lossless_const_rate_backward (the one place that launches it): analysis_lossless_backward for
+        gradients given on the CONSTANT-rate rows that mpx_rows_lerp made of plan's rows.  mag / real / imag: the
+        variable-rate rows plan.run() returned; grads = (g_mag, g_real, g_imag): float32 [n_const_rows x H] with unit
+        column stride and one row pitch, or None (not read, contributes zero); ranges: device int32 [plan.total_frames x 4]
+        (hostmath.lerp_adjoint_table over the variable frames), rowt: device float32 [n_const_rows] -> dL/d(samples),
+        float32 [plan.total_smpls].  The frame kernel forms every frame's gradient row as it loads it: no
+        [total_frames x H] gradient rows, no mpx_rows_lerp_adjoint launch, the same bits as the two calls."""
+        torch = _torch()
+        H = int(fft_len) // 2 + 1
+        nfr, total = int(plan.total_frames), int(plan.total_smpls)
+        have = [g for g in grads if g is not None]
+        n_const = int(have[0].shape[0]) if have else 0
+        for g in have:
+            if g.dtype != torch.float32 or tuple(g.shape) != (n_const, H) or g.stride(1) != 1:
+                raise ValueError("analysis_lossless_const_rate_backward: gradients must be float32 [%d x %d]" % (n_const, H))
+        if have and int(rowt.shape[0]) != n_const:
+            raise ValueError("analysis_lossless_const_rate_backward: %d gradient rows, rowt has %d"
+                             % (n_const, int(rowt.shape[0])))
+        if nfr == 0 or total == 0 or n_const == 0:
+            return torch.zeros((total,), dtype=torch.float32, device=self.device)
+        if int(ranges.numel()) != 4 * nfr:
+            raise ValueError("analysis_lossless_const_rate_backward: ranges must hold 4 entries per frame")
+        soff, scratch_floats = plan.backward_tables()
+        scratch = self.empty((max(scratch_floats, 1),))
+        out = self.empty((total,))
+        self.launch("mpx_analysis_lossless_const_rate_backward", int(fft_len), self.tables(fft_len), mag, real, imag,
+                    self.feat_ld(mag, real, imag), grads[0], grads[1], grads[2], self.feat_ld(*(have * 3)[:3]), n_const,
+                    ranges, rowt, plan.pos, plan.left, plan.right, soff, nfr, scratch, scratch_floats, out, total)
+        return out
+
     def rows_lerp_adjoint(self, src, ranges, rowt, n_rows):
         """mpx_rows_lerp_adjoint: src = (g_mag, g_real, g_imag) per-frame rows (None: stream not wanted), ranges int32
         [n_rows x 4] (hostmath.lerp_adjoint_table) and rowt on the device -> the gradients of the n_rows table rows, a

@@ -404,6 +404,13 @@ def analysis_lossless_const_rate_batch(utts, fft_len=None, const_rate_ms=5.0, en
     (m_mag, m_real, m_imag, v_f0, fs): float64 numpy, or float32 device rows with return_device (v_f0 is float64 numpy
     either way).  An utterance shorter than one step gives (0, H) matrices and an empty f0; one without a voiced frame
     raises (IndexError, as analysis_compressed_batch(b_const_rate=True) does).  copy: as analysis_lossless_batch.
+    v_sig may be a 1-D torch tensor on the engine's device (float32 / float16 / bfloat16 / float64, any element stride),
+    under analysis_lossless_batch's rules: the samples stay on the device, the rows equal those of the host-array call on
+    the same float32 samples bit for bit, a CPU tensor is a host array, a tensor on another device raises ValueError.
+    Autograd: with return_device, grad mode on and a device v_sig that requires grad, m_mag / m_real / m_imag carry a
+    grad_fn and tensor.backward() reaches v_sig (magphase_amd/autograd.py: analyze_const_rate; the forward launches and
+    their rows are the same, nothing is kept between the passes).  Not differentiable: v_pm_sec, v_voi, fs and
+    const_rate_ms; v_f0 stays a float64 host vector without grad_fn; no double backward.
     """
     const_rate_ms = check_const_rate_ms(const_rate_ms)
     utts = list(utts)
@@ -414,7 +421,12 @@ def analysis_lossless_const_rate_batch(utts, fft_len=None, const_rate_ms=5.0, en
     for lens in plan.long_frame_lens:
         for n in lens:  # Q19: truncation warns, it does not raise (magphase.py:311-315)
             warnings.warn(_WARN_LONG % (plan.fft_len, n))
-    mag, real, imag = plan.run()
+    if hm.wants_grad(return_device, [u[0] for u in utts]):
+        from .autograd import analyze_const_rate
+
+        mag, real, imag = analyze_const_rate(plan, [u[0] for u in utts])
+    else:
+        mag, real, imag = plan.run()
     if not return_device:
         h_feats = tuple(engine.to_host_f64_many([mag, real, imag]))
     out = []

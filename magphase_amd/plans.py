@@ -703,6 +703,64 @@ class LosslessConstRateAnalysisPlan:
         del var   # (stream-ordered: the allocator reuses the scratch after the interpolation)
         return out
 
+    def check_differentiable(self):
+        """What run_backward cannot take, said before any launch: nothing."""
+
+    def _backward_inputs(self, grads):
+        """The checks both backward forms share -> True when there is something to propagate."""
+        torch = _torch()
+        shp = (self.total_out_frames, self.fft_len // 2 + 1)
+        if len(grads) != 3:
+            raise ValueError("run_backward: grads = (g_mag, g_real, g_imag)")
+        for g in grads:
+            if g is not None and (g.dtype != torch.float32 or tuple(g.shape) != shp or not g.is_contiguous()):
+                raise ValueError("run_backward: gradients must be contiguous float32 [%d x %d]" % shp)
+        pl = self.lossless
+        return not (self.total_out_frames == 0 or int(pl.total_frames) == 0 or int(pl.total_smpls) == 0
+                    or all(g is None for g in grads))
+
+    def _adjoint_table(self):
+        """Per VARIABLE frame the constant-rate rows that read it (hostmath.lerp_adjoint_table of the plan's own host
+        tables), device int32 [4 total_frames]; built and uploaded by the first backward pass."""
+        if getattr(self, "_adj", None) is None:
+            self._adj = self.engine.to_device(hm.lerp_adjoint_table(self.row0_host, self.row1_host, self.rowt_host,
+                                                                    int(self.lossless.total_frames)).reshape(-1), np.int32)
+        return self._adj
+
+    def _zero_grad(self):
+        return _torch().zeros((int(self.lossless.total_smpls),), dtype=_torch().float32, device=self.engine.device)
+
+    def run_backward(self, grads):
+        """The gradient of a loss with respect to the batch's samples, float32 [total_smpls] (utterance u at the offset of
+        its samples in self.lossless.sig), given grads = (dL/d mag, dL/d real, dL/d imag) of run()'s constant-rate rows:
+        contiguous float32 [total_out_frames x H], or None for an output nobody differentiated (not read).  Zeros when
+        there are no rows, no frames or no gradients.  The variable-rate rows are RECOMPUTED (run() released them:
+        nothing is kept between the passes); then the fused form, k_analysis_lossless_bwd<P, CR = true> (the frame's
+        gradient row gathered from the constant-rate ones in registers) + k_analysis_bwd_gather.
+        Equals run_backward_staged bit for bit."""
+        if not self._backward_inputs(grads):
+            return self._zero_grad()
+        pl = self.lossless
+        rows = pl.run()
+        _wait_ready(pl)
+        out = self.engine.analysis_lossless_const_rate_backward(self.fft_len, pl, rows[0], rows[1], rows[2], grads,
+                                                                self._adjoint_table(), self.rows[2])
+        del rows   # (stream-ordered: the allocator reuses the scratch after the backward launches)
+        return out
+
+    def run_backward_staged(self, grads):
+        """run_backward from existing kernels only, the cross-check of the fused form: self.lossless.run() writes every
+        row, k_rows_lerp_adjoint folds the constant-rate gradients onto [total_frames x H] scratch rows, then
+        LosslessAnalysisPlan.run_backward (k_analysis_lossless_bwd<P> + k_analysis_bwd_gather)."""
+        if not self._backward_inputs(grads):
+            return self._zero_grad()
+        e, pl = self.engine, self.lossless
+        rows = pl.run()
+        g_rows = e.rows_lerp_adjoint(grads, self._adjoint_table(), self.rows[2], int(pl.total_frames))
+        out = pl.run_backward(rows[0], rows[1], rows[2], g_rows)
+        del rows, g_rows
+        return out
+
 
 class LosslessConstRateSynthesisPlan:
     """
