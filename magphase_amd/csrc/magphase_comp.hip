@@ -1617,11 +1617,16 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_roundtrip_pair(const fl
 // the fftshift of the synthesis undoes the factor -- the magnitude is replaced in this kernel's own convention.  X == 0
 // (the reference's angle(0) = 0) becomes the phasor (-1)^k, never NaN.  phase_out (null except on the last iteration)
 // receives angle(X_ref) for bins 0..M with np.angle's range, rows `ld` floats apart like the target magnitudes.
+// Whether the phase rows are written is a run-time branch around the arctangents (wave-uniform: a kernel argument), not a
+// template parameter: as two instances the compiler contracted the same source differently (under -ffp-contract=fast a
+// multiply fuses only with an add of its own basic block, and the arctangents' branches cut the blocks elsewhere; which
+// product of a b - c d is fused depends on the order of the block's nodes), and at P = 32 the signal of the launch with
+// phase rows differed from the other's in the last bit of 3 samples in 4.  One instance, one signal.
 // No feature rows are written; target magnitudes are float32 rows of pitch ld.  sig_in and sig_out must not overlap.
 // A kernel of its own, built from the same frame stages as k_roundtrip_pair, rather than a template arm of it: only the
 // middle of the frame loop (what is done to the spectrum) is this kernel's.
 // ---------------------------------------------------------------------------------------------
-template <int P, bool PHASE>   // PHASE: phase_out is written (the last launch of a run of iterations)
+template <int P>
 __global__ __launch_bounds__(kCompPairWaves * 64) void k_griffin_lim_pair(const float* __restrict__ sig,
                                                                          const long long* __restrict__ fpos,
                                                                          const int* __restrict__ fleft,
@@ -1662,12 +1667,12 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_griffin_lim_pair(const 
             const bool lane0 = (lane == 0);
             const float sgn = (lane & 1) ? -1.0f : 1.0f;
             const float* trow = tmag + (long long)fi * ld;
-            float* prow = PHASE ? phase_out + (long long)fi * ld : nullptr;
-            if constexpr (PHASE) {   // angle(X_ref), X_ref = (-1)^k X; X == 0 -> 0.  One bin pair at a time (the
+            if (phase_out != nullptr) {   // angle(X_ref), X_ref = (-1)^k X; X == 0 -> 0.  One bin pair at a time (the
                 // barrier keeps the compiler from interleaving the arctangents, which spills at P = 32)
                 auto ang = [](float x_r, float x_i, float s) {
                     return (x_r == 0.0f && x_i == 0.0f) ? 0.0f : atan2f(s * x_i, s * x_r);
                 };
+                float* prow = phase_out + (long long)fi * ld;
 #pragma unroll
                 for (int q = 0; q < HP; ++q) {
                     const int k = lane + 64 * q;
@@ -2154,7 +2159,7 @@ int mpx_griffin_lim_ola(void* stream, int fft_len, const void* tables, const flo
     const dim3 pgrid((n_slots + kCompPairs - 1) / kCompPairs), pblock(kCompPairWaves * 64);
 #define MPX_LAUNCH_GL(PP)                                                                                              \
     do {                                                                                                             \
-        auto KK = phase_out ? k_griffin_lim_pair<PP, true> : k_griffin_lim_pair<PP, false>;                          \
+        auto KK = k_griffin_lim_pair<PP>;                                                                            \
         if (int rc = set_lds(KK, lds_bytes_comp_pair<PP>())) return rc;                                              \
         hipLaunchKernelGGL(KK, pgrid, pblock, lds_bytes_comp_pair<PP>(), s, sig_in,                                  \
                            (const long long*)frame_pos, frame_left, frame_right, (const RunDesc*)runs, slot_off,     \
