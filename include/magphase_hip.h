@@ -967,6 +967,50 @@ int mpx_mlpg_trajectory_nll_backward(void* stream, const void* mean, int32_t mea
                                      int32_t n_utts, int64_t total_frames, int32_t D, int32_t n_win, const double* windows,
                                      double* g_mean, int64_t ld_gm, double* g_var, int64_t ld_gv, double* work);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Acoustic composition (magphase_cmp.hip): the inverse of MLPG's stream split.  No counterpart in
+ * the reference but la.interp_unv_regions (libaudio.py:273-291), the interpolation of the carried stream.
+ *
+ * The layout: n_streams <= 16 streams of dims[s] >= 1 columns (dims: HOST int32).  The static matrix x [total_frames x SD],
+ * SD = sum dims, holds their statics side by side; a composed row has W = K SD + vuv columns, K = n_win + 1 (n_win 0, 1 or
+ * 2; windows: HOST float64 [n_win x 3] taps (w[-1], w[0], w[+1])): stream s as [static | delta | acc] from column
+ * K (dims[0] + ... + dims[s - 1]), then one voicing column.  utt_frame_off: device int32 [n_utts + 1].  interp_stream: the
+ * stream carried through unvoiced frames (every column of it), or -1.  Every entry returns 0 without a launch for
+ * total_frames == 0 or n_utts == 0, and MPX_ERR_ARG for null or inconsistent arguments.
+ *
+ * mpx_cmp_voiced_neighbours: frame t of an utterance is voiced where v[(row0 + t) ld_v] > 0 (float32 / float64; NaN:
+ * unvoiced).  nb: device int32 [2 x total_frames]: nb[r] = the last voiced frame <= t, nb[total_frames + r] = the first
+ * voiced frame >= t, utterance-relative, -1 without one.
+ *
+ * mpx_cmp_compose: out[r, c] = ((sum_j w_k[j] x~[t + j, .]) - mean[c]) / std[c], taps outside the utterance dropped; x~ = x
+ * but in the carried stream, where an unvoiced frame holds the line through the voiced frames on either side, the nearest
+ * voiced value before the first / after the last, unv_fill without any (interp_zeros: 0 in every unvoiced frame); the
+ * voicing column is 1 in voiced frames, else 0.  The value stored in an unvoiced entry of the carried stream is never
+ * loaded.  mean, std: device float64 [W], or both null.  Float64 arithmetic without fused multiply-adds, one rounding on
+ * the store; out: float32 (out_f64: float64) [total_frames x W] at row pitch ld_out.
+ *
+ * mpx_cmp_compose_backward: gx [total_frames x SD] (float64) = the gradient of sum g . out with respect to x; g: float32
+ * [total_frames x W].  Unvoiced entries of the carried stream get exactly 0.  One writer per element, no atomics.
+ *
+ * mpx_cmp_column_moments: out[0] = total_frames, out[1 .. 1 + width) = the column sums, out[1 + width .. 1 + 2 width) = the
+ * sums of (x - sum / total_frames)^2, each summed over tiles of 128 rows in ascending order, then over the tiles in
+ * ascending order (mpx_mlpg_column_sums' order).  work: float64 [mpx_cmp_moments_work_doubles(total_frames, width)].
+ * ------------------------------------------------------------------------------------------------------------------ */
+int mpx_cmp_voiced_neighbours(void* stream, const void* v, int32_t v_f64, int64_t ld_v, const int32_t* utt_frame_off,
+                              int32_t n_utts, int64_t total_frames, int32_t* nb);
+int mpx_cmp_compose(void* stream, const void* x, int32_t x_f64, int64_t ld_x, const int32_t* dims, int32_t n_streams,
+                    int32_t interp_stream, int32_t interp_zeros, double unv_fill, int32_t vuv, const int32_t* nb,
+                    const int32_t* utt_frame_off, int32_t n_utts, int64_t total_frames, int32_t n_win,
+                    const double* windows, const double* mean, const double* std_dev, void* out, int32_t out_f64,
+                    int64_t ld_out);
+int mpx_cmp_compose_backward(void* stream, const float* g, int64_t ld_g, const int32_t* dims, int32_t n_streams,
+                             int32_t interp_stream, int32_t vuv, const int32_t* nb, const int32_t* utt_frame_off,
+                             int32_t n_utts, int64_t total_frames, int32_t n_win, const double* windows,
+                             const double* std_dev, double* gx, int64_t ld_gx);
+int64_t mpx_cmp_moments_work_doubles(int64_t total_frames, int64_t width);
+int mpx_cmp_column_moments(void* stream, const void* x, int32_t x_f64, int64_t ld_x, int64_t total_frames, int64_t width,
+                           double* out, double* work);
+
 /*
  * MagPhase post-filter (magphase.py:2300-2378, Q20) on [n_frames x dim] log-mel magnitudes.  half_len: int32
  * [nx_last - nx_first + 1] half lengths of the centred moving average of bins nx_first..nx_last (host table,

@@ -139,6 +139,12 @@ PROTOTYPES = {
     "mpx_mlpg_nll_work_doubles": (i64, [i64, i32]),
     "mpx_mlpg_trajectory_nll_backward": (i32, [vp, vp, i32, i64, vp, i32, i64, vp, i64, vp, i32, i64, vp, vp, i32, i64,
                                                i32, i32, vp, vp, i64, vp, i64, vp]),
+    "mpx_cmp_voiced_neighbours": (i32, [vp, vp, i32, i64, vp, i32, i64, vp]),
+    "mpx_cmp_compose": (i32, [vp, vp, i32, i64, vp, i32, i32, i32, f64, i32, vp, vp, i32, i64, i32, vp, vp, vp, vp, i32,
+                              i64]),
+    "mpx_cmp_compose_backward": (i32, [vp, vp, i64, vp, i32, i32, i32, vp, vp, i32, i64, i32, vp, vp, vp, i64]),
+    "mpx_cmp_moments_work_doubles": (i64, [i64, i64]),
+    "mpx_cmp_column_moments": (i32, [vp, vp, i32, i64, i64, i64, vp, vp]),
 }
 SYMBOLS = tuple(PROTOTYPES)
 # mpx_roundtrip_lossless_ola_flags: how the feature rows are stored (MPX_RT_STORE_ROWS, by line, MPX_RT_STORE_NT), by the

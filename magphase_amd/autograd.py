@@ -28,6 +28,9 @@ synthesize_from_mag           MagnitudeSynthesisPlan.run, Engine.output_hpf     
 min_phase                     Engine.min_phase_rows -> .min_phase_backward        the magnitudes (not where m<=0)  3.3o
 post_filter                   Engine.post_filter[_merlin]                         the log-mel magnitudes | fs,     3.3p
                                 -> Engine.post_filter[_merlin]_backward             pf_coef, av_* / boost_*
+acoustic_compose              Engine.cmp_pack, .cmp_neighbours, .cmp_compose      every stream's statics (unvoiced 3.3q
+                                -> Engine.cmp_compose_backward                      lf0: 0) | voicing, norm,
+                                                                                    windows, unv_fill
 
 No double backward.  synthesis_from_compressed_batch with per_phase_type 'min_phase' / 'linear' (synthesis_from_mag_batch
 is the differentiable form) and any synthesis with a post-filter, with pcm16_norm or with prepared= have no backward
@@ -501,6 +504,60 @@ class _PostFilter(torch.autograd.Function):
                 ctx.saved_tensors   # (none kept; raises as torch does when the graph was freed)
                 g = ctx.engine.post_filter_backward(grad_out, ctx.fs, **ctx.kw)
         return (None,) * n_head + _scatter(g, ctx.offs, ctx.like, ctx.needs_input_grad[n_head:])
+
+
+class _AcousticCompose(torch.autograd.Function):
+    """forward(engine, dims, interp, vuv, windows, norm, unv_fill, *mats): mats = the streams of mp.acoustic_compose_batch,
+    utterance-major, len(dims) per utterance ([F_i x dims[s]] tensors or host arrays).  Engine.cmp_pack,
+    Engine.cmp_neighbours and Engine.cmp_compose are the forward, Engine.cmp_compose_backward (ONE
+    mpx_cmp_compose_backward launch) the backward.  Output: the ONE float32 [sum F_i x W] buffer of composed rows (the
+    per-utterance results are row views of it).  Kept: the neighbour table, the frame offsets and std -- the composition
+    is linear in the voiced statics, so the statics themselves are not."""
+
+    @staticmethod
+    def forward(ctx, engine, dims, interp, vuv, windows, norm, unv_fill, *mats):
+        import numpy as np
+
+        k = len(dims)
+        utts = [list(mats[i:i + k]) for i in range(0, len(mats), k)]
+        x, offs = engine.cmp_pack(utts, dims)
+        offs_dev = engine.to_device(offs.astype(np.int32), np.int32)
+        nb = engine.cmp_neighbours(x[:, int(sum(dims[:interp]))], offs_dev) if interp >= 0 else None
+        mean, std = engine._cmp_norm(norm, (int(windows.shape[0]) + 1) * int(sum(dims)) + int(vuv))
+        out = engine.cmp_compose(x, nb, offs_dev, dims, interp, vuv, windows, norm=norm and (mean, std), unv_fill=unv_fill)
+        ctx.engine, ctx.dims, ctx.interp, ctx.vuv, ctx.windows = engine, dims, interp, vuv, windows
+        ctx.offs = [int(o) for o in offs]
+        ctx.like = _like(mats)
+        ctx.has_nb, ctx.has_std = nb is not None, std is not None
+        ctx.save_for_backward(offs_dev, *([nb] if nb is not None else []), *([std] if std is not None else []))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        saved = list(ctx.saved_tensors)
+        offs_dev = saved.pop(0)
+        nb = saved.pop(0) if ctx.has_nb else None
+        std = saved.pop(0) if ctx.has_std else None
+        n_head = 7   # engine, dims, interp, vuv, windows, norm, unv_fill
+        grad_out = _coerce(grad_out, unit_cols=True)
+        with torch.cuda.device(grad_out.device):
+            gx = ctx.engine.cmp_compose_backward(grad_out, nb, offs_dev, ctx.dims, ctx.interp, ctx.vuv, ctx.windows, std=std)
+        cols = _offsets(ctx.dims)
+        g = tuple(gx[:, a:b] for a, b in zip(cols[:-1], cols[1:]))
+        return (None,) * n_head + _scatter(g, ctx.offs, ctx.like, ctx.needs_input_grad[n_head:])
+
+
+def acoustic_compose(engine, utts, dims, interp, vuv, windows, norm, unv_fill):
+    """The composed rows of utts (per utterance the list of its streams' [F_i x dims[s]] operands), differentiable with
+    respect to the streams that are tensors requiring grad.  -> (the float32 [sum F_i x W] buffer with grad_fn, the row
+    offsets)."""
+    import numpy as np
+
+    out = _AcousticCompose.apply(engine, list(dims), int(interp), bool(vuv), windows, norm, float(unv_fill),
+                                 *[m for u in utts for m in u])
+    offs = np.concatenate(([0], np.cumsum([int(u[0].shape[0]) for u in utts]))).astype(np.int64)
+    return out, offs
 
 
 def post_filter(engine, mats, pf_type, fs, opts):

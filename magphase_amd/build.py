@@ -28,7 +28,7 @@ UNITS = ["magphase_f64.hip", "magphase_warp.hip", "magphase_comp.hip", "magphase
          "magphase_grad_comp.hip", "magphase_grad_minphase.hip",
          "magphase_true_env.hip", "magphase_plan.cpp", "magphase_mtjump.cpp", "magphase_output.hip", "magphase_host.cpp",
          "magphase_epochs.hip", "magphase_noise.hip", "magphase_pack.hip", "magphase_probe.hip", "magphase_type2.hip",
-         "magphase_merlin.hip", "magphase_mlpg.hip", "magphase_gl.hip"]
+         "magphase_merlin.hip", "magphase_mlpg.hip", "magphase_gl.hip", "magphase_cmp.hip"]
 SRCS = [os.path.join(CSRC, u) for u in UNITS]
 SRC = os.path.join(CSRC, "magphase_hip.hip")
 HEADERS = [os.path.join(CSRC, "wave_fft.hpp"), os.path.join(CSRC, "wave_fft_f64.hpp"),

@@ -1773,6 +1773,133 @@ class Engine:
             o += d
         return g, (gsum if glob else gv)
 
+    # ------------------------------------------------------------------ acoustic composition
+    def cmp_pack(self, utts, dims):
+        """The statics of a batch as ONE device matrix [sum F_i x sum dims] (streams side by side) and the row offsets
+        int64 [n + 1].  utts: per utterance the list of [F_i x dims[s]] operands (hostmath.cmp_operand).  Host arrays go up
+        in one copy (float64 unless all are float32); device tensors without a float64 one among them are gathered by
+        mpx_rows_pack into float32 rows (three streams per launch; float16 / bfloat16 widen exactly); anything else is
+        copied block by block into a float64 matrix, as mlpg_pack does."""
+        torch = _torch()
+        offs = np.concatenate(([0], np.cumsum([int(u[0].shape[0]) for u in utts]))).astype(np.int64)
+        total, SD = int(offs[-1]), int(sum(dims))
+        cols = np.concatenate(([0], np.cumsum(dims))).astype(int)
+        flat = [m for u in utts for m in u]
+        is_t = [torch.is_tensor(m) for m in flat]
+        f64 = any((m.dtype == torch.float64) if t else (m.dtype == np.float64) for m, t in zip(flat, is_t))
+        dt, ndt = (torch.float64, np.float64) if f64 else (torch.float32, np.float32)
+        if total == 0:
+            return torch.empty((0, SD), dtype=dt, device=self.device), offs
+        if not any(is_t):
+            host = np.concatenate([np.concatenate([np.asarray(m, dtype=ndt) for m in u], axis=1) for u in utts], axis=0)
+            return self.to_device(host, ndt).view(total, SD), offs
+        buf = torch.empty((total, SD), dtype=dt, device=self.device)
+        if all(is_t) and not f64:
+            for s0 in range(0, len(dims), 3):
+                ss = range(s0, min(s0 + 3, len(dims)))
+                self.pack_rows([[u[s] for u in utts] for s in ss], [buf[:, cols[s]:cols[s + 1]] for s in ss])
+            return buf, offs
+        for u, a, b in zip(utts, offs[:-1], offs[1:]):
+            if b > a:
+                for s, m in enumerate(u):
+                    t = torch.is_tensor(m)
+                    src = m.detach() if t else torch.from_numpy(np.ascontiguousarray(m, dtype=ndt))
+                    buf[int(a):int(b), cols[s]:cols[s + 1]].copy_(src, non_blocking=t)
+        return buf, offs
+
+    @staticmethod
+    def _cmp_layout_args(dims, windows):
+        n_win = 0 if windows is None else int(windows.shape[0])
+        wins = (ctypes.c_double * (3 * n_win))(*[float(v) for v in windows.reshape(-1)]) if n_win else None
+        return (ctypes.c_int32 * len(dims))(*[int(d) for d in dims]), len(dims), n_win, wins
+
+    def cmp_neighbours(self, v, offs_dev, out=None):
+        """ONE mpx_cmp_voiced_neighbours launch (k_cmp_neighbours).  v: device float32 / float64 [total] (any element
+        stride: a column of a matrix) or [total x 1]; voiced where v > 0.  -> int32 [2 x total]: row 0 the last voiced
+        frame at or before each frame, row 1 the first at or after it (utterance-relative, -1: none)."""
+        torch = _torch()
+        if v.dim() == 2:
+            v = v[:, 0]
+        if v.dtype not in (torch.float32, torch.float64) or v.dim() != 1:
+            raise TypeError("cmp_neighbours: a float32 / float64 vector expected")
+        total = int(v.shape[0])
+        if out is None:
+            out = torch.empty((2, total), dtype=torch.int32, device=self.device)
+        if out.dtype != torch.int32 or tuple(out.shape) != (2, total) or not out.is_contiguous():
+            raise ValueError("cmp_neighbours: out must be a contiguous int32 [2 x %d]" % total)
+        self.launch("mpx_cmp_voiced_neighbours", v, int(v.dtype == torch.float64), max(int(v.stride(0)), 1) if total > 1
+                    else 1, offs_dev, int(offs_dev.numel()) - 1, total, out)
+        return out
+
+    def _cmp_norm(self, norm, W):
+        if norm is None:
+            return None, None
+        torch = _torch()
+        out = []
+        for v in norm:
+            v = self.to_device(v, np.float64) if isinstance(v, np.ndarray) else v.detach().to(torch.float64).contiguous()
+            if v.dim() != 1 or int(v.numel()) != W:
+                raise ValueError("cmp: mean and std are vectors of %d values" % W)
+            out.append(v)
+        return tuple(out)
+
+    def cmp_compose(self, x, nb, offs_dev, dims, interp, vuv, windows, norm=None, unv_fill=0.0, zeros=False,
+                    out=None, out_f64=False):
+        """ONE mpx_cmp_compose launch (k_cmp_compose).  x: device [total x sum dims] statics (float32 / float64, any row
+        pitch); nb: cmp_neighbours' table (None without a carried stream); dims: the streams' dimensions; interp: the
+        carried stream or -1; windows: hostmath.mlpg_windows(...) or None (statics only); norm: (mean, std) float64 [W]
+        (host or device) or None.  -> out, float32 (out_f64: float64) [total x W] (given: a view with unit column stride,
+        written in place)."""
+        torch = _torch()
+        total, SD = int(x.shape[0]), int(sum(dims))
+        x64, ld_x = self._mlpg_operand(x, SD, "cmp: x", total)
+        c_dims, n_streams, n_win, wins = self._cmp_layout_args(dims, windows)
+        W = (n_win + 1) * SD + int(bool(vuv))
+        odt = torch.float64 if out_f64 else torch.float32
+        if out is None:
+            out = torch.empty((total, W), dtype=odt, device=self.device)
+        if out.dtype != odt or out.dim() != 2 or tuple(out.shape) != (total, W) or (W > 1 and out.stride(1) != 1):
+            raise ValueError("cmp: out must be a %s [%d x %d] matrix with unit column stride" % (odt, total, W))
+        ld_o = int(out.stride(0)) if total > 1 else max(int(out.stride(0)), W)
+        if nb is not None and (nb.dtype != torch.int32 or tuple(nb.shape) != (2, total) or not nb.is_contiguous()):
+            raise ValueError("cmp: nb must be a contiguous int32 [2 x %d]" % total)
+        mean, std = self._cmp_norm(norm, W)
+        self.launch("mpx_cmp_compose", x, x64, ld_x, c_dims, n_streams, int(interp), int(bool(zeros)), float(unv_fill),
+                    int(bool(vuv)), nb, offs_dev, int(offs_dev.numel()) - 1, total, n_win, wins, mean, std, out,
+                    int(bool(out_f64)), ld_o)
+        return out
+
+    def cmp_compose_backward(self, grad_out, nb, offs_dev, dims, interp, vuv, windows, std=None):
+        """ONE mpx_cmp_compose_backward launch (k_cmp_compose_bwd): grad_out float32 [total x W] (unit column stride) ->
+        the gradient of the statics, float64 [total x sum dims]; unvoiced entries of the carried stream get exactly 0."""
+        torch = _torch()
+        total, SD = int(grad_out.shape[0]), int(sum(dims))
+        c_dims, n_streams, n_win, wins = self._cmp_layout_args(dims, windows)
+        W = (n_win + 1) * SD + int(bool(vuv))
+        g64, ld_g = self._mlpg_operand(grad_out, W, "cmp: grad_out", total)
+        if g64:
+            raise TypeError("cmp: grad_out must be float32")
+        if std is not None:
+            std = self._cmp_norm((std,), W)[0]
+        gx = torch.empty((total, SD), dtype=torch.float64, device=self.device)
+        self.launch("mpx_cmp_compose_backward", grad_out, ld_g, c_dims, n_streams, int(interp), int(bool(vuv)), nb, offs_dev,
+                    int(offs_dev.numel()) - 1, total, n_win, wins, std, gx, SD)
+        return gx
+
+    def cmp_column_moments(self, x, out=None):
+        """ONE mpx_cmp_column_moments call (k_cmp_moment_tiles, k_cmp_moment_final): x device [total x W] (float32 /
+        float64, any row pitch) -> float64 [1 + 2 W] = (count, column sums, centred sums of squares) in a fixed order."""
+        torch = _torch()
+        total, W = int(x.shape[0]), int(x.shape[1])
+        x64, ld = self._mlpg_operand(x, W, "cmp: x", total)
+        if out is None:
+            out = torch.zeros(1 + 2 * W, dtype=torch.float64, device=self.device)
+        if out.dtype != torch.float64 or int(out.numel()) != 1 + 2 * W or not out.is_contiguous():
+            raise ValueError("cmp: out must be %d contiguous float64" % (1 + 2 * W))
+        work = torch.empty(int(self.lib.mpx_cmp_moments_work_doubles(total, W)), dtype=torch.float64, device=self.device)
+        self.launch("mpx_cmp_column_moments", x, x64, ld, total, W, out, work)
+        return out
+
     def warp_mag_matrix(self, mag_dim, H, alpha, b_mag_fbank_mel=False):
         """Device-resident [mag_dim x H] matrix of the magnitude compression and the name of the C entry point that goes
         with it: the cepstral mel warp (la.sp_mel_warp, mpx_mel_warp) or the mel filter bank (la.sp_mel_warp_fbank,

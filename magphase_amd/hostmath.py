@@ -1591,3 +1591,120 @@ def mlpg_layout(layout, vuv, K, what="mlpg_streams_batch"):
         streams.append((c, d))
         c += K * d
     return layout, streams, c + (1 if vuv else 0)
+
+
+# ---------------------------------------------------------------------------------------------
+# Acoustic composition: argument checks of the public functions, all before any device call
+# ---------------------------------------------------------------------------------------------
+CMP_MAX_STREAMS = 16     # the layout travels to the kernels by value (magphase_cmp.hip: CmpLayout)
+_VOI_OPS = {">": np.greater, ">=": np.greater_equal, "<": np.less, "<=": np.less_equal, "==": np.equal,
+            "!=": np.not_equal}
+
+
+def cmp_voi_cond(voi_cond):
+    """la.interp_unv_regions' voi_cond, '<op><number>' (the reference evaluates 'v_voi ' + voi_cond) -> (numpy
+    comparison, number).  No eval."""
+    import re
+
+    m = re.fullmatch(r"\s*(>=|<=|==|!=|>|<)\s*([-+]?(?:\d+\.?\d*|\.\d+)(?:[eE][-+]?\d+)?)\s*", str(voi_cond))
+    if m is None:
+        raise ValueError("voi_cond: '<op><number>' expected (op one of > >= < <= == !=), got %r" % (voi_cond,))
+    return _VOI_OPS[m.group(1)], float(m.group(2))
+
+
+def cmp_operand(m, name, dim, lf0=False):
+    """One stream of one utterance as acoustic_compose_batch takes it -> a 2-D [F x dim] host array (float32 / float64) or
+    device tensor (float16 / bfloat16 / float32 / float64, unit column stride).  A vector is a [F x 1] matrix.  TypeError:
+    not a float dtype; ValueError: shape, width, a float16 lf0 (check_feature_tensor's rule)."""
+    import sys
+
+    torch = sys.modules.get("torch")
+    if torch is not None and torch.is_tensor(m):
+        if not m.dtype.is_floating_point:
+            raise TypeError("%s: dtype %s is not a float dtype" % (name, m.dtype))
+        if m.dim() == 1 and dim == 1:
+            m = m.unsqueeze(1)
+        check_feature_tensor(m, name)
+        if lf0 and m.dtype == torch.float16:
+            raise ValueError("%s: a float16 lf0 cannot hold the unvoiced marker -1e10 (float32, bfloat16 or float64)" % name)
+        if m.device.type == "cpu":
+            m = m.detach()
+            m = (m.float() if m.dtype in (torch.float16, torch.bfloat16) else m).numpy()
+        elif m.shape[1] > 1 and m.stride(1) != 1:
+            m = m.contiguous()
+    else:
+        m = np.asarray(m)
+        if m.dtype.kind != "f":
+            raise TypeError("%s: dtype %s is not a float dtype" % (name, m.dtype))
+        if lf0 and m.dtype == np.float16:
+            raise ValueError("%s: a float16 lf0 cannot hold the unvoiced marker -1e10 (float32 or float64)" % name)
+        if m.dtype != np.float32:
+            m = m.astype(np.float64, copy=False)
+        if m.ndim == 1 and dim == 1:
+            m = m.reshape(-1, 1)
+        if m.ndim != 2:
+            raise ValueError("%s: must be 2-D [frames x %d], got %d-D" % (name, dim, m.ndim))
+    if int(m.shape[1]) != dim:
+        raise ValueError("%s: %d columns expected, got %d" % (name, dim, int(m.shape[1])))
+    return m
+
+
+def cmp_check(feats, layout, vuv, windows, unv_fill, what="acoustic_compose_batch"):
+    """Checks of acoustic_compose_batch.  feats: list of per-utterance tuples in layout order.  -> (layout, streams
+    [(first output column, dim)], W, windows [n_win x 3], feats as lists of 2-D operands, index of the 'lf0' stream or
+    -1).  The column map is mlpg_layout's."""
+    w = mlpg_windows(windows)
+    layout, streams, W = mlpg_layout(layout, vuv, w.shape[0] + 1, what)
+    if len(layout) > CMP_MAX_STREAMS:
+        raise ValueError("%s: at most %d streams" % (what, CMP_MAX_STREAMS))
+    if isinstance(unv_fill, bool) or not isinstance(unv_fill, (int, float)) or not np.isfinite(unv_fill):
+        raise ValueError("%s: unv_fill must be a finite number" % what)
+    if isinstance(feats, np.ndarray) or not isinstance(feats, (list, tuple)):
+        raise ValueError("%s: feats must be a list of per-utterance tuples %s" % (what, tuple(n for n, _ in layout)))
+    out = []
+    for u, f in enumerate(feats):
+        if isinstance(f, np.ndarray) or not isinstance(f, (list, tuple)) or len(f) != len(layout):
+            raise ValueError("%s: feats[%d] must be a tuple of %d streams %s"
+                             % (what, u, len(layout), tuple(n for n, _ in layout)))
+        ops = [cmp_operand(m, "%s: feats[%d] (%s)" % (what, u, n), d, lf0=(n == "lf0"))
+               for m, (n, d) in zip(f, layout)]
+        if any(int(m.shape[0]) != int(ops[0].shape[0]) for m in ops):
+            raise ValueError("%s: feats[%d]: the streams have %s frames" % (what, u, [int(m.shape[0]) for m in ops]))
+        out.append(ops)
+    interp = next((i for i, (n, d) in enumerate(layout) if n == "lf0" and d == 1), -1)
+    return layout, streams, W, w, out, interp
+
+
+def cmp_norm(norm, W, what="acoustic_compose_batch"):
+    """norm=(mean, std): two [W] vectors (host arrays -> float64 arrays; device tensors stay, as float64).  std must be
+    finite and > 0, mean finite (ValueError)."""
+    import sys
+
+    if norm is None:
+        return None
+    if isinstance(norm, np.ndarray) or not isinstance(norm, (list, tuple)) or len(norm) != 2:
+        raise ValueError("%s: norm must be (mean, std)" % what)
+    torch = sys.modules.get("torch")
+    out = []
+    for name, v in zip(("mean", "std"), norm):
+        if torch is not None and torch.is_tensor(v):
+            if not v.dtype.is_floating_point:
+                raise TypeError("%s: norm %s: dtype %s is not a float dtype" % (what, name, v.dtype))
+            v = v.detach().double()
+            if v.device.type == "cpu":
+                v = v.numpy()
+        else:
+            v = np.asarray(v)
+            if v.dtype.kind not in "fiu":
+                raise TypeError("%s: norm %s: dtype %s is not a real dtype" % (what, name, v.dtype))
+            v = v.astype(np.float64)
+        if len(v.shape) != 1 or int(v.shape[0]) != W:
+            raise ValueError("%s: norm %s must be a vector of %d values" % (what, name, W))
+        if isinstance(v, np.ndarray):
+            ok = np.all(np.isfinite(v)) and (name == "mean" or np.all(v > 0))
+        else:
+            ok = bool(torch.isfinite(v).all()) and (name == "mean" or bool((v > 0).all()))
+        if not ok:
+            raise ValueError("%s: norm %s must be finite%s" % (what, name, "" if name == "mean" else " and > 0"))
+        out.append(v)
+    return tuple(out)

@@ -587,3 +587,61 @@ def spectral_smoothing_rceps(m_sp_log, nc_total=60, fade_to_total=0.2):
     e = get_engine()
     out, _, _ = e.true_envelope([m], "db", int(nc_total), 0.0, fade=float(fade_to_total), max_iters=1)
     return e.to_host_f64(out[:, :H])
+
+
+# -------------------------------------------------------------------------------------------------
+# libaudio.py:273-291 on the device (k_cmp_neighbours, k_cmp_compose)
+# -------------------------------------------------------------------------------------------------
+def interp_unv_regions_batch(l_m_data, l_v_voi, voi_cond=">0", interp_type="linear", engine=None):
+    """
+    la.interp_unv_regions for many utterances in ONE launch of k_cmp_neighbours and k_cmp_compose.  l_m_data: list of
+    [F_i x n] matrices or [F_i] vectors (host arrays or device tensors, float32 / float64; one n per call); l_v_voi: the
+    voicing vectors [F_i]; voi_cond: '<op><number>' (parsed, never evaluated as code); interp_type 'linear' / 'slinear'
+    (the same thing) or 'zeros'.  Returns float64 host arrays of the inputs' shapes.  A row that is not voiced is never
+    read: NaN or -1e10 there does not reach the result ('zeros' gives an exact 0 where the reference multiplies by 0).
+    Departures from the reference: an utterance with ONE voiced row holds that row everywhere (the reference: NaN at that
+    row, a 0 / 0 in scipy); without any voiced row: ValueError (the reference: IndexError).
+    NotImplementedError: another interp_type.
+    """
+    if interp_type not in ("linear", "slinear", "zeros"):
+        raise NotImplementedError("interp_unv_regions: interp_type %r ('linear', 'slinear' or 'zeros')" % (interp_type,))
+    op, thr = hm.cmp_voi_cond(voi_cond)
+    if isinstance(l_m_data, np.ndarray) or not isinstance(l_m_data, (list, tuple)) or \
+            isinstance(l_v_voi, np.ndarray) or not isinstance(l_v_voi, (list, tuple)) or len(l_m_data) != len(l_v_voi):
+        raise ValueError("interp_unv_regions_batch: one data matrix and one voicing vector per utterance expected")
+    if not l_m_data:
+        return []
+    import torch
+
+    shapes = [tuple(int(s) for s in m.shape) for m in l_m_data]
+    n = 1 if len(shapes[0]) == 1 else shapes[0][-1]
+    mats = [hm._mlpg_matrix(m if len(m.shape) == 2 else m.reshape(-1, 1), "interp_unv_regions: data[%d]" % i, n)
+            for i, m in enumerate(l_m_data)]
+    masks = []
+    for i, (v, m) in enumerate(zip(l_v_voi, mats)):
+        v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        if v.ndim != 1 or v.shape[0] != int(m.shape[0]):
+            raise ValueError("interp_unv_regions: v_voi[%d] must be a vector of %d values" % (i, int(m.shape[0])))
+        with np.errstate(invalid="ignore"):
+            mk = op(v.astype(np.float64), thr)
+        if interp_type != "zeros" and not mk.any():
+            raise ValueError("interp_unv_regions: utterance %d has no voiced row" % i)
+        masks.append(mk.astype(np.float32))
+    from .engine import get_engine
+
+    e = engine or get_engine()
+    x, offs = e.mlpg_pack(mats, n)
+    total = int(offs[-1])
+    if total == 0:
+        return [np.zeros(s) for s in shapes]
+    offs_dev = e.to_device(offs.astype(np.int32), np.int32)
+    nb = e.cmp_neighbours(e.to_device(np.concatenate(masks), np.float32), offs_dev)
+    out = e.cmp_compose(x, nb, offs_dev, [n], 0, False, None, zeros=(interp_type == "zeros"), out_f64=True).cpu().numpy()
+    return [out[int(a):int(b)].reshape(s) for a, b, s in zip(offs[:-1], offs[1:], shapes)]
+
+
+def interp_unv_regions(m_data, v_voi, voi_cond=">0", interp_type="linear"):
+    """libaudio.py:273-291 on the device: [F x n] (or [F]) data carried through the rows where v_voi does not meet voi_cond
+    (linear between voiced rows, the nearest voiced row held at the ends; 'zeros': zero there).  See
+    interp_unv_regions_batch for the two departures from the reference."""
+    return interp_unv_regions_batch([m_data], [v_voi], voi_cond=voi_cond, interp_type=interp_type)[0]

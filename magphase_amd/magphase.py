@@ -2058,3 +2058,117 @@ def mlpg_streams_batch(cmps, var, layout=MLPG_LAYOUT, vuv=True, vuv_thres=0.5, w
     if not return_device:
         cols = [c.cpu().numpy() for c in cols]
     return [tuple(c[int(a):int(b)] for c in cols) for a, b in zip(offs[:-1], offs[1:])]
+
+
+# ---------------------------------------------------------------------------------------------
+# Acoustic composition: the rows an acoustic model is trained on -- the inverse of
+# mlpg_streams_batch.  Not the reference's code but for the interpolation of lf0, which is la.interp_unv_regions'.
+# ---------------------------------------------------------------------------------------------
+def _cmp_run(engine, utts, dims, interp, vuv, w, norm, unv_fill):
+    """The launches of acoustic_compose_batch -> (float32 device rows [sum F_i x W], row offsets)."""
+    x, offs = engine.cmp_pack(utts, dims)
+    offs_dev = engine.to_device(offs.astype(np.int32), np.int32)
+    nb = engine.cmp_neighbours(x[:, int(sum(dims[:interp]))], offs_dev) if interp >= 0 else None
+    return engine.cmp_compose(x, nb, offs_dev, dims, interp, vuv, w, norm=norm, unv_fill=unv_fill), offs
+
+
+def acoustic_compose_batch(feats, layout=MLPG_LAYOUT, vuv=True, windows=MLPG_WINDOWS, norm=None, unv_fill=0.0, engine=None,
+                           return_device=False):
+    """
+    The rows a Merlin-style acoustic model is trained on, composed on the device (k_cmp_neighbours, k_cmp_compose): what
+    mlpg_streams_batch takes apart again.  feats: list of per-utterance tuples in layout order -- with the default layout
+    (m_mag_mel_log, m_real_mel, m_imag_mel, v_lf0), what analysis_compressed_batch and mlpg_streams_batch return; each a
+    host array or a tensor on the engine's device, any float dtype (a float16 lf0 is refused: it cannot hold -1e10) and
+    any row stride; a stream of dimension 1 may be a vector.
+    Returns per utterance [F_i x W], W = K sum(dims) + (1 if vuv), K = 1 + len(windows): stream s as [static | delta | acc]
+    in its K dim_s columns, the streams in layout order, then the voicing column (hostmath.mlpg_layout's map) -- float64
+    host arrays, or with return_device float32 device tensors, row views of one buffer.
+    A stream named 'lf0' of dimension 1 is carried through unvoiced frames before its deltas are taken: voiced means
+    v_lf0 > 0 (NaN is unvoiced); between two voiced frames the value is linear in the frame index; before the first and
+    after the last voiced frame the nearest voiced value is held; an utterance without a voiced frame gets unv_fill.  An
+    utterance with exactly ONE voiced frame holds that value everywhere -- the one departure from the reference's
+    la.interp_unv_regions, which gives NaN at that frame (a 0 / 0 in scipy's interp1d).  The value stored in an unvoiced
+    entry (-1e10, NaN, anything) is never read.  The voicing column is 1.0 in voiced frames, else 0.0.
+    Deltas: the windows, taps and edge rule of dynamic_features_batch (taps outside the utterance are dropped), so
+    mlpg_streams_batch(acoustic_compose_batch(feats), var) returns the statics.
+    norm=(mean, std): two [W] vectors (host or device; AcousticStats.finalize()): the result is (y - mean) / std in every
+    column, the voicing column included (pass 0 and 1 there to keep it raw); std must be finite and > 0 (ValueError).
+    All arithmetic is float64, rounded once to float32 on the store.
+    ValueError / TypeError before any launch: a stream of the wrong width, streams of one utterance with different frame
+    counts, a dtype that is not a float dtype, bad windows, a bad layout.
+    Autograd: with return_device, grad mode on and a device input that requires grad the rows carry a grad_fn
+    (k_cmp_compose_bwd) and every stream's statics get a gradient in their own dtype and shape; unvoiced lf0 entries get
+    exactly 0.  Voicing, norm, windows and unv_fill are not differentiated; no double backward.
+    """
+    what = "acoustic_compose_batch"
+    layout, _streams, W, w, utts, interp = hm.cmp_check(feats, layout, vuv, windows, unv_fill, what)
+    norm = hm.cmp_norm(norm, W, what)
+    if not utts:
+        return []
+    dims = [d for _, d in layout]
+    engine = engine or get_engine()
+    import torch
+
+    for u in utts:
+        for m in u:
+            if torch.is_tensor(m) and m.device != engine.device:
+                raise ValueError("%s: tensor on %s, the engine runs on %s" % (what, m.device, engine.device))
+    flat = [m for u in utts for m in u]
+    if hm.wants_grad(return_device, flat):
+        from . import autograd
+
+        out, offs = autograd.acoustic_compose(engine, utts, dims, interp, bool(vuv), w, norm, float(unv_fill))
+    else:
+        out, offs = _cmp_run(engine, utts, dims, interp, bool(vuv), w, norm, float(unv_fill))
+    if not return_device:
+        out = engine.to_host_f64(out) if int(offs[-1]) else np.zeros((0, W))
+    return [out[int(a):int(b)] for a, b in zip(offs[:-1], offs[1:])]
+
+
+def acoustic_compose(m_mag_mel_log, m_real_mel, m_imag_mel, v_lf0, **kw):
+    """acoustic_compose_batch for one utterance with the default layout -> [F x W]."""
+    return acoustic_compose_batch([(m_mag_mel_log, m_real_mel, m_imag_mel, v_lf0)], **kw)[0]
+
+
+class AcousticStats:
+    """Corpus mean and standard deviation of composed rows for acoustic_compose_batch(norm=).  update(cmps) takes a list of
+    [F_i x width] matrices (host arrays or device tensors, float32 / float64): count, column sums and centred sums of
+    squares are computed on the device in one fixed order (k_cmp_moment_tiles / k_cmp_moment_final: the same input gives
+    the same bits on every run) and merged into the running totals on the host in float64 with Chan's formula.
+    finalize() -> (mean, std) float64 [width]: the population standard deviation; a zero-variance column gets std = 1.0
+    and so normalises to 0."""
+
+    def __init__(self, width):
+        if isinstance(width, bool) or not isinstance(width, (int, np.integer)) or width < 1:
+            raise ValueError("AcousticStats: width must be an integer >= 1")
+        self.width = int(width)
+        self.n = 0.0
+        self.sums = np.zeros(self.width)
+        self.m2 = np.zeros(self.width)
+
+    def update(self, cmps, engine=None):
+        if isinstance(cmps, np.ndarray) or not isinstance(cmps, (list, tuple)):
+            raise ValueError("AcousticStats.update: a list of [frames x %d] matrices expected" % self.width)
+        mats = [hm._mlpg_matrix(m, "AcousticStats.update: cmps[%d]" % i, self.width) for i, m in enumerate(cmps)]
+        if not mats or sum(int(m.shape[0]) for m in mats) == 0:
+            return self
+        engine = engine or get_engine()
+        x, _ = engine.mlpg_pack(mats, self.width)
+        res = engine.cmp_column_moments(x).cpu().numpy()
+        nb, sb, mb = float(res[0]), res[1:1 + self.width], res[1 + self.width:]
+        if self.n == 0:
+            self.n, self.sums, self.m2 = nb, sb.copy(), mb.copy()
+        else:
+            na = self.n
+            n = na + nb
+            delta = sb / nb - self.sums / na
+            self.m2 = self.m2 + mb + delta * delta * (na * nb / n)
+            self.sums = self.sums + sb
+            self.n = n
+        return self
+
+    def finalize(self):
+        if self.n == 0:
+            raise ValueError("AcousticStats.finalize: no frames seen")
+        std = np.sqrt(self.m2 / self.n)
+        return self.sums / self.n, np.where(std > 0, std, 1.0)
