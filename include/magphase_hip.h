@@ -627,8 +627,19 @@ int mpx_noise_stats_spectra(void* stream, int fft_len, const void* tables, const
  *                     interpolated by mpx_mel_unwarp_rows -- half the feature loads)
  *   win_left, win_right : anti-ringing window half lengths (Q14);  pm_rel : as mpx_ola_gather
  * per_v, ap_v, ap_u : float32[H] per-bin constants (hostmath.synthesis_bin_curves: tilt x sqrt(mask) etc., Q12/Q13)
- * n_per_bins : per_v[k] == 0 for k >= n_per_bins (the caller's promise; 0 or >= H: no promise): real / imag and per_v of those
- *              bins are not read (one row per frame form only).
+ * n_per_bins : per_v[k] == 0 for k >= n_per_bins (the caller's promise; 0 or > H: no promise, n_per_bins counts as H): those
+ *              bins have no periodic component.  One row per frame form: real / imag (and per_v) are read in whole groups of
+ *              64 bins, of VOICED frames only (the real / imag rows of unvoiced frames are not read at all).  With
+ *              Q = fft_len / 4 the groups are
+ *                [64 q, 64 q + 63]                 for every 64 q < min(n_per_bins, Q)        (the lanes' own bins),
+ *                [Q, Q + 63]                       when n_per_bins > Q                        (bin Q; the other 63 are loaded, not used),
+ *                [Q + 1 + 64 j, Q + 64 + 64 j]     for every j >= 0 with Q + 1 + 64 j < n_per_bins  (the mirror bins),
+ *              that is the leading hostmath.synth_comp_phase_columns(fft_len, n_per_bins) columns: n_per_bins rounded up to 64
+ *              while n_per_bins <= Q + 1 (every supported sample rate), Q + 1 + (n_per_bins - Q - 1 rounded up to 64) beyond,
+ *              at most H.  Every element of a group that is read must be finite -- a NaN or an infinity there reaches the
+ *              output even where per_v is 0 --; no other element of real / imag is read.
+ *              Row-table form: n_per_bins is not looked at; every bin of the rows row0[f] and row1[f] of mag, real and imag is
+ *              read for every frame, voiced or not, and must be finite.
  */
 int mpx_synth_comp_slots(void); /* wave slots of mpx_synthesis_compressed_ola on the current device */
 /* Relative speed of the compressed synthesis kernel's slots (see mpx_synth_ola_slot_weights). */

@@ -1204,7 +1204,10 @@ __global__ __launch_bounds__(kCompPairWaves * 64) void k_synth_comp_pair(const f
     #ifndef MPX_COMP_FEAT_ROWS
     #define MPX_COMP_FEAT_ROWS 16
     #endif
-            constexpr int HB = MPX_COMP_FEAT_ROWS;   // register rows per batch: 8 x HB loads in flight
+            // register rows per batch: 8 x HB loads in flight (P == 8 has fewer rows than a batch: one batch of P -- with
+            // HB == 16 the loop below ran P / HB == 0 times and fft_len 1024 with row tables skipped the assembly)
+            constexpr int HB = (P < MPX_COMP_FEAT_ROWS) ? P : MPX_COMP_FEAT_ROWS;
+            static_assert(P % HB == 0 && HB % 8 == 0, "the batches cover the P register rows, 8 at a time");
     #pragma unroll
             for (int h = 0; h < P / HB; ++h) {
                 float m0[HB], a0[HB], b0[HB], m1[HB], a1[HB], b1[HB], cpv[HB], cap[HB];

@@ -1067,6 +1067,20 @@ def _first_all_zero_from(v):
     return int(nz[-1]) + 1 if nz.size else 0
 
 
+def synth_comp_phase_columns(fft_len, n_per_bins):
+    """Leading columns of the real / imag rows that mpx_synthesis_compressed_ola (one row per frame) reads of a voiced
+    frame when it is given n_per_bins (include/magphase_hip.h): the kernel loads phase in whole 64-bin groups -- below
+    fft_len/4 the groups [64 q, 64 q + 63], above it the groups [fft_len/4 + 1 + 64 j, fft_len/4 + 64 + 64 j] (the mirror
+    bins of a lane's pair) -- so for n_per_bins <= fft_len/4 + 1 this is n_per_bins rounded up to 64, beyond it
+    fft_len/4 + 1 + (n_per_bins - fft_len/4 - 1 rounded up to 64), never more than fft_len/2 + 1.  What fills the rows for that
+    entry must write this many columns."""
+    H, Q = int(fft_len) // 2 + 1, int(fft_len) // 4
+    n = H if (n_per_bins <= 0 or n_per_bins > H) else int(n_per_bins)
+    if n <= Q + 1:
+        return min((n + 63) // 64 * 64, H)
+    return min(Q + 1 + (n - Q - 1 + 63) // 64 * 64, H)
+
+
 def post_filter_tables(mag_dim, fs, av_len_at_zero=None, av_len_at_nyq=None, boost_at_zero=None, boost_at_nyq=None):
     """
     Host tables of the MagPhase post-filter (magphase.py:2300-2347, Q20): defaults per sample rate (same warnings /

@@ -1319,7 +1319,8 @@ class CompressedSynthesisPlan:
         if self.unwarp_rows:   # constant -> variable rate inside the unwarp: one spectrum row per synthesis frame
             e.launch("mpx_mel_unwarp_rows", self.total_frames, H, a_mag, self.mag_dim, self.u_mag, mag, self.a_real,
                      self.a_imag, self.phase_dim, self.u_phase, real, imag, ld, self.row0, self.row1, self.rowt,
-                     self.n_rows, self.tile_first, self.voiced if magphase else None, self.n_per if magphase else 0)
+                     self.n_rows, self.tile_first, self.voiced if magphase else None,
+                     hm.synth_comp_phase_columns(N, self.n_per) if magphase else 0)   # every column the synthesis reads
         else:                   # variable-rate features: rows == frames
             e.launch("mpx_mel_unwarp", self.n_rows, H, a_mag, self.mag_dim, self.u_mag, mag, self.a_real, self.a_imag,
                      self.phase_dim, self.u_phase, real, imag, ld)
