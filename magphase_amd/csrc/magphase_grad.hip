@@ -48,6 +48,7 @@ __device__ __forceinline__ GradGeom grad_geom(const float* __restrict__ gy, long
 // gather masks by sample index, it never multiplies).
 template <int P>
 __device__ __forceinline__ void stage_grad_async(const GradGeom& g, int tile0, unsigned lds_byte, int lane) {
+    if (g.hi <= g.lo) return;   // nothing kept of the frame: no address is formed at all
     for (int c = 0; c < P; ++c) {
         const int n0 = tile0 + 64 * c;
         if (n0 + 64 <= g.lo || n0 >= g.hi) continue;   // wave-uniform
